@@ -10,8 +10,12 @@ random-init weights of the real architecture) are synthetic and resident in HBM 
 With N > 1 the token rows of the ONE clip are sharded over the ranks (strong scaling): K/V all-gather over RCCL per
 self-attention block, everything else token-local.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus
-  roofline     - dominant kernel (by time) of the timed region, HIP-event timed on the launch stream
+Prints ONE JSON line (rank 0) with the driver's contract keys.  A plain run does only what that line needs: set-up,
+warm-up, the timed steps and, with --dump-outputs DIR, the last timed step's outputs as DIR/<name>.npy (float32).
+--full adds the secondary figures, each outside the timed steps unless noted:
+  roofline     - dominant kernel (by time) of the timed region, HIP-event timed on the launch stream (event pairs inside
+                 the timed steps)
+  host_enqueue_ms_empty_queue, guidance_2, tokenizer, pass_measured (node_pass_measured with --node-pass), exchange (N > 1)
   cpu_baseline - the CPU oracle (oracle/dit_oracle.py, a bit-exact restatement of the reference's CPU path) timed on
                  this host's cores on a bounded sample (rank 0, N=1 only)
 """
@@ -118,6 +122,23 @@ def cpu_baseline(pkg, S_full, budget_s=40.0):
         sample = (f"1 of 28 blocks at S=2048 measured {t_small:.2f}s, scaled by the FLOP ratio to S={S_full} "
                   f"({est:.0f}s/block est.), x28")
     return {"value": 1.0 / (28.0 * t_blk), "unit": "steps/s", "cores": cores, "kind": "port", "sample": sample}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Each tensor as out_dir/<name>.npy in float32.  A tensor over its share of DUMP_LIMIT_BYTES is written as a fixed,
+    seeded sample of its flattened elements (the same positions on every run), so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays) // 4          # elements per array (4096 B: .npy header room)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 CONFIGS = {   # BASELINE.json configs that fit one node: (frames, height, width, default steps, default warm-up)
@@ -280,6 +301,11 @@ def main():
     ap.add_argument("--pass-steps", type=int, default=35, help="denoising steps of the measured pass (BASELINE: 35)")
     ap.add_argument("--node-pass", action="store_true",
                     help="also wall-clock the inverse node's call: 5 G-buffer passes stepped as one batch (nodes.py:187-213)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures (roofline, host enqueue, guidance 2, tokenizer, measured pass, exchange "
+                         "timers, CPU baseline); the --no-* options above trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32; seeded sample above 64 MB)")
     args = ap.parse_args()
     cf, ch, cw, cs, cwu = CONFIGS[args.config]
     args.frames = cf if args.frames is None else args.frames
@@ -287,6 +313,8 @@ def main():
     args.width = cw if args.width is None else args.width
     args.steps = cs if args.steps is None else args.steps
     args.warmup = cwu if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))          # before any GPU call
@@ -354,7 +382,7 @@ def main():
     model = pkg.model_diffusion_renderer.CleanDiffusionRendererModel(dict(cfg, net=net), device=dev, process_group=pg)
     model.load_state_dict(sd, strict=True)
     # small clips: the CPU baseline runs the WHOLE workload (4 steps of the full model), on a host copy of the same weights
-    full_cpu = (rank == 0 and world == 1 and not args.no_cpu_baseline and S <= 256 and args.blocks == 28)
+    full_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and S <= 256 and args.blocks == 28)
     sd_cpu = {k: v.cpu() for k, v in sd.items()} if full_cpu else None
     del sd
     torch.cuda.empty_cache()
@@ -365,10 +393,13 @@ def main():
     xt = (sw.synth_tensor("bench.noise", (1, 16, F_, h, w), torch.float32, device=dev, scale=1.7) * sig[0].item()).to(torch.bfloat16)
     cond = sw.synth_tensor("bench.cond", (1, 16, F_, h, w), torch.float32, device=dev, scale=1.0).to(torch.bfloat16)
 
+    last = {}
+
     def one_step(i, x):
         t = model.scheduler.timesteps[i]
         xs = model.scheduler.scale_model_input(x, timestep=t)
         out = model.net(x=xs, timesteps=t, latent_condition=cond, context_index=3)
+        last["net_output"] = out
         model.scheduler.current_step = i
         return model.scheduler.step(out, t, x).prev_sample
 
@@ -384,9 +415,9 @@ def main():
     # shapes are sampled evenly); bracketing every launch would add ~10 ms of queue time per step
     # (small shapes replay the forward as one hipGraph, where per-launch events do not apply: no roofline there)
     # (sharded runs: every 29th launch, the event pairs sit on rank 0 only and would skew its step against the other ranks)
-    timer = N.KernelTimer(sample_every=7 if world == 1 else 29) if (rank == 0 and S > 4096 and not os.environ.get("DRN_NO_TIMER")) else None
+    timer = N.KernelTimer(sample_every=7 if world == 1 else 29) if (args.full and rank == 0 and S > 4096 and not os.environ.get("DRN_NO_TIMER")) else None
     N.set_timer(timer)
-    xtimer = pkg.parallel.ExchangeTimer() if (pg is not None and rank == 0) else None      # (also the 1-rank RCCL rehearsal)
+    xtimer = pkg.parallel.ExchangeTimer() if (args.full and pg is not None and rank == 0) else None   # (also the 1-rank RCCL rehearsal)
     pkg.parallel.set_exchange_timer(xtimer)
     if pg is not None and world == 1:
         pkg.parallel.SINGLE_RANK_COLLECTIVES = True       # 1-rank rehearsal under torchrun: issue the RCCL calls anyway
@@ -407,20 +438,25 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         elapsed = tmax.item()
     assert torch.isfinite(xt.float()).all(), "non-finite latent"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": xt, "net_output": last["net_output"]})
+    last.clear()
     # the host's own cost of a step: ONE step enqueued on an EMPTY queue (nothing to wait for), outside the timed region.  The
     # loop figure above also contains the time the host spent blocked on the full HIP queue, i.e. mostly GPU time.
-    model.scheduler.set_timesteps(max(total, 2))
-    barrier()
-    h0 = time.perf_counter()
-    _x = one_step(0, xt)
-    host_empty_ms = 1e3 * (time.perf_counter() - h0)
-    barrier()
-    del _x
+    host_empty_ms = None
+    if args.full:
+        model.scheduler.set_timesteps(max(total, 2))
+        barrier()
+        h0 = time.perf_counter()
+        _x = one_step(0, xt)
+        host_empty_ms = 1e3 * (time.perf_counter() - h0)
+        barrier()
+        del _x
 
     # ---- secondary figure: the same step at the pipeline's default guidance 2.0 = cond + uncond forwards, which the
     #      sampler runs as ONE batch of two clips; one warm-up + two timed steps, outside the headline's timed region
     cfg_ms = None
-    if not args.no_cfg and world == 1:          # (sharded runs: headline only, nothing extra that could cost the line)
+    if args.full and not args.no_cfg and world == 1:      # (sharded runs: headline only, nothing extra that could cost the line)
         def cfg_step(i, x):
             t = model.scheduler.timesteps[i]
             xs = model.scheduler.scale_model_input(x, timestep=t)
@@ -441,7 +477,7 @@ def main():
     # ---- tokenizer leg (rank 0, outside the timed region): one encode + one decode of the full clip, for frames/s and the
     #      conv kernel's achieved HBM rate.  Random-init CV8x8x8 weights; synthetic RGB clip resident in HBM.
     tok, vae = None, None
-    if rank == 0 and not args.no_tokenizer:
+    if args.full and rank == 0 and not args.no_tokenizer:
         try:
             vae = pkg.CleanVAE.CleanVAE(state_dict=sw.synth_vae_state_dict(device=dev), device=dev)
             clip = sw.synth_tensor("bench.rgb", (1, 3, args.frames, args.height, args.width), torch.float32, device=dev).to(torch.bfloat16)
@@ -519,55 +555,55 @@ def main():
         ms = 1e3 * elapsed / args.steps
         steps_s = args.steps / elapsed
         fl_faithful, fl_exec = dit_flops(S, L=args.blocks), dit_flops(S, L=args.blocks, faithful=False)
-        summ = timer.summary() if timer is not None else {"gemm": {"launches": 1, "ms_total": 1.0, "ms_avg": 1.0, "flops": 0.0, "bytes": 0.0}}
-        dom = max(summ, key=lambda k: summ[k]["ms_total"])
-        d = summ[dom]
-        achieved = d["flops"] / (d["ms_total"] * 1e-3) / 1e12        # TFLOP/s over that kernel's launches
-        # L2-miss traffic per launch of that kernel family from the committed rocprofv3 PMC passes of this same command
-        # (FETCH_SIZE / WRITE_SIZE in separate runs, FETCH doubled per MI355X_MICROARCH.md); null if the profile is absent
-        traffic = None
-        try:
-            if S != 18432 or args.blocks != 28 or world != 1:
-                raise KeyError("profile was taken on the headline configuration only")
-            with open(os.path.join(ROOT, "profiles", TRAFFIC_PROFILE)) as f:
-                traffic = json.load(f)["families"][dom]["bytes_per_launch_corrected"]
-        except (OSError, KeyError, ValueError):
-            pass
-        roofline = {"bound": "mfma", "kernel": {"gemm": "gemm256s_kernel" if world == 1 else "gemm144_kernel", "attention": "attention16_fwd_kernel" if os.environ.get("DRN_ATT16", "1") != "0" else "attention_fwd_kernel"}[dom],
-                    "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                    "traffic_unit": "bytes/launch (L2-miss traffic incl. Infinity-Cache hits)",
-                    "traffic_source": f"profiles/{TRAFFIC_PROFILE}: committed rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this command, NOT "
-                                      "measured in this run (goes stale when a kernel changes)",
-                    "launches_per_step": d.get("launches_seen", d["launches"]) // args.steps, "launches_timed": d["launches"],
-                    "avg_launch_ms": round(d["ms_avg"], 4),
-                    "per_kernel": {k: {"tflops": round(v["flops"] / (v["ms_total"] * 1e-3) / 1e12, 1),
-                                       "ms_per_step": round(v["ms_avg"] * v.get("launches_seen", v["launches"]) / args.steps, 2)}
-                                   for k, v in summ.items()}}
-        if timer is None:
-            # small clips (S <= 4096): a forward is a weight stream (HBM roofline); per-launch event pairs would cost
-            # ~9 % of a 7 ms step, so the rate is the executed linears' weight bytes over the WHOLE step (a lower bound on the
-            # GEMM kernels' own rate)
-            wbytes = 12.0 * 4096 * 4096 * 2 * args.blocks
-            gbs = wbytes / (ms * 1e-3) / 1e9
-            roofline = {"bound": "hbm", "kernel": "few-token linears (gemm_tall_kernel, gemm256w_kernel slices)", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS,
-                        "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None,
-                        "note": "weight bytes of the executed linears / whole step time (no per-launch events at this size)"}
-            if S >= 1024:
-                # config 2 (S = 1024 / 2048): 256+ FLOP per weight byte x 4-8 -> the MFMA roofline; still no
-                # per-launch events (a pair costs ~35 us, 3 % of a 24 ms step): executed FLOPs over the whole step
-                tf = fl_exec / (ms * 1e-3) / 1e12
-                roofline = {"bound": "mfma", "kernel": "whole DiT step (GEMM tile kernels + attention_fwd_kernel)",
-                            "achieved": round(tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                            "frac": round(tf / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                            "note": "executed FLOPs / whole step time (no per-launch events at this size): a lower bound on "
-                                    "the MFMA kernels' own rate"}
+        if args.full:
+            summ = timer.summary() if timer is not None else {"gemm": {"launches": 1, "ms_total": 1.0, "ms_avg": 1.0, "flops": 0.0, "bytes": 0.0}}
+            dom = max(summ, key=lambda k: summ[k]["ms_total"])
+            d = summ[dom]
+            achieved = d["flops"] / (d["ms_total"] * 1e-3) / 1e12        # TFLOP/s over that kernel's launches
+            # L2-miss traffic per launch of that kernel family from the committed rocprofv3 PMC passes of this same command
+            # (FETCH_SIZE / WRITE_SIZE in separate runs, FETCH doubled per MI355X_MICROARCH.md); null if the profile is absent
+            traffic = None
+            try:
+                if S != 18432 or args.blocks != 28 or world != 1:
+                    raise KeyError("profile was taken on the headline configuration only")
+                with open(os.path.join(ROOT, "profiles", TRAFFIC_PROFILE)) as f:
+                    traffic = json.load(f)["families"][dom]["bytes_per_launch_corrected"]
+            except (OSError, KeyError, ValueError):
+                pass
+            roofline = {"bound": "mfma", "kernel": {"gemm": "gemm256s_kernel" if world == 1 else "gemm144_kernel", "attention": "attention16_fwd_kernel" if os.environ.get("DRN_ATT16", "1") != "0" else "attention_fwd_kernel"}[dom],
+                        "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                        "traffic_unit": "bytes/launch (L2-miss traffic incl. Infinity-Cache hits)",
+                        "traffic_source": f"profiles/{TRAFFIC_PROFILE}: committed rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this command, NOT "
+                                          "measured in this run (goes stale when a kernel changes)",
+                        "launches_per_step": d.get("launches_seen", d["launches"]) // args.steps, "launches_timed": d["launches"],
+                        "avg_launch_ms": round(d["ms_avg"], 4),
+                        "per_kernel": {k: {"tflops": round(v["flops"] / (v["ms_total"] * 1e-3) / 1e12, 1),
+                                           "ms_per_step": round(v["ms_avg"] * v.get("launches_seen", v["launches"]) / args.steps, 2)}
+                                       for k, v in summ.items()}}
+            if timer is None:
+                # small clips (S <= 4096): a forward is a weight stream (HBM roofline); per-launch event pairs would cost
+                # ~9 % of a 7 ms step, so the rate is the executed linears' weight bytes over the WHOLE step (a lower bound on the
+                # GEMM kernels' own rate)
+                wbytes = 12.0 * 4096 * 4096 * 2 * args.blocks
+                gbs = wbytes / (ms * 1e-3) / 1e9
+                roofline = {"bound": "hbm", "kernel": "few-token linears (gemm_tall_kernel, gemm256w_kernel slices)", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS,
+                            "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None,
+                            "note": "weight bytes of the executed linears / whole step time (no per-launch events at this size)"}
+                if S >= 1024:
+                    # config 2 (S = 1024 / 2048): 256+ FLOP per weight byte x 4-8 -> the MFMA roofline; still no
+                    # per-launch events (a pair costs ~35 us, 3 % of a 24 ms step): executed FLOPs over the whole step
+                    tf = fl_exec / (ms * 1e-3) / 1e12
+                    roofline = {"bound": "mfma", "kernel": "whole DiT step (GEMM tile kernels + attention_fwd_kernel)",
+                                "achieved": round(tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                                "frac": round(tf / PEAK_BF16_TFLOPS, 4), "traffic": None,
+                                "note": "executed FLOPs / whole step time (no per-launch events at this size): a lower bound on "
+                                        "the MFMA kernels' own rate"}
         out = {
             "metric": "denoising_steps_per_sec", "value": round(steps_s, 4), "unit": "steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 2), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "rccl_ranks": world,
             **({"transport": "gloo (rehearsal: ranks share one GPU, host-staged exchanges - not a measurement)"} if backend == "gloo" else {}),
-            "host_enqueue_ms_empty_queue": round(host_empty_ms, 2),
             "host_loop_wall_ms_per_step": round(1e3 * host_loop / args.steps, 2),
             "config": {"workload": f"inverse pass, {args.frames}f x {args.height} x {args.width} clip: EDM Euler step = 1 DiT "
                                    f"forward (D=4096, {args.blocks} blocks, 32 heads) over S={S} tokens, guidance 0",
@@ -578,8 +614,10 @@ def main():
             "dit_tflops_executed": round(fl_exec / (ms * 1e-3) / 1e12, 1),
             "mfma_frac_executed": round(fl_exec / (ms * 1e-3) / 1e12 / (PEAK_BF16_TFLOPS * world), 4),
             "frames_per_sec_35step_pass_dit_only": round(args.frames / (35 * ms * 1e-3), 3),
-            "roofline": roofline,
         }
+        if args.full:
+            out["host_enqueue_ms_empty_queue"] = round(host_empty_ms, 2)
+            out["roofline"] = roofline
         if xtimer is not None:
             # rank 0's view: time its compute stream waited in front of each exchange, per self-attention layer
             xs = xtimer.summary()
@@ -601,7 +639,7 @@ def main():
                 pass_measured["measured_over_composed"] = round(pass_measured["seconds"] / comp, 4)
         if node_measured is not None:
             out["node_pass_measured"] = node_measured
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_full(pkg, net, sd_cpu, (F_, h, w), 4) if sd_cpu is not None else cpu_baseline(pkg, S)
         print(json.dumps(out), flush=True)
     if pg is not None:

@@ -9,7 +9,6 @@ import torch
 
 from conftest import load_golden, tiny_net
 from oracle import dit_oracle as O
-from oracle.ref_import import reference_available
 
 CASES = [  # fixture, tag, D, L, heads, forward
     ("dit_tinyA.safetensors", "tinyA", 256, 1, 2, False),
@@ -95,25 +94,17 @@ def test_sampler_trajectory_goldens(pkg, fixture, tag):
     assert torch.equal(x0, gold["x0"])
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference not present (GPU box)")
 def test_oracle_equals_live_reference(pkg):
-    """Where /root/reference exists (build container), re-run it and compare live (not just via fixtures)."""
-    from oracle.ref_import import load_reference
-    import sys, os
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
-    ref = load_reference()
+    """A 2-block forward with inputs unlike the CASES ones (context index 4, odd latent width) against the output of the
+    reference model built as a user would (tests/golden/dit_live_tiny.safetensors, tools/make_goldens.py live_case)."""
+    gold, meta = load_golden("dit_live_tiny.safetensors")
     net = tiny_net(pkg, 256, 2, 2)
     sd = pkg.synthetic_weights.synth_state_dict(net, torch.bfloat16)
-    cfg = ref.config.get_inverse_renderer_config()
-    cfg["net"] = dict(net)
-    model = ref.model.CleanDiffusionRendererModel(cfg).to(torch.bfloat16)
-    model.load_state_dict(sd, strict=False)
     sw = pkg.synthetic_weights
     x = sw.synth_tensor("live.x", (1, 16, 1, 8, 12), torch.float32, scale=3.0).to(torch.bfloat16)
     cond = sw.synth_tensor("live.c", (1, 16, 1, 8, 12), torch.float32, scale=1.0).to(torch.bfloat16)
-    t = torch.tensor(0.37)
-    ci = torch.full((1, 1), 4, dtype=torch.long)
+    t = torch.tensor(float(meta["sigma"]))
+    ci = torch.full((1, 1), int(meta["context_index"]), dtype=torch.long)
     with torch.no_grad():
-        y_ref = model.net(x=x, timesteps=t, latent_condition=cond, context_index=ci)
         y = O.DitOracle(sd, net).forward(x, t, cond, ci)
-    assert torch.equal(y, y_ref)
+    assert torch.equal(y, gold["out.bf16"])

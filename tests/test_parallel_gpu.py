@@ -278,7 +278,7 @@ def test_bench_under_torchrun_one_rank_rccl(gpu, exchange):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "2", "--steps", "1",
-           "--warmup", "1", "--no-cpu-baseline", "--no-tokenizer", "--no-cfg"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-tokenizer", "--no-cfg"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

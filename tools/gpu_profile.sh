@@ -11,12 +11,12 @@ export TMPDIR=/tmp
 TICK=$!
 trap "kill $TICK" EXIT
 echo "--- kernel stats, cfg3 (headline) incl. the tokenizer leg"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $P/ks3 -o ks3 -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cfg --no-pass > $P/ks3.json 2> $P/ks3.err || { tail -5 $P/ks3.err; exit 3; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $P/ks3 -o ks3 -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cfg --no-pass > $P/ks3.json 2> $P/ks3.err || { tail -5 $P/ks3.err; exit 3; }
 tail -1 $P/ks3.json | cut -c1-300
 echo "--- kernel stats, cfg1"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $P/ks1 -o ks1 -- python3 bench.py --config cfg1 --steps 8 --warmup 2 --no-cpu-baseline --no-tokenizer --no-cfg > $P/ks1.json 2> $P/ks1.err || { tail -5 $P/ks1.err; exit 4; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $P/ks1 -o ks1 -- python3 bench.py --full --config cfg1 --steps 8 --warmup 2 --no-cpu-baseline --no-tokenizer --no-cfg > $P/ks1.json 2> $P/ks1.err || { tail -5 $P/ks1.err; exit 4; }
 tail -1 $P/ks1.json | cut -c1-300
-CMD="python3 bench.py --blocks 4 --steps 1 --warmup 1 --no-cpu-baseline --no-cfg --no-pass"
+CMD="python3 bench.py --full --blocks 4 --steps 1 --warmup 1 --no-cpu-baseline --no-cfg --no-pass"
 echo "--- FETCH_SIZE pass"
 timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $P/f -o f -- $CMD > $P/f.json 2> $P/f.err || { tail -5 $P/f.err; exit 5; }
 echo "--- WRITE_SIZE pass"

@@ -441,6 +441,42 @@ def vae_config_case():
     print("wrote", path)
 
 
+def configs_case(ref):
+    """The reference's configuration functions at the clip sizes the nodes use, as a settings-only JSON fixture."""
+    out = {"inverse_576x1024x57": ref.config.get_inverse_renderer_config(576, 1024, 57),
+           "forward_704x1280x57": ref.config.get_forward_renderer_config(704, 1280, 57),
+           "network": ref.config.get_network_config(),
+           "scheduler": ref.config.get_scheduler_config()}
+    path = os.path.join(GOLD, "reference_configs.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    with open(path) as f:
+        assert json.load(f) == out, "a config value does not survive JSON"
+    print("wrote", path)
+
+
+def live_case(ref):
+    """A 2-block DiT forward through the reference model built as a user would (fp32 construction, .to(bf16)), with inputs
+    unlike the dit_case ones (context index 4, an odd latent width); the oracle must match it bit for bit."""
+    net = dict(ref.config.get_inverse_renderer_config()["net"], model_channels=256, num_blocks=2, num_heads=2)
+    sd = sw.synth_state_dict(net, torch.bfloat16)
+    cfg = ref.config.get_inverse_renderer_config()
+    cfg["net"] = dict(net)
+    model = ref.model.CleanDiffusionRendererModel(cfg).to(torch.bfloat16)
+    model.load_state_dict(sd, strict=False)
+    x = sw.synth_tensor("live.x", (1, 16, 1, 8, 12), torch.float32, scale=3.0).to(torch.bfloat16)
+    cond = sw.synth_tensor("live.c", (1, 16, 1, 8, 12), torch.float32, scale=1.0).to(torch.bfloat16)
+    t = torch.tensor(0.37)
+    ci = torch.full((1, 1), 4, dtype=torch.long)
+    with torch.no_grad():
+        y = model.net(x=x, timesteps=t, latent_condition=cond, context_index=ci)
+        assert torch.equal(O.DitOracle(sd, net).forward(x, t, cond, ci), y), "oracle != reference"
+    meta = dict(META_COMMON, case="live", D="256", L="2", heads="2", latent=json.dumps([1, 8, 12]), sigma="0.37",
+                context_index="4", inputs="synth_tensor('live.x',(1,16,1,8,12),fp32,scale=3).to(bf16); "
+                                          "synth_tensor('live.c',...,scale=1).to(bf16)")
+    return {"out.bf16": y.contiguous()}, meta
+
+
 def save(name, tensors, meta):
     os.makedirs(GOLD, exist_ok=True)
     path = os.path.join(GOLD, name)
@@ -485,6 +521,10 @@ def main():
         vae_config_case()
     if want("cond"):
         save("conditions.safetensors", *conditions_case(ref))
+    if want("configs"):
+        configs_case(ref)
+    if want("live"):
+        save("dit_live_tiny.safetensors", *live_case(ref))
     if args.full and want("fullwidth"):
         for tag, (t, m) in full_width_cases(ref).items():
             save({"g4": "sampler_full28_cfg1_g4.safetensors"}.get(tag, f"dit_{tag}.safetensors"), t, m)

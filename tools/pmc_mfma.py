@@ -1,7 +1,7 @@
 """Fold a rocprofv3 counter pass of the bench command into MFMA utilisation per kernel -> profiles/rNN_pmc_mfma.json.
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES --kernel-trace \
-        --output-format csv -d gpurun_out/prof/m -o m -- python3 bench.py --blocks 4 --steps 1 --warmup 1 ...
+        --output-format csv -d OUT/m -o m -- python3 bench.py --full --blocks 4 --steps 1 --warmup 1 ...
     python tools/pmc_mfma.py <m_counter_collection.csv> [<m_kernel_trace.csv>] out.json
 
 What the counters are (rocprofiler-sdk counter_defs.yaml, gfx950): SQ_VALU_MFMA_BUSY_CYCLES = cycles the matrix pipe of a SIMD is

@@ -1,9 +1,9 @@
 """Fold two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; collected separately, MI355X_MICROARCH.md 'rocprofv3 PMC slots') of
 the bench command into per-kernel L2-miss traffic per launch -> profiles/rNN_pmc_traffic.json (read by bench.py's roofline).
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_f -o f -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-cfg
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_w -o w -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-cfg
-    python tools/pmc_traffic.py gpurun_out/pmc_f/.../f_counter_collection.csv gpurun_out/pmc_w/.../w_counter_collection.csv [out.json]
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_f -o f -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-cfg
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_w -o w -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-cfg
+    python tools/pmc_traffic.py OUT/pmc_f/.../f_counter_collection.csv OUT/pmc_w/.../w_counter_collection.csv [out.json]
 
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE counts a 128-byte request as 64 bytes, hence corrected bytes =
 2 * FETCH + WRITE (the guide's correction)."""
@@ -55,7 +55,7 @@ def main():
             fw, blocks = int(os.environ.get("PMC_FORWARDS", "2")), int(os.environ.get("PMC_BLOCKS", "28"))
             calls = {"gemm": (4 * blocks + 2) * fw, "attention": blocks * fw}.get(fam, tl)
             families[fam] = {"kernel_launches": tl, "calls": calls, "bytes_per_launch_corrected": int(tb / calls)}
-    out = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `python3 bench.py --steps 1 --warmup 1 "
+    out = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `python3 bench.py --full --steps 1 --warmup 1 "
                    "--no-cpu-baseline --no-cfg`; per-launch averages over all launches of the kernel; corrected = "
                    "2*FETCH_SIZE + WRITE_SIZE in bytes (gfx950 FETCH_SIZE counts 128-B requests as 64 B); a GEMM wrapper call "
                    "may be two kernel launches (whole-round + tail)",
