@@ -30,6 +30,9 @@ from .host_tables import rope_cos_sin, timestep_sinusoid
 from .parallel import ShardPlan, allgather_rows_, alltoall_bands_, alltoall_rows_, group_info, wait_exchange
 
 
+PRECISIONS = ("bf16", "mxfp8")
+
+
 def _pad_cols(w: torch.Tensor, mult: int) -> torch.Tensor:
     n, k = w.shape
     kp = (k + mult - 1) // mult * mult
@@ -52,7 +55,18 @@ def _pad_rows(w: torch.Tensor, mult: int) -> torch.Tensor:
 
 class HipDiT:
     def __init__(self, net: dict, state_dict: Dict[str, torch.Tensor], device=None, prefix: str = "net.",
-                 process_group=None):
+                 process_group=None, precision: Optional[str] = None):
+        """precision: "bf16" (default) or "mxfp8" (opt-in: the q|k|v, out-proj, MLP-up and MLP-down GEMMs of every block run on
+        MXFP8 operands quantised on the device, drn.h; everything else stays bf16).  None = $DRN_DIT_PRECISION, else "bf16"."""
+        import os
+        if precision is None:
+            precision = os.environ.get("DRN_DIT_PRECISION", "") or "bf16"
+        if precision not in PRECISIONS:
+            raise ValueError(f"unknown DiT precision {precision!r}: expected one of {PRECISIONS}")
+        if precision == "mxfp8" and process_group is not None:
+            raise ValueError("precision='mxfp8' with a process_group (sequence parallelism) is not built yet")
+        self.precision = precision
+        self._mx = precision == "mxfp8"
         self.net = dict(net)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.D = net["model_channels"]
@@ -66,9 +80,12 @@ class HipDiT:
         self.with_mask = net.get("concat_padding_mask", True)
         if self.D // self.heads != 128:
             raise ValueError("HipDiT kernels are specialised for head_dim 128 (the renderer's only configuration)")
+        hidden = int(self.D * net["mlp_ratio"])
+        if self._mx and (self.D % 256 or hidden % 256):
+            raise ValueError(f"precision='mxfp8' needs model_channels and the MLP width to be multiples of 256 (the MXFP8 GEMM's "
+                             f"N and K contract); got {self.D} and {hidden}")
         N.load_library()
         self.pg = process_group
-        import os
         world = group_info(process_group)[1] if process_group is not None else 1
         mode = os.environ.get("DRN_SP_EXCHANGE", "auto")
         if mode not in ("auto", "a2a", "gather"):
@@ -88,6 +105,7 @@ class HipDiT:
         self._ctx_cache = {}
         self._ws = {}
         self._graphs = {}
+        self._mx_act = {}          # mxfp8: (rows, K) -> MxTensor, the quantised A operand of the next block linear
         self.trace = None          # tests: dict filled with per-sub-block activations "block{i}.{j}" -> [S, D]
         # DRN_PER_LAUNCH=1: one ctypes call per kernel (the path the sharded engine and the traces use) instead of the
         # drn_dit_forward sequencer - same kernels, same bits (tests compare the two)
@@ -155,19 +173,31 @@ class HipDiT:
         self.w_cao = torch.stack(ca_o, 0).contiguous() if ca_o else None   # [n_ca, D, D]
         # site index of every cross-attention sub-block (for its gate)
         self.ca_sites = [i * len(self.kinds) + j for i in range(self.L) for j, k in enumerate(self.kinds) if k == "ca"]
-        # the same sub-block list as the host table drn_dit_forward walks (weights never move after load)
+        if self._mx:
+            # quantise the four block linears once, on the device, and drop their bf16 copies
+            for subs in self.blocks:
+                for sb in subs:
+                    for key in ("wqkv", "wo", "w1", "w2"):
+                        if key in sb:
+                            sb[key] = N.mx_quant(sb[key])
+            torch.cuda.synchronize(dev)
+            torch.cuda.empty_cache()
+        # the same sub-block list as the host table drn_dit_forward walks (weights never move after load; mxfp8 does not use it)
         flat = [sb for subs in self.blocks for sb in subs]
         self._subs_c = (N.DitSub * len(flat))()
         for site, sb in enumerate(flat):
             e = self._subs_c[site]
             e.site, e.ca_index = site, -1
             if sb["kind"] == "fa":
-                e.kind, e.w_a, e.w_b = N.SUB_FA, sb["wqkv"].data_ptr(), sb["wo"].data_ptr()
-                e.qn, e.kn = sb["qn"].data_ptr(), sb["kn"].data_ptr()
+                e.kind, e.qn, e.kn = N.SUB_FA, sb["qn"].data_ptr(), sb["kn"].data_ptr()
+                if not self._mx:
+                    e.w_a, e.w_b = sb["wqkv"].data_ptr(), sb["wo"].data_ptr()
             elif sb["kind"] == "ca":
                 e.kind, e.ca_index = N.SUB_CA, sb["idx"]
             else:
-                e.kind, e.w_a, e.w_b = N.SUB_MLP, sb["w1"].data_ptr(), sb["w2"].data_ptr()
+                e.kind = N.SUB_MLP
+                if not self._mx:
+                    e.w_a, e.w_b = sb["w1"].data_ptr(), sb["w2"].data_ptr()
 
     # ------------------------------------------------------------------ per-timestep vectors (K10, K11)
     def prepare_timesteps(self, sigmas) -> None:
@@ -368,6 +398,16 @@ class HipDiT:
         g.replay()
         return out.clone()                                       # the graph's output buffer is reused by the next replay
 
+    def _lin(self, a, w, out, epilogue=N.EPI_NONE, gate=None, residual=None, rows_per_batch=None):
+        """A block linear (q|k|v, out-proj, MLP-up, MLP-down): the bf16 GEMM, or with precision 'mxfp8' the quantisation of
+        `a` followed by the MXFP8 GEMM against the weights quantised at load."""
+        if not self._mx:
+            return N.gemm(a, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch)
+        key = tuple(a.shape)
+        aq = N.mx_quant(a, out=self._mx_act.get(key))
+        self._mx_act[key] = aq
+        return N.gemm_mxfp8(aq, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch)
+
     @staticmethod
     def _traced(X, pending, B):
         if pending is None:
@@ -460,7 +500,7 @@ class HipDiT:
 
         # the latent is tiny: every rank patchifies it all and keeps its own token band
         P = N.patchify_concat(x, cond, self.with_mask, self.pt, self.ps, self.kpad)
-        if self.exchange == "none" and self.trace is None and not self._per_launch:
+        if self.exchange == "none" and self.trace is None and not self._per_launch and not self._mx:
             # one GPU: the whole launch sequence below is enqueued by ONE C call (csrc/dit_forward.hip: same kernels, same
             # arguments, same order -> same bits; ~570 ctypes round trips less per forward)
             a = N.DitForwardArgs()
@@ -518,7 +558,7 @@ class HipDiT:
                 if sb["kind"] == "fa":
                     if self.exchange == "none":
                         QKV = ws["qkv"]
-                        N.gemm(Hb, sb["wqkv"], out=QKV, rows_per_batch=rows)
+                        self._lin(Hb, sb["wqkv"], QKV, rows_per_batch=rows)
                         q, k, v = QKV[:, :D], QKV[:, D:2 * D], QKV[:, 2 * D:]
                         N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
                         if B == 1:
@@ -526,8 +566,8 @@ class HipDiT:
                         else:
                             Q3 = QKV.view(B, S, 3 * D)
                             N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:], out=O.view(B, S, D), heads=self.heads)
-                        N.gemm(O, sb["wo"], out=X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
-                               rows_per_batch=rows)
+                        self._lin(O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
+                                  rows_per_batch=rows)
                     else:
                         # sharded: the exchanges (and the projections that write / read their slabs) run clip by clip on this
                         # rank's band of each clip; every clip of a batch has the same sigma, hence the same gate row
@@ -539,9 +579,9 @@ class HipDiT:
                             band = slice(b * rows, (b + 1) * rows)
                             self._fa_sharded(sb, Hb[band], X[band], O[band], ws, plan, cos, sin, gate, fused)
                 else:
-                    N.gemm(Hb, sb["w1"], out=U, epilogue=N.EPI_GELU, rows_per_batch=rows)
-                    N.gemm(U, sb["w2"], out=X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
-                           rows_per_batch=rows)
+                    self._lin(Hb, sb["w1"], U, epilogue=N.EPI_GELU, rows_per_batch=rows)
+                    self._lin(U, sb["w2"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
+                              rows_per_batch=rows)
 
         if self.trace is not None:
             self.trace[f"block{(site - 1) // nk}.{(site - 1) % nk}"] = self._traced(X, pending, B)

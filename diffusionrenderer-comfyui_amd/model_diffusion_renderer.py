@@ -132,7 +132,9 @@ class CleanDiffusionRendererModel:
         if strict and (missing or unexpected or bad):
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:5]} unexpected {unexpected[:5]} "
                                f"shape mismatch {bad[:5]}")
-        self.net = HipDiT(self.config["net"], state_dict, device=self.device, process_group=self.process_group)
+        # config key "dit_precision": "bf16" (default) or the opt-in "mxfp8" block linears; absent -> $DRN_DIT_PRECISION / bf16
+        self.net = HipDiT(self.config["net"], state_dict, device=self.device, process_group=self.process_group,
+                          precision=self.config.get("dit_precision"))
         return missing, unexpected
 
     def _get_tensor_kwargs(self):

@@ -65,6 +65,8 @@ SIGNATURES = {
     "drn_gemm_force_tile": [_I],
     "drn_gemm_force_res_prefetch": [_I],
     "drn_gemm_tall_force_shape": [_I],
+    "drn_mx_quant_bf16": [_P, _L, _L, _L, _P, _P, _P],
+    "drn_gemm_mxfp8": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _P],
     "drn_gemv_bf16": [_P, _P, _P, _L, _L, _I, _I, _L, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _I, _P],
     "drn_ln_modulate": [_P, _P, _P, _P, _P, _L, _L, _L, _F, _P],
     "drn_ln_force_kernel": [_I],
@@ -300,6 +302,57 @@ def gemm_blocked(a, w, out, M, epilogue=EPI_NONE, gate=None, residual=None, a_pl
            "drn_gemm_bf16_blocked")
     if t0 is not None:
         _TIMER.end("gemm", t0, 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N * (2 if residual is not None else 1)))
+    return out
+
+
+class MxTensor:
+    """An MXFP8 matrix (drn.h, MXFP8 block linears): q [rows, K] e4m3fn, scales [rows, K / 32] uint8 (E8M0 bytes)."""
+
+    def __init__(self, q, scales):
+        self.q, self.scales = q, scales
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+
+def mx_quant(x, out=None):
+    """bf16 [M, K] (row-strided view allowed) -> MxTensor, on the device (drn_mx_quant_bf16).  `out`: an MxTensor to reuse."""
+    _bf16(x)
+    M, K = x.shape
+    assert x.stride(1) == 1
+    if K % 32:
+        raise ValueError(f"MXFP8 quantisation needs K % 32 == 0 (K = {K})")
+    if out is None:
+        out = MxTensor(torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device),
+                       torch.empty((M, K // 32), dtype=torch.uint8, device=x.device))
+    assert out.q.shape == (M, K) and out.q.is_contiguous() and out.scales.shape == (M, K // 32) and out.scales.is_contiguous()
+    _check(load_library().drn_mx_quant_bf16(_ptr(x), M, K, x.stride(0), _ptr(out.q), _ptr(out.scales), _stream()),
+           "drn_mx_quant_bf16")
+    return out
+
+
+def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None):
+    """out[M, N] = epi(dequant(a) @ dequant(w)^T) for MxTensors a [M, K], w [N, K] (drn_gemm_mxfp8).  N % 256 == 0, K % 128 == 0."""
+    _bf16(out, gate, residual)
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"MXFP8 GEMM: K of a ({K}) and w ({w.shape[1]}) differ")
+    if N % 256 or K % 128:
+        raise ValueError(f"MXFP8 GEMM needs N % 256 == 0 and K % 128 == 0 (N = {N}, K = {K})")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.q.device)
+    assert out.shape == (M, N) and out.stride(1) == 1
+    ldr = residual.stride(0) if residual is not None else 0
+    if residual is not None:
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+    t0 = _TIMER.begin("gemm") if _TIMER is not None else None
+    rpb = rows_per_batch if rows_per_batch else max(M, 1)
+    _check(load_library().drn_gemm_mxfp8(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, out.stride(0),
+                                         epilogue, _ptr(gate), _ptr(residual), ldr, rpb, _stream()), "drn_gemm_mxfp8")
+    if t0 is not None:
+        _TIMER.end("gemm", t0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (2 if residual is not None else 1))
     return out
 
 

@@ -50,13 +50,16 @@ class LoadDiffusionRendererModel:
     def INPUT_TYPES(s):
         import folder_paths
         return {"required": {"model": (folder_paths.get_filename_list("diffusion_models"),
-                                       {"tooltip": "Models are loaded from 'ComfyUI/models/diffusion_models'"})}}
+                                       {"tooltip": "Models are loaded from 'ComfyUI/models/diffusion_models'"})},
+                "optional": {"dit_precision": (["bf16", "mxfp8"],
+                                               {"default": "bf16",
+                                                "tooltip": "mxfp8: opt-in MXFP8 block linears (faster, ~4x the bf16 error)"})}}
 
     RETURN_TYPES = ("DIFFUSION_RENDERER_PIPELINE",)
     FUNCTION = "load_pipeline"
     CATEGORY = "Cosmos1"
 
-    def load_pipeline(self, model):
+    def load_pipeline(self, model, dit_precision="bf16"):
         import folder_paths
         import comfy.model_management as mm
         import comfy.utils
@@ -75,7 +78,7 @@ class LoadDiffusionRendererModel:
         state_dict = comfy.utils.load_torch_file(checkpoint_path, safe_load=True)
         if "model" in state_dict:
             state_dict = state_dict["model"]
-        model_instance = CleanDiffusionRendererModel(get_inverse_renderer_config(), device=device)
+        model_instance = CleanDiffusionRendererModel(dict(get_inverse_renderer_config(), dit_precision=dit_precision), device=device)
         model_instance.load_state_dict(state_dict, strict=True)     # repack to the HIP layouts, weights stay on GPU
         del state_dict
         mm.soft_empty_cache()

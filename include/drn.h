@@ -103,6 +103,24 @@ int drn_gemm_force_res_prefetch(int on);
  * (same bits), -1 = the default (environment DRN_GEMM_TALL_SHAPE, else built in).  Returns the previous setting. */
 int drn_gemm_tall_force_shape(int shape);
 
+/* ---- MXFP8 block linears (opt-in precision, HipDiT(precision="mxfp8"); no reference counterpart).
+ * Format (OCP MX v1.0): elements OCP e4m3fn (not fnuz); one E8M0 scale byte (e + 127) per 32 consecutive elements along K.
+ * For a block with bf16 absolute maximum amax: e = floor(log2(amax)) - 8, e + 1 if amax / 2^e > 448 (significand above 1.75),
+ * clamped to [-127, 127]; an all-zero block gets e = -127.  Element = rne_e4m3fn(x / 2^e), never above 448.  Non-finite
+ * inputs are outside the contract.
+ * Layouts: elements [rows, K] row-major, contiguous (ld = K), one byte each; scales [rows, K / 32] row-major, one byte each
+ * (the scale of elements k .. k+31 of row r at r * (K / 32) + k / 32).  Weights [N, K] and activations [M, K] alike. */
+/* X [M, K] bf16 with row stride ldx -> Q [M, K] e4m3 + scales [M, K / 32].  K % 32 == 0, ldx % 8 == 0, X 16-byte and Q 8-byte
+ * aligned, M * K / 8 < 2^31. */
+int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q, void* scales, void* stream);
+/* C[M, N] = epi(dequant(A) . dequant(W)^T) on v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulate, bf16 out; the epilogues of
+ * drn_gemm_bf16 with the same rounding points (gate [batches, N] bf16, row r uses batch r / rows_per_batch; residual [M, ldr]
+ * bf16, may alias C).  A / SA, W / SW in the layouts above.  Any M >= 1; N % 256 == 0 and K % 128 == 0 (DRN_EINVAL
+ * otherwise); ldc / ldr % 4 == 0, A / W 16-byte, C / R / gate 8-byte, scales 4-byte aligned. */
+int drn_gemm_mxfp8(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K,
+                   int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
+                   void* stream);
+
 /* ---- weight-streaming GEMV family (batch-1 vectors: timestep MLP, AdaLN-LoRA, the 1-key cross-attention).
  * For g in [0,groups), b in [0,batch): y[g,b,:] = epi(W[g] . act(x[g,b,:]))   W[g]: [N,K] bf16
  *   y = bf16(acc); if add: y = bf16(y + add[g,b,n]); if mul: y = bf16(mul[g,b,n] * y)

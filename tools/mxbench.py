@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""MXFP8 against bf16 on one box, interleaved in ONE process (CDNA guide rule 24), random data.
+    python tools/mxbench.py [gemm] [model] [--rounds R] [--cold C]
+gemm:  the four cfg-3 block linears (M = 18 432): drn_gemm_bf16 (the kernel it picks) against drn_mx_quant_bf16 of the activation
+       + drn_gemm_mxfp8 (and each of the two alone); the quantiser in GB/s against the HBM peak.
+model: ms per step (DiT forward + Euler step) of the 28-block model at cfg 3 (57 x 576 x 1024, S = 18 432) and cfg 1 (256 x 256,
+       S = 256) with precision bf16 and mxfp8 (synthetic weights)."""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+HBM_PEAK_GBS = 8000.0
+SHAPES = [("qkv", 12288, 4096, 0), ("out-proj", 4096, 4096, 2), ("mlp-up", 16384, 4096, 1), ("mlp-down", 4096, 16384, 2)]
+
+
+def timed(fn, reps):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        fn()
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) / reps
+
+
+def bench_gemm(pkg, args):
+    N = pkg.native
+    dev = torch.device("cuda")
+    M = args.M
+    g = torch.Generator(device="cpu").manual_seed(0)
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(torch.bfloat16).to(dev)
+
+    print(f"# GEMM, M = {M}, {args.rounds} interleaved rounds x {args.reps} launches, weights rotated over {args.cold} copies")
+    for name, n, k, epi in SHAPES:
+        a = rnd(M, k)
+        ws = [rnd(n, k, scale=k ** -0.5) for _ in range(args.cold)]
+        wqs = [N.mx_quant(w) for w in ws]
+        out = torch.empty(M, n, dtype=torch.bfloat16, device=dev)
+        gate = rnd(1, n, scale=0.5) if epi == 2 else None
+        res = rnd(M, n) if epi == 2 else None
+        aq = N.mx_quant(a)
+        it = {"i": 0}
+
+        def nxt():
+            it["i"] = (it["i"] + 1) % args.cold
+            return it["i"]
+
+        def run_bf16():
+            N.gemm(a, ws[nxt()], out=out, epilogue=epi, gate=gate, residual=res)
+
+        def run_quant():
+            N.mx_quant(a, out=aq)
+
+        def run_mx():
+            N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res)
+
+        def run_both():
+            N.mx_quant(a, out=aq)
+            N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res)
+
+        cases = [("bf16", run_bf16), ("quant", run_quant), ("mxfp8", run_mx), ("quant+mxfp8", run_both)]
+        for _, f in cases:
+            timed(f, 3)
+        t = {c: [] for c, _ in cases}
+        for _ in range(args.rounds):
+            for c, f in cases:
+                t[c].append(timed(f, args.reps))
+        med = {c: sorted(v)[len(v) // 2] for c, v in t.items()}
+        fl = 2.0 * M * n * k
+        qbytes = M * k * 2 + M * k + M * k / 32
+        print(f"{name:9s} N={n:5d} K={k:5d}: bf16 {med['bf16']:.3f} ms ({fl / med['bf16'] / 1e9:.0f} TF) | "
+              f"mxfp8 {med['mxfp8']:.3f} ms ({fl / med['mxfp8'] / 1e9:.0f} TF) | quant {med['quant']:.3f} ms "
+              f"({qbytes / med['quant'] / 1e6:.0f} GB/s = {qbytes / med['quant'] / 1e6 / HBM_PEAK_GBS:.2f} of HBM peak) | "
+              f"quant+mxfp8 {med['quant+mxfp8']:.3f} ms = {med['quant+mxfp8'] / med['bf16']:.3f} x bf16")
+        del ws, wqs, a, aq, out, gate, res
+        torch.cuda.empty_cache()
+
+
+def bench_model(pkg, args):
+    N = pkg.native
+    dev = torch.device("cuda")
+    sw = pkg.synthetic_weights
+    net = dict(pkg.diffusion_renderer_config.get_inverse_renderer_config()["net"], model_channels=4096, num_blocks=28, num_heads=32)
+    sd = sw.synth_state_dict(net, torch.bfloat16, device=dev)
+    dits = {}
+    for prec in ("bf16", "mxfp8"):
+        dits[prec] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision=prec)
+    del sd
+    torch.cuda.empty_cache()
+    for cfg, (F_, h, w) in (("cfg3", (8, 72, 128)), ("cfg1", (1, 32, 32))):
+        x = sw.synth_tensor("mxb.x", (1, 16, F_, h, w), torch.float32, scale=2.0).to(torch.bfloat16).to(dev)
+        cond = sw.synth_tensor("mxb.c", (1, 16, F_, h, w), torch.float32).to(torch.bfloat16).to(dev)
+        xs = x.clone()
+        for d in dits.values():
+            d.prepare_timesteps([1.5])
+
+        def step(d):
+            y = d(xs, 1.5, cond, 0)
+            N.edm_step(y, xs, 0.9, 0.1, 1.5, -0.05)
+
+        for d in dits.values():
+            step(d)
+        torch.cuda.synchronize()
+        reps = args.model_reps if cfg == "cfg3" else 5 * args.model_reps
+        t = {p: [] for p in dits}
+        for _ in range(args.rounds):
+            for p, d in dits.items():
+                t[p].append(timed(lambda: step(d), reps))
+        med = {p: sorted(v)[len(v) // 2] for p, v in t.items()}
+        print(f"# model {cfg} (latent {F_}x{h}x{w}): bf16 {med['bf16']:.2f} ms/step | mxfp8 {med['mxfp8']:.2f} ms/step "
+              f"({100 * (1 - med['mxfp8'] / med['bf16']):+.1f} % lower)")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", nargs="*", default=["gemm", "model"])
+    ap.add_argument("--M", type=int, default=18432)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--model-reps", type=int, default=3)
+    ap.add_argument("--cold", type=int, default=3, help="gemm: rotate over this many weight copies (HBM, not Infinity Cache)")
+    args = ap.parse_args()
+    pkg = load_package()
+    pkg.native.load_library()
+    print(f"# device {torch.cuda.get_device_name()}")
+    if "gemm" in args.what:
+        bench_gemm(pkg, args)
+    if "model" in args.what:
+        bench_model(pkg, args)
+
+
+if __name__ == "__main__":
+    main()
