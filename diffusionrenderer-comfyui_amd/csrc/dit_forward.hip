@@ -2,7 +2,8 @@
 //
 // Replaces the Python-level block loop of the reference (CleanGeneralDIT.py:686-706: patch embed, 28 x {FA, CA, MLP}, final
 // layer) as a SEQUENCER only: every launch below is one of the kernels behind the other entry points of drn.h, called with the
-// arguments the per-launch host path (dit_engine.HipDiT._run) passes, in the same order - results are bit-identical to it.
+// arguments the per-launch host path (dit_engine.HipDiT._run) passes, in the same order - results are bit-identical to it,
+// in both precisions of the block linears (args->precision: 0 = bf16, 1 = MXFP8 with the activations quantised per linear).
 // Why it exists: a forward is ~570 launches; through ctypes + torch wrappers each costs the host 6-12 us, which at S = 256
 // (cfg 1: a 6.8 ms GPU step) made the host the bound of the denoising loop.  From C the same launches cost the host ~2 ms.
 // Host code only (no kernel lives in this file).
@@ -164,6 +165,37 @@ static int fwd_gemm(const drn_dit_forward_args* a, const void* A, const void* W,
     return drn_gemm_bf16(A, W, C, M, N, K, lda, K, ldc, epi, gate, residual, ldr, rpb, stream);
 }
 
+// The same for a block linear of a precision-1 (MXFP8) forward: quantise A into AQ | AS, then the MXFP8 product chosen as
+// native.gemm_mxfp8 chooses it (drn_gemm_mxfp8_splitk_choice on ONE clip's rows): drn_gemm_mxfp8 (0), the fused few-token kernel
+// (1) or its K slices (> 1; `defer` as in fwd_gemm, same conditions).
+static int fwd_gemm_mx(const drn_dit_forward_args* a, const void* A, const void* W, const void* SW, void* C, int64_t M, int64_t N,
+                       int64_t K, int64_t lda, int64_t ldc, int epi, const void* gate, const void* residual, int64_t ldr,
+                       void* stream, int* defer = nullptr) {
+    const int64_t rpb = a->S;
+    const int64_t Mb = (rpb > 0 && rpb < M && M % rpb == 0) ? rpb : M;
+    if (defer) *defer = 0;
+    DRN_TRY(drn_mx_quant_bf16(A, M, K, lda, a->AQ, a->AS, stream));
+    const int splits = drn_gemm_mxfp8_splitk_choice(Mb, N, K);
+    Scope sc((drn_timer*)a->timer, 0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (residual ? 2 : 1), (hipStream_t)stream);
+    if (splits == 0) return drn_gemm_mxfp8(a->AQ, a->AS, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, stream);
+    if (splits > 1) {
+        if (!a->gemm_ws || drn_gemm_splitk_workspace_bytes(M, N, splits) > a->gemm_ws_bytes) return DRN_EINVAL;
+        if (defer && epi == DRN_EPI_GATE_RES && N == a->D && N > 1024 && ldc == N && ldr == N && residual == C) {
+            *defer = splits;
+            return drn_gemm_mxfp8_splitk_partials(a->AQ, a->AS, W, SW, M, N, K, rpb, splits, a->gemm_ws, stream);
+        }
+    }
+    return drn_gemm_mxfp8_splitk(a->AQ, a->AS, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, splits, a->gemm_ws, stream);
+}
+
+// a block linear in the precision of the forward
+static int fwd_lin(const drn_dit_forward_args* a, const void* A, const void* W, const void* SW, void* C, int64_t M, int64_t N,
+                   int64_t K, int epi, const void* gate, const void* residual, void* stream, int* defer = nullptr) {
+    const int64_t ldr = residual ? N : 0;
+    if (a->precision == 1) return fwd_gemm_mx(a, A, W, SW, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer);
+    return fwd_gemm(a, A, W, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer);
+}
+
 extern "C" int64_t drn_dit_forward_attn_workspace_bytes(int64_t B, int heads, int64_t S) {
     int64_t plan[6];
     const int n = drn_attention_plan(heads, S, S, plan);
@@ -188,6 +220,23 @@ extern "C" int64_t drn_dit_forward_gemm_workspace_bytes(int64_t B, int64_t S, in
     return need;
 }
 
+extern "C" int64_t drn_dit_forward_mx_act_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden) {
+    const int64_t k = D > hidden ? D : hidden;
+    return B * S * k + B * S * (k / 32);
+}
+
+extern "C" int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden) {
+    const int64_t M = B * S;
+    const int64_t shapes[4][2] = {{3 * D, D}, {D, D}, {hidden, D}, {D, hidden}};
+    int64_t need = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int splits = drn_gemm_mxfp8_splitk_choice(S, shapes[i][0], shapes[i][1]);
+        const int64_t b = drn_gemm_splitk_workspace_bytes(M, shapes[i][0], splits);
+        need = b > need ? b : need;
+    }
+    return need;
+}
+
 extern "C" int64_t drn_dit_forward_args_bytes(void) { return (int64_t)sizeof(drn_dit_forward_args); }
 extern "C" int64_t drn_dit_sub_bytes(void) { return (int64_t)sizeof(drn_dit_sub); }
 
@@ -197,6 +246,16 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
     DRN_CHECK_ARG(a->n_sub >= 0 && (a->n_sub == 0 || a->subs) && a->X && a->H && a->QKV && a->O && a->U && a->Y);
     DRN_CHECK_ARG(a->P && a->w_patch && a->w_final && a->final_shift && a->final_scale && a->shift && a->scale && a->gate);
     const int64_t S = a->S, B = a->B, D = a->D, M = B * S;
+    DRN_CHECK_ARG(a->precision == 0 || a->precision == 1);
+    if (a->precision == 1) {                             // everything the MXFP8 block linears need, before anything is launched
+        DRN_CHECK_ARG(D % 256 == 0 && a->hidden % 256 == 0 && a->AQ && a->AS);
+        DRN_CHECK_ARG(a->act_bytes >= drn_dit_forward_mx_act_bytes(B, S, D, a->hidden));
+        const int64_t need = drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, a->hidden);
+        DRN_CHECK_ARG(need == 0 || (a->gemm_ws && a->gemm_ws_bytes >= need));
+        for (int i = 0; i < a->n_sub; ++i)
+            if (a->subs[i].kind == DRN_SUB_FA || a->subs[i].kind == DRN_SUB_MLP)
+                DRN_CHECK_ARG(a->subs[i].w_a && a->subs[i].w_b && a->subs[i].s_a && a->subs[i].s_b);
+    }
     const bf16_t* shift = (const bf16_t*)a->shift;
     const bf16_t* scale = (const bf16_t*)a->scale;
     const bf16_t* gate = (const bf16_t*)a->gate;
@@ -250,7 +309,7 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
             bf16_t* q = (bf16_t*)a->QKV;
             bf16_t* k = q + D;
             bf16_t* v = q + 2 * D;
-            DRN_TRY(fwd_gemm(a, a->H, sb->w_a, a->QKV, M, 3 * D, D, D, 3 * D, DRN_EPI_NONE, nullptr, nullptr, 0, stream));
+            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->QKV, M, 3 * D, D, DRN_EPI_NONE, nullptr, nullptr, stream));
             DRN_TRY(drn_qk_norm_rope(q, k, sb->qn, sb->kn, a->cos, a->sin, M, a->heads, 3 * D, 3 * D, S, 0, a->eps, stream));
             {
                 Scope tsc((drn_timer*)a->timer, 1, 4.0 * B * a->heads * S * S * 128, 2.0 * B * a->heads * 128 * (4.0 * S), (hipStream_t)stream);
@@ -271,13 +330,13 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
                     }
                 }
             }
-            DRN_TRY(fwd_gemm(a, a->O, sb->w_b, a->X, M, D, D, D, D, DRN_EPI_GATE_RES, gt, a->X, D, stream, fuse ? &deferred : nullptr));
+            DRN_TRY(fwd_lin(a, a->O, sb->w_b, sb->s_b, a->X, M, D, D, DRN_EPI_GATE_RES, gt, a->X, stream, fuse ? &deferred : nullptr));
             deferred_gate = gt;
         } else if (sb->kind == DRN_SUB_MLP) {
             DRN_CHECK_ARG(sb->w_a && sb->w_b);
-            DRN_TRY(fwd_gemm(a, a->H, sb->w_a, a->U, M, a->hidden, D, D, a->hidden, DRN_EPI_GELU, nullptr, nullptr, 0, stream));
-            DRN_TRY(fwd_gemm(a, a->U, sb->w_b, a->X, M, D, a->hidden, a->hidden, D, DRN_EPI_GATE_RES, gt, a->X, D, stream,
-                             fuse ? &deferred : nullptr));
+            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->U, M, a->hidden, D, DRN_EPI_GELU, nullptr, nullptr, stream));
+            DRN_TRY(fwd_lin(a, a->U, sb->w_b, sb->s_b, a->X, M, D, a->hidden, DRN_EPI_GATE_RES, gt, a->X, stream,
+                            fuse ? &deferred : nullptr));
             deferred_gate = gt;
         } else {
             return DRN_EINVAL;

@@ -521,6 +521,23 @@ extern "C" int drn_gemm_bf16_splitk_partials(const void* A, const void* W, int64
     return splitk_slices(A, W, M, N, K, lda, ldw, rows_per_batch, splits, workspace, stream);
 }
 
+// the reduce launch of a split-K product: sum of the fp32 slices [splits][M][N] + epilogue (arguments validated by the callers:
+// drn_gemm_bf16_splitk below, drn_gemm_mxfp8_splitk in gemm_mx_tall.hip)
+int drn_gemm_splitk_reduce(const void* workspace, int splits, void* C, int64_t M, int64_t N, int64_t ldc, int epilogue,
+                           const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int64_t blocks = (M * (N / 4) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+#define EARGS (const float*)workspace, splits, (bf16_t*)C, M, N, ldc, (const bf16_t*)gate, (const bf16_t*)residual, ldr, rows_per_batch
+    switch (epilogue) {
+        case DRN_EPI_NONE: gemm_splitk_epilogue_kernel<DRN_EPI_NONE><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(EARGS); break;
+        case DRN_EPI_GELU: gemm_splitk_epilogue_kernel<DRN_EPI_GELU><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(EARGS); break;
+        default: gemm_splitk_epilogue_kernel<DRN_EPI_GATE_RES><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(EARGS); break;
+    }
+#undef EARGS
+    return drn_launch_status();
+}
+
 extern "C" int drn_gemm_bf16_splitk(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                                     int64_t ldw, int64_t ldc, int epilogue, const void* gate, const void* residual,
                                     int64_t ldr, int64_t rows_per_batch, int splits, void* workspace, void* stream) {
@@ -537,15 +554,5 @@ extern "C" int drn_gemm_bf16_splitk(const void* A, const void* W, void* C, int64
         const int rc = splitk_slices(A, W, M, N, K, lda, ldw, rows_per_batch, splits, workspace, stream);
         if (rc != DRN_OK) return rc;
     }
-    hipStream_t st = (hipStream_t)stream;
-    int64_t blocks = (M * (N / 4) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-#define EARGS (const float*)workspace, splits, (bf16_t*)C, M, N, ldc, (const bf16_t*)gate, (const bf16_t*)residual, ldr, rows_per_batch
-    switch (epilogue) {
-        case DRN_EPI_NONE: gemm_splitk_epilogue_kernel<DRN_EPI_NONE><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(EARGS); break;
-        case DRN_EPI_GELU: gemm_splitk_epilogue_kernel<DRN_EPI_GELU><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(EARGS); break;
-        default: gemm_splitk_epilogue_kernel<DRN_EPI_GATE_RES><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(EARGS); break;
-    }
-#undef EARGS
-    return drn_launch_status();
+    return drn_gemm_splitk_reduce(workspace, splits, C, M, N, ldc, epilogue, gate, residual, ldr, rows_per_batch, stream);
 }

@@ -182,7 +182,8 @@ class HipDiT:
                             sb[key] = N.mx_quant(sb[key])
             torch.cuda.synchronize(dev)
             torch.cuda.empty_cache()
-        # the same sub-block list as the host table drn_dit_forward walks (weights never move after load; mxfp8 does not use it)
+        # the same sub-block list as the host table drn_dit_forward walks (weights never move after load; mxfp8: the e4m3
+        # elements and their scale arrays)
         flat = [sb for subs in self.blocks for sb in subs]
         self._subs_c = (N.DitSub * len(flat))()
         for site, sb in enumerate(flat):
@@ -190,14 +191,17 @@ class HipDiT:
             e.site, e.ca_index = site, -1
             if sb["kind"] == "fa":
                 e.kind, e.qn, e.kn = N.SUB_FA, sb["qn"].data_ptr(), sb["kn"].data_ptr()
-                if not self._mx:
-                    e.w_a, e.w_b = sb["wqkv"].data_ptr(), sb["wo"].data_ptr()
+                wa, wb = sb["wqkv"], sb["wo"]
             elif sb["kind"] == "ca":
                 e.kind, e.ca_index = N.SUB_CA, sb["idx"]
             else:
                 e.kind = N.SUB_MLP
-                if not self._mx:
-                    e.w_a, e.w_b = sb["w1"].data_ptr(), sb["w2"].data_ptr()
+                wa, wb = sb["w1"], sb["w2"]
+            if sb["kind"] != "ca":
+                if self._mx:
+                    e.w_a, e.w_b, e.s_a, e.s_b = wa.q.data_ptr(), wb.q.data_ptr(), wa.scales.data_ptr(), wb.scales.data_ptr()
+                else:
+                    e.w_a, e.w_b = wa.data_ptr(), wb.data_ptr()
 
     # ------------------------------------------------------------------ per-timestep vectors (K10, K11)
     def prepare_timesteps(self, sigmas) -> None:
@@ -279,6 +283,12 @@ class HipDiT:
                 ws["qkv"] = torch.empty((B * S, 3 * D), dtype=bf, device=dev)      # q | k | v, fused projection
                 lib = N.load_library()
                 nb = lib.drn_dit_forward_gemm_workspace_bytes(B, S, D, ws["u"].shape[1], self.w_final.shape[0], self.kpad)
+                if self._mx:
+                    # the slices of the MXFP8 block linears share gemm_ws; AQ | AS: the quantised A operand of the next one
+                    nb = max(nb, lib.drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, ws["u"].shape[1]))
+                    kmax = max(D, ws["u"].shape[1])
+                    ws["act"] = torch.empty(lib.drn_dit_forward_mx_act_bytes(B, S, D, ws["u"].shape[1]), dtype=torch.uint8, device=dev)
+                    ws["act_q_bytes"] = n * kmax
                 ws["gemm_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-K partials (few tokens)
                 nb = lib.drn_dit_forward_attn_workspace_bytes(B, self.heads, S)
                 ws["attn_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-KV partials
@@ -400,13 +410,15 @@ class HipDiT:
 
     def _lin(self, a, w, out, epilogue=N.EPI_NONE, gate=None, residual=None, rows_per_batch=None):
         """A block linear (q|k|v, out-proj, MLP-up, MLP-down): the bf16 GEMM, or with precision 'mxfp8' the quantisation of
-        `a` followed by the MXFP8 GEMM against the weights quantised at load."""
+        `a` followed by the MXFP8 GEMM against the weights quantised at load (native.gemm_mxfp8 picks the few-token kernel and its
+        K slices from one clip's rows, as drn_dit_forward does)."""
         if not self._mx:
             return N.gemm(a, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch)
         key = tuple(a.shape)
         aq = N.mx_quant(a, out=self._mx_act.get(key))
         self._mx_act[key] = aq
-        return N.gemm_mxfp8(aq, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch)
+        return N.gemm_mxfp8(aq, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch,
+                            splitk=None)
 
     @staticmethod
     def _traced(X, pending, B):
@@ -500,7 +512,7 @@ class HipDiT:
 
         # the latent is tiny: every rank patchifies it all and keeps its own token band
         P = N.patchify_concat(x, cond, self.with_mask, self.pt, self.ps, self.kpad)
-        if self.exchange == "none" and self.trace is None and not self._per_launch and not self._mx:
+        if self.exchange == "none" and self.trace is None and not self._per_launch:
             # one GPU: the whole launch sequence below is enqueued by ONE C call (csrc/dit_forward.hip: same kernels, same
             # arguments, same order -> same bits; ~570 ctypes round trips less per forward)
             a = N.DitForwardArgs()
@@ -526,6 +538,10 @@ class HipDiT:
             a.gemm_ws, a.gemm_ws_bytes = (gws.data_ptr(), gws.numel()) if gws is not None else (None, 0)
             a.attn_ws, a.attn_ws_bytes = (aws.data_ptr(), aws.numel()) if aws is not None else (None, 0)
             a.eps = 1e-6
+            if self._mx:
+                a.precision = 1
+                a.AQ, a.AS = ws["act"].data_ptr(), ws["act"].data_ptr() + ws["act_q_bytes"]
+                a.act_bytes = ws["act"].numel()
             N.dit_forward(a)
             return N.unpatchify(Y, B, self.out_ch, Tp, Hp, Wp, self.pt, self.ps)
         sharded = self.exchange != "none"

@@ -22,7 +22,8 @@ SUB_FA, SUB_CA, SUB_MLP = 0, 1, 2
 
 class DitSub(Structure):                      # drn_dit_sub (include/drn.h)
     _fields_ = [("kind", c_int32), ("site", c_int32), ("ca_index", c_int32), ("reserved", c_int32),
-                ("w_a", c_void_p), ("w_b", c_void_p), ("qn", c_void_p), ("kn", c_void_p)]
+                ("w_a", c_void_p), ("w_b", c_void_p), ("qn", c_void_p), ("kn", c_void_p),
+                ("s_a", c_void_p), ("s_b", c_void_p)]
 
 
 class DitForwardArgs(Structure):              # drn_dit_forward_args (include/drn.h), field for field
@@ -35,7 +36,8 @@ class DitForwardArgs(Structure):              # drn_dit_forward_args (include/dr
                 ("final_shift", c_void_p), ("final_scale", c_void_p), ("w_final", c_void_p), ("n_final", c_int64),
                 ("X", c_void_p), ("H", c_void_p), ("QKV", c_void_p), ("O", c_void_p), ("U", c_void_p), ("Y", c_void_p),
                 ("gemm_ws", c_void_p), ("gemm_ws_bytes", c_int64), ("attn_ws", c_void_p), ("attn_ws_bytes", c_int64),
-                ("timer", c_void_p), ("eps", c_float), ("reserved", c_int32)]
+                ("timer", c_void_p), ("eps", c_float), ("precision", c_int32),
+                ("AQ", c_void_p), ("AS", c_void_p), ("act_bytes", c_int64)]
 
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); must match include/drn.h one-to-one
@@ -46,6 +48,8 @@ SIGNATURES = {
     "drn_dit_sub_bytes": [],
     "drn_dit_forward_gemm_workspace_bytes": [_L, _L, _L, _L, _L, _L],
     "drn_dit_forward_attn_workspace_bytes": [_L, _I, _L],
+    "drn_dit_forward_mx_act_bytes": [_L, _L, _L, _L],
+    "drn_dit_forward_mx_gemm_workspace_bytes": [_L, _L, _L, _L],
     "drn_timer_create": [_I, _I],
     "drn_timer_destroy": [_P],
     "drn_timer_count": [_P],
@@ -67,6 +71,11 @@ SIGNATURES = {
     "drn_gemm_tall_force_shape": [_I],
     "drn_mx_quant_bf16": [_P, _L, _L, _L, _P, _P, _P],
     "drn_gemm_mxfp8": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _P],
+    "drn_gemm_mxfp8_splitk_choice": [_L, _L, _L],
+    "drn_gemm_mxfp8_splitk": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _I, _P, _P],
+    "drn_gemm_mxfp8_splitk_partials": [_P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P],
+    "drn_gemm_mxfp8_force_small_m": [_I],
+    "drn_gemm_mxfp8_tall_force_shape": [_I],
     "drn_gemv_bf16": [_P, _P, _P, _L, _L, _I, _I, _L, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _I, _P],
     "drn_ln_modulate": [_P, _P, _P, _P, _P, _L, _L, _L, _F, _P],
     "drn_ln_force_kernel": [_I],
@@ -87,7 +96,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
-             "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
+             "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_mx_act_bytes": c_int64,
+             "drn_dit_forward_mx_gemm_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
              "drn_ln_force_kernel": None, "drn_attention_force_shape16": None}
 
 
@@ -332,8 +342,19 @@ def mx_quant(x, out=None):
     return out
 
 
-def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None):
-    """out[M, N] = epi(dequant(a) @ dequant(w)^T) for MxTensors a [M, K], w [N, K] (drn_gemm_mxfp8).  N % 256 == 0, K % 128 == 0."""
+def mx_gemm_plan(M, N, K, rows_per_batch=None) -> int:
+    """How gemm_mxfp8 runs an [M, N, K] product: 0 = drn_gemm_mxfp8 (256 x 256 tiles), s >= 1 = the few-token kernel with s K
+    slices (1 = unsplit, fused epilogue).  Decided by drn_gemm_mxfp8_splitk_choice from ONE clip's rows: clips stacked along the
+    rows (rows_per_batch) get the plan of a clip alone (batch-invariant summation order).  Host-only."""
+    rpb = rows_per_batch if rows_per_batch else max(M, 1)
+    Mb = rpb if (0 < rpb < M and M % rpb == 0) else M
+    return int(load_library().drn_gemm_mxfp8_splitk_choice(Mb, N, K))
+
+
+def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None, splitk=None):
+    """out[M, N] = epi(dequant(a) @ dequant(w)^T) for MxTensors a [M, K], w [N, K].  N % 256 == 0, K % 128 == 0.
+    splitk: None = mx_gemm_plan decides (drn_gemm_mxfp8, or the few-token kernel drn_gemm_mxfp8_splitk with its K slices);
+    0 = drn_gemm_mxfp8; k >= 1 = the few-token kernel with k slices."""
     _bf16(out, gate, residual)
     M, K = a.shape
     N = w.shape[0]
@@ -349,8 +370,23 @@ def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows
         assert residual.shape == (M, N) and residual.stride(1) == 1
     t0 = _TIMER.begin("gemm") if _TIMER is not None else None
     rpb = rows_per_batch if rows_per_batch else max(M, 1)
-    _check(load_library().drn_gemm_mxfp8(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, out.stride(0),
-                                         epilogue, _ptr(gate), _ptr(residual), ldr, rpb, _stream()), "drn_gemm_mxfp8")
+    lib = load_library()
+    splits = mx_gemm_plan(M, N, K, rows_per_batch) if splitk is None else int(splitk)
+    if splits >= 1:
+        ws = None
+        if splits > 1:
+            nbytes = lib.drn_gemm_splitk_workspace_bytes(M, N, splits)
+            key = (a.q.device, "gemm")
+            ws = _SPLIT_WS.get(key)
+            if ws is None or ws.numel() < nbytes:
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=a.q.device)
+                _SPLIT_WS[key] = ws
+        _check(lib.drn_gemm_mxfp8_splitk(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, out.stride(0),
+                                         epilogue, _ptr(gate), _ptr(residual), ldr, rpb, splits, _ptr(ws), _stream()),
+               "drn_gemm_mxfp8_splitk")
+    else:
+        _check(lib.drn_gemm_mxfp8(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, out.stride(0),
+                                  epilogue, _ptr(gate), _ptr(residual), ldr, rpb, _stream()), "drn_gemm_mxfp8")
     if t0 is not None:
         _TIMER.end("gemm", t0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (2 if residual is not None else 1))
     return out

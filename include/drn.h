@@ -120,6 +120,33 @@ int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q,
 int drn_gemm_mxfp8(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K,
                    int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
                    void* stream);
+/* ---- the same product for few tokens (one clip of 256 .. 1024 rows; csrc/gemm_mx_tall.hip): a workgroup owns a tile of one
+ * clip's rows x a narrow column band (128 x 128 or 256 x 64) over the whole K or over one of `splits` K slices, so that enough
+ * CUs stream the weights.  Operands, format and lane maps are those of drn_gemm_mxfp8.
+ * drn_gemm_mxfp8_splitk_choice (host-only): 0 = not a few-token shape, call drn_gemm_mxfp8; s >= 1 = the few-token kernel with s
+ * K slices (1 = unsplit, fused epilogue).  A pure function of (M, N, K); callers with B clips stacked along the rows pass ONE
+ * clip's rows.  Rule: 0 where the 256 x 256 tiles of drn_gemm_mxfp8 cover 3/4 of the 256 CUs; else M N / 16384 column tiles
+ * x the largest power-of-two s with tiles x s <= 256 and at least 8 K steps of 128 per slice.
+ * drn_gemm_mxfp8_splitk: splits == 1 runs the fused kernel (same rounding points as drn_gemm_mxfp8); splits > 1 writes fp32
+ * slices [splits][M][N] to `workspace` (drn_gemm_splitk_workspace_bytes(M, N, splits): the layout of the bf16 slices) and runs
+ * the reduce + epilogue launch of drn_gemm_bf16_splitk.  drn_gemm_mxfp8_splitk_partials: the slices alone (bit for bit the
+ * same), for drn_splitk_gate_res_ln_modulate.
+ * Contract: M % 256 == 0, at most 1024 rows per clip (rows_per_batch, or M), N % 256 == 0, K % 128 == 0, (K / 128) % splits == 0,
+ * 1 <= splits <= 64 (partials: >= 2), a 16-byte aligned workspace when splits > 1, alignments as drn_gemm_mxfp8; anything else
+ * returns DRN_EINVAL and launches nothing. */
+int drn_gemm_mxfp8_splitk_choice(int64_t M, int64_t N, int64_t K);
+int drn_gemm_mxfp8_splitk(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K,
+                          int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
+                          int splits, void* workspace, void* stream);
+int drn_gemm_mxfp8_splitk_partials(const void* A, const void* SA, const void* W, const void* SW, int64_t M, int64_t N, int64_t K,
+                                   int64_t rows_per_batch, int splits, void* workspace, void* stream);
+/* tuning hook (tests / A-B runs), as drn_gemm_force_tile: 0 = drn_gemm_mxfp8_splitk_choice returns 0 everywhere (every product on
+ * drn_gemm_mxfp8), 1 = the default, -1 = query only; returns the previous setting.  Environment DRN_MX_SMALL_M=0 sets the
+ * process default. */
+int drn_gemm_mxfp8_force_small_m(int on);
+/* tuning hook (tests / A-B runs): tile of the few-token MXFP8 kernel, 0 = 256 rows x 64 columns (3 stages), 1 = 128 x 128
+ * (4 stages), -1 = the default (environment DRN_MX_TALL_SHAPE, else built in).  Returns the previous setting. */
+int drn_gemm_mxfp8_tall_force_shape(int shape);
 
 /* ---- weight-streaming GEMV family (batch-1 vectors: timestep MLP, AdaLN-LoRA, the 1-key cross-attention).
  * For g in [0,groups), b in [0,batch): y[g,b,:] = epi(W[g] . act(x[g,b,:]))   W[g]: [N,K] bf16
@@ -211,6 +238,7 @@ int drn_attention_plan(int heads, int64_t Sq, int64_t Sk, int64_t* plan);
  * `for block in self.blocks.values()`, final_layer) as a SEQUENCER: every launch is one of the kernels above with the arguments
  * the per-launch host path passes (dit_engine.HipDiT._run), so the results are bit-identical to it; ~570 launches cost the host
  * ~2 ms from here instead of 4-7 ms through ctypes.  Patchify before and unpatchify after stay separate calls.
+ * Both precisions of the block linears take it (`precision`).
  * B clips of S tokens are stacked along the rows (row = b S + s; attention runs per clip).  All pointers device memory. */
 #define DRN_SUB_FA 0     /* self-attention sub-block      CleanGeneralDIT.py:465-517 with block_type "FA" */
 #define DRN_SUB_CA 1     /* cross-attention sub-block: one key -> softmax == 1 -> x += bf16(gate * to_out(to_v(ctx))) */
@@ -224,6 +252,8 @@ typedef struct drn_dit_sub {
     const void* w_b;     /* FA: to_out [D, D];               MLP: layer2 [D, hidden] */
     const void* qn;      /* FA: RMSNorm weight of q [128] */
     const void* kn;      /* FA: RMSNorm weight of k [128] */
+    const void* s_a;     /* precision 1: E8M0 scales of w_a (then w_a / w_b are e4m3 elements); else NULL */
+    const void* s_b;     /* precision 1: E8M0 scales of w_b */
 } drn_dit_sub;
 typedef struct drn_dit_forward_args {
     int64_t struct_bytes;                 /* sizeof(drn_dit_forward_args): ABI check */
@@ -241,13 +271,26 @@ typedef struct drn_dit_forward_args {
     void* gemm_ws; int64_t gemm_ws_bytes;                       /* split-K partials (drn_dit_forward_gemm_workspace_bytes) */
     void* attn_ws; int64_t attn_ws_bytes;                       /* split-KV partials (drn_dit_forward_attn_workspace_bytes) */
     void* timer;                          /* drn_timer_create handle or NULL */
-    float eps; int32_t reserved;
+    float eps;
+    int32_t precision;                    /* 0: bf16 block linears; 1: MXFP8 (subs carry e4m3 weights + scales; patch embed, final
+                                           * layer, AdaLN and attention stay bf16) */
+    void* AQ; void* AS; int64_t act_bytes;  /* precision 1: the quantised A operand of the next block linear, elements
+                                           * [B S, max(D, hidden)] and scales [B S, max(D, hidden) / 32]; act_bytes = the bytes behind
+                                           * both together (drn_dit_forward_mx_act_bytes) */
 } drn_dit_forward_args;
 int drn_dit_forward(const drn_dit_forward_args* args, void* stream);
 int64_t drn_dit_forward_args_bytes(void);     /* sizeof the two structs as this library was compiled (binding self-check) */
 int64_t drn_dit_sub_bytes(void);
 int64_t drn_dit_forward_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden, int64_t n_final, int64_t kpad);
 int64_t drn_dit_forward_attn_workspace_bytes(int64_t B, int heads, int64_t S);
+/* host-only sizers for drn_dit_forward with precision 1: the quantised-activation scratch (AQ and AS together), and the fp32
+ * slices of the widest sliced block linear under drn_gemm_mxfp8_splitk_choice (the caller allocates the larger of this and the
+ * bf16 figure for gemm_ws).  With precision 1 every block linear runs as drn_mx_quant_bf16 into AQ | AS, then drn_gemm_mxfp8
+ * (choice 0), the fused few-token kernel (1) or its slices (> 1: a sliced gated-residual linear defers its sum into the next
+ * LayerNorm pass exactly as the bf16 one does).  DRN_EINVAL before any launch when AQ / AS are NULL, act_bytes or gemm_ws_bytes
+ * are short, a FA / MLP sub-block lacks weights or scales, or D / hidden are not multiples of 256. */
+int64_t drn_dit_forward_mx_act_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden);
+int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden);
 
 /* ---- per-launch timing inside drn_dit_forward (the roofline leg of bench.py; no reference counterpart): a pool of HIP event
  * pairs; every `sample_every`-th GEMM (kind 0) and attention (kind 1) call of a forward is bracketed on the launch stream.

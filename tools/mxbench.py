@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """MXFP8 against bf16 on one box, interleaved in ONE process (CDNA guide rule 24), random data.
-    python tools/mxbench.py [gemm] [model] [--rounds R] [--cold C]
-gemm:  the four cfg-3 block linears (M = 18 432): drn_gemm_bf16 (the kernel it picks) against drn_mx_quant_bf16 of the activation
-       + drn_gemm_mxfp8 (and each of the two alone); the quantiser in GB/s against the HBM peak.
+    python tools/mxbench.py [gemm] [model] [--M ROWS] [--rounds R] [--cold C] [--sweep]
+gemm:  the four block linears at M rows (default 18 432 = cfg 3): what native.gemm runs in bf16 against drn_mx_quant_bf16 of the
+       activation + drn_gemm_mxfp8 (and each of the two alone); the quantiser in GB/s against the HBM peak.
+       --M 256 / --M 1024 (few tokens): also quantise + what native.gemm_mxfp8 picks (the few-token kernel of gemm_mx_tall.hip,
+       its reduce launch included where it slices K) against quantise + drn_gemm_mxfp8 (the small-M path off); the weight copies
+       are rotated over more than the 256 MB Infinity Cache.  --sweep adds both tile shapes at every power-of-two slice count.
 model: ms per step (DiT forward + Euler step) of the 28-block model at cfg 3 (57 x 576 x 1024, S = 18 432) and cfg 1 (256 x 256,
-       S = 256) with precision bf16 and mxfp8 (synthetic weights)."""
+       S = 256) with precision bf16, mxfp8, and mxfp8 built under DRN_PER_LAUNCH=1 (one ctypes call per kernel; at cfg 1 also
+       with the small-M path off: the path of an mxfp8 engine before gemm_mx_tall.hip), synthetic weights."""
 import argparse
 import os
 import sys
@@ -38,10 +42,15 @@ def bench_gemm(pkg, args):
     def rnd(*shape, scale=1.0):
         return (torch.randn(*shape, generator=g) * scale).to(torch.bfloat16).to(dev)
 
-    print(f"# GEMM, M = {M}, {args.rounds} interleaved rounds x {args.reps} launches, weights rotated over {args.cold} copies")
+    lib = N.load_library()
+    few = M <= 1024 and M % 256 == 0
+    print(f"# GEMM, M = {M}, {args.rounds} interleaved rounds x {args.reps} launches, weights rotated over >= {args.cold} copies")
     for name, n, k, epi in SHAPES:
         a = rnd(M, k)
-        ws = [rnd(n, k, scale=k ** -0.5) for _ in range(args.cold)]
+        # few tokens: the product is a weight stream, so the fp8 copies together must not fit the 256 MB Infinity Cache
+        cold = max(args.cold, -(-600_000_000 // (n * k))) if few else args.cold
+        w0 = rnd(n, k, scale=k ** -0.5)
+        ws = [w0] + [w0.clone() for _ in range(cold - 1)]
         wqs = [N.mx_quant(w) for w in ws]
         out = torch.empty(M, n, dtype=torch.bfloat16, device=dev)
         gate = rnd(1, n, scale=0.5) if epi == 2 else None
@@ -50,7 +59,7 @@ def bench_gemm(pkg, args):
         it = {"i": 0}
 
         def nxt():
-            it["i"] = (it["i"] + 1) % args.cold
+            it["i"] = (it["i"] + 1) % cold
             return it["i"]
 
         def run_bf16():
@@ -60,13 +69,26 @@ def bench_gemm(pkg, args):
             N.mx_quant(a, out=aq)
 
         def run_mx():
-            N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res)
+            N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res, splitk=0)
 
         def run_both():
             N.mx_quant(a, out=aq)
-            N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res)
+            N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res, splitk=0)
+
+        def small(shape, splits):
+            def run():
+                lib.drn_gemm_mxfp8_tall_force_shape(shape)
+                N.mx_quant(a, out=aq)
+                N.gemm_mxfp8(aq, wqs[nxt()], out=out, epilogue=epi, gate=gate, residual=res, splitk=splits)
+            return run
 
         cases = [("bf16", run_bf16), ("quant", run_quant), ("mxfp8", run_mx), ("quant+mxfp8", run_both)]
+        plan = N.mx_gemm_plan(M, n, k) if few else 0
+        if plan:
+            cases.append(("quant+small-M", small(-1, None)))
+            if args.sweep:
+                for shape in (0, 1):
+                    cases += [(f"shape{shape} s={sp}", small(shape, sp)) for sp in (1, 2, 4, 8, 16) if (k // 128) % sp == 0]
         for _, f in cases:
             timed(f, 3)
         t = {c: [] for c, _ in cases}
@@ -80,6 +102,16 @@ def bench_gemm(pkg, args):
               f"mxfp8 {med['mxfp8']:.3f} ms ({fl / med['mxfp8'] / 1e9:.0f} TF) | quant {med['quant']:.3f} ms "
               f"({qbytes / med['quant'] / 1e6:.0f} GB/s = {qbytes / med['quant'] / 1e6 / HBM_PEAK_GBS:.2f} of HBM peak) | "
               f"quant+mxfp8 {med['quant+mxfp8']:.3f} ms = {med['quant+mxfp8'] / med['bf16']:.3f} x bf16")
+        if plan:
+            sm = med["quant+small-M"]
+            print(f"          few-token path ({plan} slice{'s' if plan > 1 else ''}{', reduce launch included' if plan > 1 else ''}, {cold} weight "
+                  f"copies): quant+small-M {sm * 1e3:.1f} us = {sm / med['bf16']:.3f} x bf16 ({med['bf16'] * 1e3:.1f} us) = "
+                  f"{sm / med['quant+mxfp8']:.3f} x quant+drn_gemm_mxfp8 ({med['quant+mxfp8'] * 1e3:.1f} us); quant alone "
+                  f"{med['quant'] * 1e3:.1f} us")
+            if args.sweep:
+                print("          sweep (quant + kernel [+ reduce], us): "
+                      + "  ".join(f"{c} {med[c] * 1e3:.1f}" for c, _ in cases if c.startswith("shape")))
+            lib.drn_gemm_mxfp8_tall_force_shape(-1)
         del ws, wqs, a, aq, out, gate, res
         torch.cuda.empty_cache()
 
@@ -93,6 +125,10 @@ def bench_model(pkg, args):
     dits = {}
     for prec in ("bf16", "mxfp8"):
         dits[prec] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision=prec)
+    os.environ["DRN_PER_LAUNCH"] = "1"                   # read at construction
+    dits["mxfp8 per-launch"] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision="mxfp8")
+    del os.environ["DRN_PER_LAUNCH"]
+    lib = N.load_library()
     del sd
     torch.cuda.empty_cache()
     for cfg, (F_, h, w) in (("cfg3", (8, 72, 128)), ("cfg1", (1, 32, 32))):
@@ -102,21 +138,28 @@ def bench_model(pkg, args):
         for d in dits.values():
             d.prepare_timesteps([1.5])
 
-        def step(d):
+        def step(d, small_m=1):
+            lib.drn_gemm_mxfp8_force_small_m(small_m)
             y = d(xs, 1.5, cond, 0)
             N.edm_step(y, xs, 0.9, 0.1, 1.5, -0.05)
+            lib.drn_gemm_mxfp8_force_small_m(1)
 
-        for d in dits.values():
-            step(d)
+        runs = {p: (lambda d=d: step(d)) for p, d in dits.items()}
+        if cfg == "cfg1":
+            runs["mxfp8 per-launch, small-M off"] = lambda: step(dits["mxfp8 per-launch"], 0)
+        for f in runs.values():
+            f()
         torch.cuda.synchronize()
         reps = args.model_reps if cfg == "cfg3" else 5 * args.model_reps
-        t = {p: [] for p in dits}
+        t = {p: [] for p in runs}
         for _ in range(args.rounds):
-            for p, d in dits.items():
-                t[p].append(timed(lambda: step(d), reps))
+            for p, f in runs.items():
+                t[p].append(timed(f, reps))
         med = {p: sorted(v)[len(v) // 2] for p, v in t.items()}
         print(f"# model {cfg} (latent {F_}x{h}x{w}): bf16 {med['bf16']:.2f} ms/step | mxfp8 {med['mxfp8']:.2f} ms/step "
-              f"({100 * (1 - med['mxfp8'] / med['bf16']):+.1f} % lower)")
+              f"({100 * (1 - med['mxfp8'] / med['bf16']):+.1f} % lower) | "
+              + " | ".join(f"{p} {v:.2f}" for p, v in med.items() if p not in ("bf16", "mxfp8"))
+              + " | spread (min..max) " + ", ".join(f"{p} {min(v):.2f}..{max(v):.2f}" for p, v in t.items()))
 
 
 def main():
@@ -127,6 +170,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--model-reps", type=int, default=3)
     ap.add_argument("--cold", type=int, default=3, help="gemm: rotate over this many weight copies (HBM, not Infinity Cache)")
+    ap.add_argument("--sweep", action="store_true", help="gemm at few tokens: both tile shapes x slice counts of the few-token kernel")
     args = ap.parse_args()
     pkg = load_package()
     pkg.native.load_library()
