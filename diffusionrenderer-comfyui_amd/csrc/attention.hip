@@ -24,6 +24,7 @@
 // so on every SIMD one wave feeds the matrix pipe while its partner's VALU work fills the issue slots between its MFMAs.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "mx_quant.h"
 
 // Build switches (A/B timing of variants in one process: tools/kbench.py --lib; the shipped library uses the defaults):
 //   ATT_EPI_LDS 1: O is transposed through LDS and stored as whole 256-B rows (16 B per lane); 0: 8-B row-strided stores.
@@ -561,9 +562,13 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_kernel(
 }
 
 // merge the nsplit partials of one (row, head): O = sum_s w_s O_s / sum_s w_s l_s,  w_s = 2^((m_s - max m) * scale*log2e)
+// MX = true: the bf16 row is also written as MXFP8 (drn.h; OQ [batch * Sq rows at clip stride mx_bs, heads * 128], OS [.., heads * 4]):
+// a lane holds 2 consecutive d, the 16 lanes l .. l ^ 15 one 32-element block; O may then be NULL.
+template <bool MX>
 __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __restrict__ Opart, const float* __restrict__ MLpart,
                                                                 bf16_t* __restrict__ O, int nsplit, int batch, int heads, int64_t Sq,
-                                                                int64_t ldo, int64_t bso, float scale_log2e) {
+                                                                int64_t ldo, int64_t bso, float scale_log2e,
+                                                                uint8_t* __restrict__ OQ, uint8_t* __restrict__ OS, int64_t mx_bs) {
     const int lane = threadIdx.x & 63;
     const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (batch, row, head)
     const int64_t items = (int64_t)batch * Sq * heads;
@@ -585,14 +590,27 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __r
         o1 += w * o.y;
     }
     const float inv = 1.0f / den;
-    *reinterpret_cast<uint32_t*>(O + b * bso + row * ldo + (int64_t)head * 128 + 2 * lane) = pack_bf2(o0 * inv, o1 * inv);
+    const uint32_t packed = pack_bf2(o0 * inv, o1 * inv);
+    if (!MX) {
+        *reinterpret_cast<uint32_t*>(O + b * bso + row * ldo + (int64_t)head * 128 + 2 * lane) = packed;
+    } else {
+        uint32_t amax = mx_amax2(packed);
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) amax = max(amax, (uint32_t)__shfl_xor((int)amax, o, 64));
+        const int e = mx_block_exp(amax);
+        const float qs = mx_inv_scale(e);
+        const int64_t r = b * mx_bs + row;
+        *reinterpret_cast<uint16_t*>(OQ + (r * heads + head) * 128 + 2 * lane) = (uint16_t)mx_pack2(packed, qs);
+        if ((lane & 15) == 0) OS[(r * heads + head) * 4 + (lane >> 4)] = (uint8_t)(e + 127);
+        if (O) *reinterpret_cast<uint32_t*>(O + b * bso + row * ldo + (int64_t)head * 128 + 2 * lane) = packed;
+    }
 }
 
 // attention16.hip: the same kernel on v_mfma_f32_16x16x32_bf16 (same grid, same arguments)
 void drn_attention16_launch(const void* q, const void* k, const void* v, void* o, int heads, int64_t Sq, int64_t Sk, int64_t ldq,
                             int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
                             float scale_log2e, int nqb, int64_t total, int nsplit, int64_t kv_chunk, float* opart, float* mlpart,
-                            hipStream_t st);
+                            hipStream_t st, void* oq, void* os, int64_t mx_bs);
 // default since round 3: the 16x16x32 body (tools/kbench.py attn --shapes 0,1: 4.21-4.33 vs 4.46-4.62 ms at cfg 3, in the model
 // 121.8 vs 124.6 ms of attention per step; both bodies pass the same tests).  DRN_ATT16=0 selects the 32x32x16 body below.
 #ifndef ATT_DEFAULT_SHAPE16
@@ -601,15 +619,37 @@ void drn_attention16_launch(const void* q, const void* k, const void* v, void* o
 static int g_att16 = -1;       // -1: DRN_ATT16 from the environment (default ATT_DEFAULT_SHAPE16); 0 / 1 forced (tests, A/B)
 extern "C" void drn_attention_force_shape16(int on) { g_att16 = on; }
 
+static bool attention_shape16() {
+    static int env16 = -1;
+    if (env16 < 0) {
+        const char* e = getenv("DRN_ATT16");
+        env16 = e ? (e[0] != '0') : ATT_DEFAULT_SHAPE16;
+    }
+    return (g_att16 >= 0 ? g_att16 : env16) != 0;
+}
+
+// whether drn_attention_bf16_mx / drn_attention_splitkv_bf16_mx can run (only the 16x16x32 body has the MX epilogue): host-only
+extern "C" int drn_attention_mx_available(void) { return attention_shape16() ? 1 : 0; }
+
+// oq / os != NULL: the output is (also) written as MXFP8, o may then be NULL (the _mx entry points)
 static int attention_launch(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t Sq, int64_t Sk,
                             int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv,
-                            int64_t bso, float scale, int nsplit, void* workspace, void* stream) {
-    DRN_CHECK_ARG(q && k && v && o && batch > 0 && heads > 0 && Sq >= 0 && Sk > 0 && nsplit >= 1);
+                            int64_t bso, float scale, int nsplit, void* workspace, void* stream, void* oq = nullptr,
+                            void* os = nullptr) {
+    DRN_CHECK_ARG(q && k && v && (o || oq) && batch > 0 && heads > 0 && Sq >= 0 && Sk > 0 && nsplit >= 1);
     DRN_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0);
     DRN_CHECK_ARG(bsq % 8 == 0 && bsk % 8 == 0 && bsv % 8 == 0 && bso % 8 == 0);
     DRN_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 15) == 0);
     // the tile DMA addresses a K / V row as a 32-bit byte offset from the tile's first row (64 rows x ld x 2 B)
     DRN_CHECK_ARG(ldk > 0 && ldv > 0 && 64 * ldk * 2 < (1ll << 32) && 64 * ldv * 2 < (1ll << 32));
+    int64_t mx_bs = 0;
+    if (oq) {
+        // MX output: rows of heads * 128 elements, contiguous; clip b starts bso / ldo rows after clip b - 1 (the bf16 geometry)
+        DRN_CHECK_ARG(os && attention_shape16() && ldo == (int64_t)heads * 128 && bso >= 0 && bso % ldo == 0);
+        DRN_CHECK_ARG(((uintptr_t)oq & 7) == 0 && ((uintptr_t)os & 3) == 0);
+        mx_bs = bso / ldo;
+        DRN_CHECK_ARG(batch == 1 || mx_bs >= Sq);
+    }
     if (Sq == 0) return DRN_OK;
     int64_t kv_chunk = Sk;
     if (nsplit > 1) {
@@ -624,22 +664,23 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
     float* opart = (float*)workspace;
     float* mlpart = opart ? opart + (int64_t)nsplit * batch * Sq * heads * 128 : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    static int env16 = -1;
-    if (env16 < 0) {
-        const char* e = getenv("DRN_ATT16");
-        env16 = e ? (e[0] != '0') : ATT_DEFAULT_SHAPE16;
-    }
-    if (g_att16 >= 0 ? g_att16 : env16) {
+    if (attention_shape16()) {
+        // (a launch whose keys are split writes fp32 partials: the MX epilogue is the combine kernel's)
         drn_attention16_launch(q, k, v, o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale_log2e, (int)nqb, total, nsplit,
-                               kv_chunk, opart, mlpart, st);
+                               kv_chunk, opart, mlpart, st, nsplit > 1 ? nullptr : oq, os, mx_bs);
     } else
     attention_fwd_kernel<<<dim3((unsigned)total, 1, 1), dim3(512), 0, st>>>(
         (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk,
         bsv, bso, scale_log2e, (int)nqb, (int)total, nsplit, kv_chunk, opart, mlpart);
     if (nsplit > 1) {
         const int64_t items = (int64_t)batch * Sq * heads;
-        attention_combine_kernel<<<dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch,
-                                                                                            heads, Sq, ldo, bso, scale_log2e);
+        const dim3 grid((unsigned)((items + 3) / 4));
+        if (oq)
+            attention_combine_kernel<true><<<grid, dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch, heads, Sq, ldo, bso,
+                                                                       scale_log2e, (uint8_t*)oq, (uint8_t*)os, mx_bs);
+        else
+            attention_combine_kernel<false><<<grid, dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch, heads, Sq, ldo, bso,
+                                                                        scale_log2e, nullptr, nullptr, 0);
     }
     return drn_launch_status();
 }
@@ -647,7 +688,15 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
 extern "C" int drn_attention_bf16(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t Sq,
                                   int64_t Sk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq,
                                   int64_t bsk, int64_t bsv, int64_t bso, float scale, void* stream) {
+    DRN_CHECK_ARG(o);
     return attention_launch(q, k, v, o, batch, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale, 1, nullptr, stream);
+}
+
+extern "C" int drn_attention_bf16_mx(const void* q, const void* k, const void* v, void* o, void* oq, void* os, int batch, int heads,
+                                     int64_t Sq, int64_t Sk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq,
+                                     int64_t bsk, int64_t bsv, int64_t bso, float scale, void* stream) {
+    DRN_CHECK_ARG(oq && os);
+    return attention_launch(q, k, v, o, batch, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale, 1, nullptr, stream, oq, os);
 }
 
 extern "C" int64_t drn_attention_splitkv_workspace_bytes(int batch, int heads, int64_t Sq, int nsplit) {
@@ -658,6 +707,16 @@ extern "C" int drn_attention_splitkv_bf16(const void* q, const void* k, const vo
                                           int64_t Sk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq,
                                           int64_t bsk, int64_t bsv, int64_t bso, float scale, int nsplit, void* workspace,
                                           void* stream) {
+    DRN_CHECK_ARG(o);
     return attention_launch(q, k, v, o, batch, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale, nsplit, workspace,
                             stream);
+}
+
+extern "C" int drn_attention_splitkv_bf16_mx(const void* q, const void* k, const void* v, void* o, void* oq, void* os, int batch,
+                                             int heads, int64_t Sq, int64_t Sk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                             int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, float scale, int nsplit,
+                                             void* workspace, void* stream) {
+    DRN_CHECK_ARG(oq && os);
+    return attention_launch(q, k, v, o, batch, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale, nsplit, workspace,
+                            stream, oq, os);
 }

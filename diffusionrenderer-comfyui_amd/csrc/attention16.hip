@@ -21,6 +21,7 @@
 // free the slot; hand-counted s_waitcnt lgkmcnt (V fragment = 2 LDS reads, K fragment = 1).  The last 8 reads of M(t) fetch the
 // first V key step of tile t for M(t+1) and stay in flight across S(t).
 #include "drn_common.h"
+#include "mx_quant.h"
 
 #define QROWS 256
 #define KVT 64
@@ -34,11 +35,14 @@
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
+// MX = true (a second instantiation: the bf16 one is untouched): the unsplit epilogue also writes the bf16 output row as MXFP8
+// (drn.h: elements OQ [batch * q_rows, heads * 128], scales OS [batch * q_rows, heads * 4], clip b at row b * mx_bs); O may be NULL.
+template <bool MX>
 __global__ __launch_bounds__(512, 2) void attention16_fwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kp, const bf16_t* __restrict__ Vp, bf16_t* __restrict__ O,
     int heads, int64_t Sq, int64_t Sk_total, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk,
     int64_t bsv, int64_t bso, float scale_log2e, int nqb, int total, int nsplit, int64_t kv_chunk,
-    float* __restrict__ Opart, float* __restrict__ MLpart) {
+    float* __restrict__ Opart, float* __restrict__ MLpart, uint8_t* __restrict__ OQ, uint8_t* __restrict__ OS, int64_t mx_bs) {
     __shared__ __attribute__((aligned(1024))) char smem[(NKB + NVB) * KBYTES];   // K0..K2 V0..V3 - the ONLY LDS object
 
     const int tid = threadIdx.x;
@@ -486,17 +490,39 @@ __global__ __launch_bounds__(512, 2) void attention16_fwd_kernel(
             const int row = 4 * j + (lane >> 4);
             const uint4 v = *reinterpret_cast<const uint4*>(ob + row * 256 + ((oc ^ (row & 15)) << 4));
             const int64_t qr = q0 + row;
-            if (qr < Sq) *reinterpret_cast<uint4*>(op + qr * ldo) = v;
+            if (!MX) {
+                if (qr < Sq) *reinterpret_cast<uint4*>(op + qr * ldo) = v;
+            } else {
+                // the lane's 8 consecutive d are a quarter of a 32-element block; lanes oc .. oc ^ 3 (same row) hold all of it:
+                // mx_quant_kernel's lane group on the bf16 values the store above would write -> the same bytes
+                uint32_t amax = max(max(mx_amax2(v.x), mx_amax2(v.y)), max(mx_amax2(v.z), mx_amax2(v.w)));
+                amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+                amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+                const int e = mx_block_exp(amax);
+                const float inv = mx_inv_scale(e);
+                if (qr < Sq) {
+                    const int64_t r = b * mx_bs + qr;
+                    *reinterpret_cast<uint2*>(OQ + (r * heads + head) * 128 + oc * 8) = make_uint2(mx_pack4(v.x, v.y, inv), mx_pack4(v.z, v.w, inv));
+                    if ((oc & 3) == 0) OS[(r * heads + head) * 4 + (oc >> 2)] = (uint8_t)(e + 127);
+                    if (O) *reinterpret_cast<uint4*>(op + qr * ldo) = v;
+                }
+            }
         }
     }
 }
 
-// called by attention.hip's launcher (same grid, same arguments as attention_fwd_kernel)
+// called by attention.hip's launcher (same grid, same arguments as attention_fwd_kernel); oq != NULL (unsplit launches only):
+// the MX-writing instantiation
 void drn_attention16_launch(const void* q, const void* k, const void* v, void* o, int heads, int64_t Sq, int64_t Sk, int64_t ldq,
                             int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
                             float scale_log2e, int nqb, int64_t total, int nsplit, int64_t kv_chunk, float* opart, float* mlpart,
-                            hipStream_t st) {
-    attention16_fwd_kernel<<<dim3((unsigned)total, 1, 1), dim3(512), 0, st>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso,
-        scale_log2e, nqb, (int)total, nsplit, kv_chunk, opart, mlpart);
+                            hipStream_t st, void* oq, void* os, int64_t mx_bs) {
+    if (oq)
+        attention16_fwd_kernel<true><<<dim3((unsigned)total, 1, 1), dim3(512), 0, st>>>(
+            (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso,
+            scale_log2e, nqb, (int)total, nsplit, kv_chunk, opart, mlpart, (uint8_t*)oq, (uint8_t*)os, mx_bs);
+    else
+        attention16_fwd_kernel<false><<<dim3((unsigned)total, 1, 1), dim3(512), 0, st>>>(
+            (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso,
+            scale_log2e, nqb, (int)total, nsplit, kv_chunk, opart, mlpart, nullptr, nullptr, 0);
 }

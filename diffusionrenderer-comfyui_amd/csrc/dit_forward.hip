@@ -10,6 +10,9 @@
 #include <stdlib.h>
 #include "drn_common.h"
 
+// attention.hip: 1 when the selected attention body has the MX epilogue (drn_attention_bf16_mx would run)
+extern "C" int drn_attention_mx_available(void);
+
 // ---- how to cover the (q-block, head) grid with whole rounds of the 256 CUs (was native.attention_plan; measured cost model)
 static const int kCUs = 256;
 
@@ -168,31 +171,47 @@ static int fwd_gemm(const drn_dit_forward_args* a, const void* A, const void* W,
 // The same for a block linear of a precision-1 (MXFP8) forward: quantise A into AQ | AS, then the MXFP8 product chosen as
 // native.gemm_mxfp8 chooses it (drn_gemm_mxfp8_splitk_choice on ONE clip's rows): drn_gemm_mxfp8 (0), the fused few-token kernel
 // (1) or its K slices (> 1; `defer` as in fwd_gemm, same conditions).
+// mx_fused forwards: QA | QSA != NULL = the producer of A wrote it as MX there already (no quantise launch; A is not read);
+// CQ | CS != NULL (MLP-up) = the GELU result leaves as MX through drn_gemm_mxfp8_gelu_mx where that entry has a kernel
+// (*c_is_mx = 1), else as bf16 into C (*c_is_mx = 0: the consumer quantises by launch, the same bytes).
 static int fwd_gemm_mx(const drn_dit_forward_args* a, const void* A, const void* W, const void* SW, void* C, int64_t M, int64_t N,
                        int64_t K, int64_t lda, int64_t ldc, int epi, const void* gate, const void* residual, int64_t ldr,
-                       void* stream, int* defer = nullptr) {
+                       void* stream, int* defer = nullptr, const void* QA = nullptr, const void* QSA = nullptr, void* CQ = nullptr,
+                       void* CS = nullptr, int* c_is_mx = nullptr) {
     const int64_t rpb = a->S;
     const int64_t Mb = (rpb > 0 && rpb < M && M % rpb == 0) ? rpb : M;
     if (defer) *defer = 0;
-    DRN_TRY(drn_mx_quant_bf16(A, M, K, lda, a->AQ, a->AS, stream));
+    if (c_is_mx) *c_is_mx = 0;
+    if (!QA) {
+        DRN_TRY(drn_mx_quant_bf16(A, M, K, lda, a->AQ, a->AS, stream));
+        QA = a->AQ;
+        QSA = a->AS;
+    }
     const int splits = drn_gemm_mxfp8_splitk_choice(Mb, N, K);
     Scope sc((drn_timer*)a->timer, 0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (residual ? 2 : 1), (hipStream_t)stream);
-    if (splits == 0) return drn_gemm_mxfp8(a->AQ, a->AS, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, stream);
+    if (CQ && epi == DRN_EPI_GELU && splits <= 1) {
+        if (c_is_mx) *c_is_mx = 1;
+        return drn_gemm_mxfp8_gelu_mx(QA, QSA, W, SW, CQ, CS, M, N, K, rpb, stream);
+    }
+    if (splits == 0) return drn_gemm_mxfp8(QA, QSA, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, stream);
     if (splits > 1) {
         if (!a->gemm_ws || drn_gemm_splitk_workspace_bytes(M, N, splits) > a->gemm_ws_bytes) return DRN_EINVAL;
         if (defer && epi == DRN_EPI_GATE_RES && N == a->D && N > 1024 && ldc == N && ldr == N && residual == C) {
             *defer = splits;
-            return drn_gemm_mxfp8_splitk_partials(a->AQ, a->AS, W, SW, M, N, K, rpb, splits, a->gemm_ws, stream);
+            return drn_gemm_mxfp8_splitk_partials(QA, QSA, W, SW, M, N, K, rpb, splits, a->gemm_ws, stream);
         }
     }
-    return drn_gemm_mxfp8_splitk(a->AQ, a->AS, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, splits, a->gemm_ws, stream);
+    return drn_gemm_mxfp8_splitk(QA, QSA, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, splits, a->gemm_ws, stream);
 }
 
 // a block linear in the precision of the forward
 static int fwd_lin(const drn_dit_forward_args* a, const void* A, const void* W, const void* SW, void* C, int64_t M, int64_t N,
-                   int64_t K, int epi, const void* gate, const void* residual, void* stream, int* defer = nullptr) {
+                   int64_t K, int epi, const void* gate, const void* residual, void* stream, int* defer = nullptr,
+                   const void* QA = nullptr, const void* QSA = nullptr, void* CQ = nullptr, void* CS = nullptr,
+                   int* c_is_mx = nullptr) {
     const int64_t ldr = residual ? N : 0;
-    if (a->precision == 1) return fwd_gemm_mx(a, A, W, SW, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer);
+    if (a->precision == 1)
+        return fwd_gemm_mx(a, A, W, SW, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer, QA, QSA, CQ, CS, c_is_mx);
     return fwd_gemm(a, A, W, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer);
 }
 
@@ -223,6 +242,10 @@ extern "C" int64_t drn_dit_forward_gemm_workspace_bytes(int64_t B, int64_t S, in
 extern "C" int64_t drn_dit_forward_mx_act_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden) {
     const int64_t k = D > hidden ? D : hidden;
     return B * S * k + B * S * (k / 32);
+}
+
+extern "C" int64_t drn_dit_forward_mx_u_bytes(int64_t B, int64_t S, int64_t hidden) {
+    return B * S * hidden + B * S * (hidden / 32);
 }
 
 extern "C" int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden) {
@@ -256,6 +279,9 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
             if (a->subs[i].kind == DRN_SUB_FA || a->subs[i].kind == DRN_SUB_MLP)
                 DRN_CHECK_ARG(a->subs[i].w_a && a->subs[i].w_b && a->subs[i].s_a && a->subs[i].s_b);
     }
+    DRN_CHECK_ARG(a->mx_fused == 0 || (a->mx_fused == 1 && a->precision == 1));
+    const bool mxf = a->mx_fused == 1;                   // producers write the quantised operand of the next block linear themselves
+    if (mxf) DRN_CHECK_ARG(a->UQ && a->US && a->u_act_bytes >= drn_dit_forward_mx_u_bytes(B, S, a->hidden));
     const bf16_t* shift = (const bf16_t*)a->shift;
     const bf16_t* scale = (const bf16_t*)a->scale;
     const bf16_t* gate = (const bf16_t*)a->gate;
@@ -272,18 +298,27 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
         const char* e = getenv("DRN_FUSE_SPLITK_LN");    // 0: the split-K epilogue and the LayerNorm as two launches (A/B runs)
         fuse = (e && e[0] == '0') ? 0 : 1;
     }
-    // LayerNorm + modulate of X into H, folding a deferred split-K epilogue in
-#define LN_NEXT(SH, SC)                                                                                               \
+    // LayerNorm + modulate of X into H, folding a deferred split-K epilogue in.  MXOUT (mx_fused, in front of a FA / MLP
+    // sub-block): the result goes to AQ | AS as MXFP8 [M, D] instead (H is not written): the q|k|v / MLP-up linear reads it there.
+#define LN_NEXT(SH, SC, MXOUT)                                                                                        \
     do {                                                                                                              \
         if (deferred) {                                                                                               \
-            DRN_TRY(drn_splitk_gate_res_ln_modulate(a->gemm_ws, deferred, a->X, deferred_gate, pending, SH, SC, a->H, M, D, S,  \
-                                                    a->eps, stream));                                                 \
+            if (MXOUT)                                                                                                \
+                DRN_TRY(drn_splitk_gate_res_ln_modulate_mx(a->gemm_ws, deferred, a->X, deferred_gate, pending, SH, SC, nullptr,   \
+                                                           a->AQ, a->AS, M, D, S, a->eps, stream));                   \
+            else                                                                                                      \
+                DRN_TRY(drn_splitk_gate_res_ln_modulate(a->gemm_ws, deferred, a->X, deferred_gate, pending, SH, SC, a->H, M, D,   \
+                                                        S, a->eps, stream));                                          \
             deferred = 0;                                                                                             \
+        } else if (MXOUT) {                                                                                           \
+            DRN_TRY(drn_ln_modulate_mx(a->X, pending, SH, SC, nullptr, a->AQ, a->AS, M, D, S, a->eps, stream));       \
         } else {                                                                                                      \
             DRN_TRY(drn_ln_modulate(a->X, pending, SH, SC, a->H, M, D, S, a->eps, stream));                           \
         }                                                                                                             \
         pending = nullptr;                                                                                            \
     } while (0)
+    const void* hq = mxf ? a->AQ : nullptr;              // the MX operand LN_NEXT left for q|k|v / MLP-up
+    const void* hs = mxf ? a->AS : nullptr;
     for (int i = 0; i < a->n_sub; ++i) {
         const drn_dit_sub* sb = &a->subs[i];
         const bf16_t* sh = shift + (int64_t)sb->site * a->shift_site_stride;
@@ -303,13 +338,16 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
             pending = (const bf16_t*)a->addvec + (int64_t)sb->ca_index * a->addvec_stride;
             continue;
         }
-        LN_NEXT(sh, sc);
+        LN_NEXT(sh, sc, mxf);
         if (sb->kind == DRN_SUB_FA) {
             DRN_CHECK_ARG(sb->w_a && sb->w_b && sb->qn && sb->kn && a->cos && a->sin);
             bf16_t* q = (bf16_t*)a->QKV;
             bf16_t* k = q + D;
             bf16_t* v = q + 2 * D;
-            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->QKV, M, 3 * D, D, DRN_EPI_NONE, nullptr, nullptr, stream));
+            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->QKV, M, 3 * D, D, DRN_EPI_NONE, nullptr, nullptr, stream, nullptr, hq, hs));
+            // mx_fused: attention writes O as MX into AQ | AS (the q|k|v GEMM that read them has finished in stream order);
+            // the 32x32x16 body has no MX epilogue: that site keeps bf16 O + the quantise launch (the same bytes)
+            const bool omx = mxf && drn_attention_mx_available();
             DRN_TRY(drn_qk_norm_rope(q, k, sb->qn, sb->kn, a->cos, a->sin, M, a->heads, 3 * D, 3 * D, S, 0, a->eps, stream));
             {
                 Scope tsc((drn_timer*)a->timer, 1, 4.0 * B * a->heads * S * S * 128, 2.0 * B * a->heads * 128 * (4.0 * S), (hipStream_t)stream);
@@ -320,30 +358,44 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
                     const int ns = (int)plan[3 * p + 2];
                     const bf16_t* qs = q + q0 * 3 * D;
                     bf16_t* os = (bf16_t*)a->O + q0 * D;
+                    uint8_t* oq = omx ? (uint8_t*)a->AQ + q0 * D : nullptr;
+                    uint8_t* osc = omx ? (uint8_t*)a->AS + q0 * (D / 32) : nullptr;
                     if (ns > 1) {
                         if (!a->attn_ws || drn_attention_splitkv_workspace_bytes((int)B, a->heads, nq, ns) > a->attn_ws_bytes) return DRN_EINVAL;
+                        if (omx)
+                            DRN_TRY(drn_attention_splitkv_bf16_mx(qs, k, v, nullptr, oq, osc, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D,
+                                                                  D, S * 3 * D, S * 3 * D, S * 3 * D, S * D, sm_scale, ns, a->attn_ws, stream));
+                        else
                         DRN_TRY(drn_attention_splitkv_bf16(qs, k, v, os, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D, D, S * 3 * D,
                                                            S * 3 * D, S * 3 * D, S * D, sm_scale, ns, a->attn_ws, stream));
+                    } else if (omx) {
+                        DRN_TRY(drn_attention_bf16_mx(qs, k, v, nullptr, oq, osc, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D, D, S * 3 * D,
+                                                      S * 3 * D, S * 3 * D, S * D, sm_scale, stream));
                     } else {
                         DRN_TRY(drn_attention_bf16(qs, k, v, os, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D, D, S * 3 * D, S * 3 * D,
                                                    S * 3 * D, S * D, sm_scale, stream));
                     }
                 }
             }
-            DRN_TRY(fwd_lin(a, a->O, sb->w_b, sb->s_b, a->X, M, D, D, DRN_EPI_GATE_RES, gt, a->X, stream, fuse ? &deferred : nullptr));
+            DRN_TRY(fwd_lin(a, a->O, sb->w_b, sb->s_b, a->X, M, D, D, DRN_EPI_GATE_RES, gt, a->X, stream, fuse ? &deferred : nullptr,
+                            omx ? a->AQ : nullptr, omx ? a->AS : nullptr));
             deferred_gate = gt;
         } else if (sb->kind == DRN_SUB_MLP) {
             DRN_CHECK_ARG(sb->w_a && sb->w_b);
-            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->U, M, a->hidden, D, DRN_EPI_GELU, nullptr, nullptr, stream));
+            // mx_fused: MLP-up reads AQ | AS and writes U as MX into UQ | US (a second buffer: written while AQ is read) where the
+            // GELU -> MX epilogue exists; a sliced MLP-up writes bf16 U and MLP-down quantises it by launch
+            int umx = 0;
+            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->U, M, a->hidden, D, DRN_EPI_GELU, nullptr, nullptr, stream, nullptr, hq, hs,
+                            mxf ? a->UQ : nullptr, mxf ? a->US : nullptr, &umx));
             DRN_TRY(fwd_lin(a, a->U, sb->w_b, sb->s_b, a->X, M, D, a->hidden, DRN_EPI_GATE_RES, gt, a->X, stream,
-                            fuse ? &deferred : nullptr));
+                            fuse ? &deferred : nullptr, umx ? a->UQ : nullptr, umx ? a->US : nullptr));
             deferred_gate = gt;
         } else {
             return DRN_EINVAL;
         }
     }
     // final layer (CleanGeneralDIT.py:583-590): LN + modulate with the first 2D of the LoRA vector, Linear(D -> n_final)
-    LN_NEXT((const bf16_t*)a->final_shift, (const bf16_t*)a->final_scale);
+    LN_NEXT((const bf16_t*)a->final_shift, (const bf16_t*)a->final_scale, false);
 #undef LN_NEXT
     DRN_TRY(fwd_gemm(a, a->H, a->w_final, a->Y, M, a->n_final, D, D, a->n_final, DRN_EPI_NONE, nullptr, nullptr, 0, stream));
     return DRN_OK;

@@ -3,6 +3,7 @@
 // fp contraction is off in this file: several kernels are bit-exact restatements of unfused torch fp32 ops.
 #pragma clang fp contract(off)
 #include "drn_common.h"
+#include "mx_quant.h"
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm (no affine) + AdaLN modulate, optional broadcast pre-add.
@@ -16,6 +17,35 @@
 //   * ln_modulate_kernel4<NCH>:  four waves per row, wave w owns group w, partial sums meet in LDS - few rows (cfg 1: 256 rows
 //     on 64 workgroups of the one-wave kernel took 11.7 us per call, a chain of three memory round trips on a quarter of the CUs).
 // NCH < 4 (D <= 1024: the tiny test networks) keeps a single butterfly and has no four-wave form.
+// Where the modulated row goes.  MX = false: h [rows, D] bf16 (the kernels as they always were; hq / hs are unused trailing
+// arguments).  MX = true: the same bf16 values quantised as MXFP8 (drn.h: elements hq [rows, D] + one E8M0 byte per 32 columns in
+// hs), and h as well when it is not NULL.  A lane's 8 columns are a quarter of a 32-column block and the lanes l .. l ^ 3 hold the
+// whole block (D % 32 == 0: the four are inside the row or outside it together): mx_quant_kernel's lane group, so the bytes are
+// those of drn_mx_quant_bf16 on h.
+template <bool MX>
+__device__ __forceinline__ void ln_store(bf16_t* hr, uint8_t* hq, uint8_t* hs, int64_t row, int c, int D, const float (&o)[8]) {
+    if (!MX) {
+        *reinterpret_cast<uint4*>(hr + c) = pack8(o);
+    } else {
+        // the row is the same for the whole wave: as a scalar its three output addresses cost no VGPRs (as a vector value the
+        // one-wave kernel at NCH = 4 took 70 VGPRs, 7 waves per SIMD against the bf16 form's 8)
+        row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)row);
+        // o[] is bf16-exact (rounded through bf16 above): amax and elements straight from it, the packed row only for h
+        uint32_t amax = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = max(amax, mx_abs_bits(o[j]));
+        amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+        amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+        const int e = mx_block_exp(amax);
+        const float inv = mx_inv_scale(e);
+        if (hr) *reinterpret_cast<uint4*>(hr + c) = pack8(o);
+        uint8_t* qrow = hq + row * D;                       // scalar bases + 32-bit lane offsets (saddr stores)
+        uint8_t* srow = hs + row * (D / 32);
+        *reinterpret_cast<uint2*>(qrow + (uint32_t)c) = make_uint2(mx_pack4f(o[0], o[1], o[2], o[3], inv), mx_pack4f(o[4], o[5], o[6], o[7], inv));
+        if ((threadIdx.x & 3) == 0) srow[(uint32_t)c >> 5] = (uint8_t)(e + 127);
+    }
+}
+
 template <int NCH>
 __device__ __forceinline__ float ln_tree_sum(const float (&part)[NCH]) {
     if (NCH < 4) {
@@ -41,11 +71,12 @@ __device__ __forceinline__ float ln_tree_sum(const float (&part)[NCH]) {
     return (g[0] + g[1]) + (g[2] + g[3]);
 }
 
-template <int NCH>
+template <int NCH, bool MX>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ add,
                                                           const bf16_t* __restrict__ shift,
                                                           const bf16_t* __restrict__ scale, bf16_t* __restrict__ h,
-                                                          int64_t rows, int D, int64_t rpb, float eps) {
+                                                          int64_t rows, int D, int64_t rpb, float eps,
+                                                          uint8_t* __restrict__ hq, uint8_t* __restrict__ hs) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -94,7 +125,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(bf16_t* __restrict__ x
     const float rstd = 1.0f / sqrtf(var + eps);
     const bf16_t* sh = shift + b * D;
     const bf16_t* sc = scale + b * D;
-    bf16_t* hr = h + row * D;
+    bf16_t* hr = (MX && !h) ? nullptr : h + row * D;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c = (lane + 64 * i) * 8;
@@ -108,18 +139,19 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(bf16_t* __restrict__ x
                 const float s1 = rbf(1.0f + fc[j]);
                 o[j] = rbf(rbf(n * s1) + fs[j]);
             }
-            *reinterpret_cast<uint4*>(hr + c) = pack8(o);
+            ln_store<MX>(hr, hq, hs, row, c, D, o);
         }
     }
 }
 
 // four waves per row: wave w owns chunks w * G .. w * G + G - 1 (G = NCH / 4); D must fill all NCH chunk columns' lanes or leave
 // whole lanes empty exactly as above (c < D test per chunk)
-template <int NCH>
+template <int NCH, bool MX>
 __global__ __launch_bounds__(256) void ln_modulate_kernel4(bf16_t* __restrict__ x, const bf16_t* __restrict__ add,
                                                            const bf16_t* __restrict__ shift,
                                                            const bf16_t* __restrict__ scale, bf16_t* __restrict__ h,
-                                                           int64_t rows, int D, int64_t rpb, float eps) {
+                                                           int64_t rows, int D, int64_t rpb, float eps,
+                                                           uint8_t* __restrict__ hq, uint8_t* __restrict__ hs) {
     static_assert(NCH >= 4 && NCH % 4 == 0, "four-wave form needs whole chunk groups");
     constexpr int G = NCH / 4;
     __shared__ float red[2][4];
@@ -178,7 +210,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel4(bf16_t* __restrict__ 
     __syncthreads();
     const float var = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)D;
     const float rstd = 1.0f / sqrtf(var + eps);
-    bf16_t* hr = h + row * D;
+    bf16_t* hr = (MX && !h) ? nullptr : h + row * D;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int c = (lane + 64 * (w * G + g)) * 8;
@@ -190,7 +222,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel4(bf16_t* __restrict__ 
                 const float s1 = rbf(1.0f + fc[g][j]);
                 o[j] = rbf(rbf(n * s1) + fs[g][j]);
             }
-            *reinterpret_cast<uint4*>(hr + c) = pack8(o);
+            ln_store<MX>(hr, hq, hs, row, c, D, o);
         }
     }
 }
@@ -202,12 +234,13 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel4(bf16_t* __restrict__ 
 //   x     = bf16(x + add_vec) if add_vec                 written back instead         (= ln_modulate's broadcast pre-add)
 //   h     = modulate(LayerNorm(x))                       four waves per row           (= ln_modulate_kernel4: same summation tree)
 // Every step rounds where the separate kernels round: the same bits as epilogue kernel + ln_modulate.
-template <int NCH>
+template <int NCH, bool MX>
 __global__ __launch_bounds__(256) void splitk_gate_res_ln_kernel(const float* __restrict__ part, int splits, int64_t part_stride,
                                                                  bf16_t* __restrict__ x, const bf16_t* __restrict__ gate,
                                                                  const bf16_t* __restrict__ add, const bf16_t* __restrict__ shift,
                                                                  const bf16_t* __restrict__ scale, bf16_t* __restrict__ h,
-                                                                 int D, int64_t rpb, float eps) {
+                                                                 int D, int64_t rpb, float eps,
+                                                                 uint8_t* __restrict__ hq, uint8_t* __restrict__ hs) {
     static_assert(NCH >= 4 && NCH % 4 == 0, "four waves per row");
     constexpr int G = NCH / 4;
     __shared__ float red[2][4];
@@ -295,7 +328,7 @@ __global__ __launch_bounds__(256) void splitk_gate_res_ln_kernel(const float* __
     __syncthreads();
     const float var = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)D;
     const float rstd = 1.0f / sqrtf(var + eps);
-    bf16_t* hr = h + row * D;
+    bf16_t* hr = (MX && !h) ? nullptr : h + row * D;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int c = (lane + 64 * (w * G + g)) * 8;
@@ -307,24 +340,25 @@ __global__ __launch_bounds__(256) void splitk_gate_res_ln_kernel(const float* __
                 const float s1 = rbf(1.0f + fc[g][j]);
                 o[j] = rbf(rbf(n * s1) + fs[g][j]);
             }
-            *reinterpret_cast<uint4*>(hr + c) = pack8(o);
+            ln_store<MX>(hr, hq, hs, row, c, D, o);
         }
     }
 }
 
-extern "C" int drn_splitk_gate_res_ln_modulate(const void* partials, int splits, void* x, const void* gate, const void* add_vec,
-                                               const void* shift, const void* scale, void* h, int64_t rows, int64_t D,
-                                               int64_t rows_per_batch, float eps, void* stream) {
-    DRN_CHECK_ARG(partials && x && gate && shift && scale && h && splits >= 1 && rows >= 0 && rows < (1ll << 31));
+template <bool MX>
+static int launch_splitk_gate_res_ln(const void* partials, int splits, void* x, const void* gate, const void* add_vec,
+                                     const void* shift, const void* scale, void* h, void* hq, void* hs, int64_t rows, int64_t D,
+                                     int64_t rows_per_batch, float eps, void* stream) {
+    DRN_CHECK_ARG(partials && x && gate && shift && scale && splits >= 1 && rows >= 0 && rows < (1ll << 31));
     DRN_CHECK_ARG(D > 1024 && D % 8 == 0 && D <= 8192 && rows_per_batch > 0 && ((uintptr_t)partials & 15) == 0);
     if (rows == 0) return DRN_OK;
     const int nch = (int)((D + 511) / 512);
     dim3 grid((unsigned)rows), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH(N)                                                                                                     \
-    splitk_gate_res_ln_kernel<N><<<grid, block, 0, st>>>((const float*)partials, splits, rows * D, (bf16_t*)x,       \
+    splitk_gate_res_ln_kernel<N, MX><<<grid, block, 0, st>>>((const float*)partials, splits, rows * D, (bf16_t*)x,   \
         (const bf16_t*)gate, (const bf16_t*)add_vec, (const bf16_t*)shift, (const bf16_t*)scale, (bf16_t*)h, (int)D,  \
-        rows_per_batch, eps)
+        rows_per_batch, eps, (uint8_t*)hq, (uint8_t*)hs)
     if (nch <= 4) LAUNCH(4);
     else if (nch <= 8) LAUNCH(8);
     else LAUNCH(16);
@@ -332,12 +366,29 @@ extern "C" int drn_splitk_gate_res_ln_modulate(const void* partials, int splits,
     return drn_launch_status();
 }
 
+extern "C" int drn_splitk_gate_res_ln_modulate(const void* partials, int splits, void* x, const void* gate, const void* add_vec,
+                                               const void* shift, const void* scale, void* h, int64_t rows, int64_t D,
+                                               int64_t rows_per_batch, float eps, void* stream) {
+    DRN_CHECK_ARG(h);
+    return launch_splitk_gate_res_ln<false>(partials, splits, x, gate, add_vec, shift, scale, h, nullptr, nullptr, rows, D,
+                                            rows_per_batch, eps, stream);
+}
+
+extern "C" int drn_splitk_gate_res_ln_modulate_mx(const void* partials, int splits, void* x, const void* gate, const void* add_vec,
+                                                  const void* shift, const void* scale, void* h, void* hq, void* hs, int64_t rows,
+                                                  int64_t D, int64_t rows_per_batch, float eps, void* stream) {
+    DRN_CHECK_ARG(hq && hs && D % 32 == 0 && ((uintptr_t)hq & 7) == 0);
+    return launch_splitk_gate_res_ln<true>(partials, splits, x, gate, add_vec, shift, scale, h, hq, hs, rows, D, rows_per_batch, eps,
+                                           stream);
+}
+
 static int g_ln_force = -1;      // tests: 0 = one wave per row always, 1 = four waves per row wherever it exists, -1 = by row count
 extern "C" void drn_ln_force_kernel(int which) { g_ln_force = which; }
 
-extern "C" int drn_ln_modulate(void* x, const void* add_vec, const void* shift, const void* scale, void* h,
-                               int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream) {
-    DRN_CHECK_ARG(x && shift && scale && h && rows >= 0 && D > 0 && D % 8 == 0 && D <= 8192 && rows_per_batch > 0);
+template <bool MX>
+static int launch_ln_modulate(void* x, const void* add_vec, const void* shift, const void* scale, void* h, void* hq, void* hs,
+                              int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream) {
+    DRN_CHECK_ARG(x && shift && scale && rows >= 0 && D > 0 && D % 8 == 0 && D <= 8192 && rows_per_batch > 0);
     if (rows == 0) return DRN_OK;
     hipStream_t st = (hipStream_t)stream;
     const int nch = (int)((D + 511) / 512);
@@ -347,8 +398,8 @@ extern "C" int drn_ln_modulate(void* x, const void* add_vec, const void* shift, 
     const bool four = nch > 2 && rows < (1ll << 31) && (g_ln_force == 1 || (g_ln_force < 0 && (rows <= 4096 || !add_vec)));
     dim3 grid(four ? (unsigned)rows : (unsigned)((rows + 3) / 4)), block(256);
 #define LAUNCH(K, N)                                                                                                  \
-    K<N><<<grid, block, 0, st>>>((bf16_t*)x, (const bf16_t*)add_vec, (const bf16_t*)shift, (const bf16_t*)scale,      \
-                                 (bf16_t*)h, rows, (int)D, rows_per_batch, eps)
+    K<N, MX><<<grid, block, 0, st>>>((bf16_t*)x, (const bf16_t*)add_vec, (const bf16_t*)shift, (const bf16_t*)scale,  \
+                                     (bf16_t*)h, rows, (int)D, rows_per_batch, eps, (uint8_t*)hq, (uint8_t*)hs)
     if (nch <= 1) LAUNCH(ln_modulate_kernel, 1);
     else if (nch <= 2) LAUNCH(ln_modulate_kernel, 2);
     else if (nch <= 4) { if (four) LAUNCH(ln_modulate_kernel4, 4); else LAUNCH(ln_modulate_kernel, 4); }
@@ -356,6 +407,18 @@ extern "C" int drn_ln_modulate(void* x, const void* add_vec, const void* shift, 
     else { if (four) LAUNCH(ln_modulate_kernel4, 16); else LAUNCH(ln_modulate_kernel, 16); }
 #undef LAUNCH
     return drn_launch_status();
+}
+
+extern "C" int drn_ln_modulate(void* x, const void* add_vec, const void* shift, const void* scale, void* h,
+                               int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream) {
+    DRN_CHECK_ARG(h);
+    return launch_ln_modulate<false>(x, add_vec, shift, scale, h, nullptr, nullptr, rows, D, rows_per_batch, eps, stream);
+}
+
+extern "C" int drn_ln_modulate_mx(void* x, const void* add_vec, const void* shift, const void* scale, void* h, void* hq, void* hs,
+                                  int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream) {
+    DRN_CHECK_ARG(hq && hs && D % 32 == 0 && ((uintptr_t)hq & 7) == 0);
+    return launch_ln_modulate<true>(x, add_vec, shift, scale, h, hq, hs, rows, D, rows_per_batch, eps, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

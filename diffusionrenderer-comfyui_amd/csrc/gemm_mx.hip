@@ -17,6 +17,7 @@
 // the 16x16 shape (col = lane & 15, row = 4 * (lane >> 4) + r) then gives a lane 4 consecutive output COLUMNS of one row.
 #include <type_traits>
 #include "drn_common.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -25,39 +26,11 @@ constexpr int MX_K = 128;                        // K step (elements = bytes)
 constexpr int MX_DATA = MX_T * MX_K;             // 32 KiB per operand per stage
 constexpr int MX_STAGE = 2 * MX_DATA + 2 * MX_T * 4;
 constexpr int MX_A = 0, MX_W = MX_DATA, MX_SA = 2 * MX_DATA, MX_SW = 2 * MX_DATA + MX_T * 4;
+constexpr int EPI_GELU_MX = 4;                   // internal: bf16(gelu(bf16(acc))) written as MXFP8 (C = elements [M, N], CS = scales)
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef const __attribute__((address_space(1))) void* mx_gptr_t;
 typedef __attribute__((address_space(3))) void* mx_lptr_t;
-
-// |v| <= 448, finite -> OCP e4m3fn bits, round to nearest even (integer arithmetic: the same bits as torch's conversion)
-__device__ __forceinline__ uint32_t f32_to_e4m3(float v) {
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t sign = (u >> 24) & 0x80u;
-    const uint32_t a = u & 0x7fffffffu;
-    uint32_t r;
-    if (a >= 0x3c800000u) {                                   // >= 2^-6: normal e4m3, 3 mantissa bits kept
-        r = ((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3);
-    } else {                                                  // subnormal e4m3: multiples of 2^-9 (8 * 2^-9 = the smallest normal)
-        r = (uint32_t)__builtin_rintf(__uint_as_float(a) * 512.0f);
-    }
-    return r | sign;
-}
-
-// E8M0 exponent of a block from the bit pattern of its bf16 absolute maximum (finite): floor(log2(amax)) - 8, one more when the
-// significand of amax is above 1.75 (so that amax / 2^e <= 448), clamped to [-127, 127]; an all-zero block gets -127.
-__device__ __forceinline__ int mx_block_exp(uint32_t amax_bits) {
-    if (amax_bits == 0) return -127;
-    const int E = (int)(amax_bits >> 7), m = (int)(amax_bits & 0x7f);
-    int e;
-    if (E > 0) {
-        e = E - 127 - 8 + (m > 96 ? 1 : 0);                   // 1 + m / 128 > 1.75
-    } else {                                                  // bf16 subnormal: m * 2^-133
-        const int p = 31 - __builtin_clz((unsigned)m);
-        e = -133 + p - 8 + (4 * m > 7 * (1 << p) ? 1 : 0);
-    }
-    return e < -127 ? -127 : (e > 127 ? 127 : e);
-}
 
 // 4 lanes per 32-element block, 8 elements per lane: lane-group amax by two xor shuffles
 __global__ __launch_bounds__(256) void mx_quant_kernel(const bf16_t* __restrict__ X, int64_t ldx, int chunks_per_row, int total,
@@ -103,7 +76,8 @@ template <int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ SA,
                                                          const uint8_t* __restrict__ W, const uint8_t* __restrict__ SW,
                                                          bf16_t* C, int64_t M, int64_t N, int64_t K, int64_t ldc,
-                                                         const bf16_t* __restrict__ gate, const bf16_t* R, int64_t ldr, int64_t rpb) {
+                                                         const bf16_t* __restrict__ gate, const bf16_t* R, int64_t ldr, int64_t rpb,
+                                                         uint8_t* __restrict__ CS) {
     // the two stages as two LDS objects: the reads of one and the DMA into the other then provably do not alias, and the
     // compiler puts no vmcnt wait of its own in front of the fragment reads (one shared array: a vmcnt(0) before every step)
     __shared__ __attribute__((aligned(1024))) char lds0[MX_STAGE];
@@ -205,6 +179,40 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
     }
 
     // epilogue: lane holds C[m0 + wm*128 + 16 mt + fr][n0 + wn*64 + 16 nt + 4 fq + r], r = 0..3 (8-byte stores)
+    if (EPI == EPI_GELU_MX) {
+        // the GELU epilogue, its bf16 result quantised here (drn.h; the bytes of drn_mx_quant_bf16 on what DRN_EPI_GELU writes): the
+        // 32-column block j of a row is the tiles nt = 2 j, 2 j + 1 of the four lanes fq = 0..3 (lane ^ 16, lane ^ 32) with the
+        // same fr, 8 values each.  The shuffles run for every row (a ragged last tile only masks the stores).
+        uint8_t* CQ = reinterpret_cast<uint8_t*>(C);
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) {
+            const int64_t m = m0 + wm * 128 + mt * 16 + fr;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                uint32_t w[2][2];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    float v[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = gelu_erf_fast(rbf(acc[mt][2 * j + t][r]));
+                    w[t][0] = pack_bf2(v[0], v[1]);
+                    w[t][1] = pack_bf2(v[2], v[3]);
+                }
+                uint32_t amax = max(max(mx_amax2(w[0][0]), mx_amax2(w[0][1])), max(mx_amax2(w[1][0]), mx_amax2(w[1][1])));
+                amax = max(amax, (uint32_t)__shfl_xor((int)amax, 16, 64));
+                amax = max(amax, (uint32_t)__shfl_xor((int)amax, 32, 64));
+                const int e = mx_block_exp(amax);
+                const float inv = mx_inv_scale(e);
+                const int64_t n = n0 + wn * 64 + j * 32 + fq * 4;
+                if (m < M) {
+                    *reinterpret_cast<uint32_t*>(CQ + m * N + n) = mx_pack4(w[0][0], w[0][1], inv);
+                    *reinterpret_cast<uint32_t*>(CQ + m * N + n + 16) = mx_pack4(w[1][0], w[1][1], inv);
+                    if (fq == 0) CS[m * (N / 32) + (n >> 5)] = (uint8_t)(e + 127);
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
         const int64_t m = m0 + wm * 128 + mt * 16 + fr;
@@ -234,21 +242,36 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
 
 template <int EPI>
 int launch_mx(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K, int64_t ldc,
-              const void* gate, const void* R, int64_t ldr, int64_t rpb, hipStream_t st) {
+              const void* gate, const void* R, int64_t ldr, int64_t rpb, hipStream_t st, void* CS = nullptr) {
     const int64_t tiles = (M + MX_T - 1) / MX_T * (N / MX_T);
     gemm_mx_kernel<EPI><<<dim3((unsigned)tiles), dim3(512), 0, st>>>(
         (const uint8_t*)A, (const uint8_t*)SA, (const uint8_t*)W, (const uint8_t*)SW, (bf16_t*)C, M, N, K, ldc,
-        (const bf16_t*)gate, (const bf16_t*)R, ldr, rpb);
+        (const bf16_t*)gate, (const bf16_t*)R, ldr, rpb, (uint8_t*)CS);
     return drn_launch_status();
 }
 
 }  // namespace
+
+// the 256 x 256 kernel with the GELU -> MX epilogue (drn_gemm_mxfp8_gelu_mx in gemm_mx_tall.hip validates and dispatches)
+int drn_gemm_mx_gelu_mx_launch(const void* A, const void* SA, const void* W, const void* SW, void* CQ, void* CS, int64_t M, int64_t N,
+                               int64_t K, void* stream) {
+    DRN_CHECK_ARG((M + MX_T - 1) / MX_T * (N / MX_T) < (1ll << 31));
+    return launch_mx<EPI_GELU_MX>(A, SA, W, SW, CQ, M, N, K, N, nullptr, nullptr, 0, 1, (hipStream_t)stream, CS);
+}
+
+static int64_t g_mx_quant_calls = 0;       // launches enqueued by drn_mx_quant_bf16 (host-side; one host thread per process: drn.h)
+extern "C" int64_t drn_mx_quant_calls(int reset) {
+    const int64_t n = g_mx_quant_calls;
+    if (reset) g_mx_quant_calls = 0;
+    return n;
+}
 
 extern "C" int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q, void* scales, void* stream) {
     DRN_CHECK_ARG(X && Q && scales && M >= 1 && K >= 32 && K % 32 == 0 && ldx >= K && ldx % 8 == 0);
     DRN_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 7) == 0);
     DRN_CHECK_ARG(M * (K / 8) < (1ll << 31));
     const int total = (int)(M * (K / 8));
+    ++g_mx_quant_calls;
     mx_quant_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
         (const bf16_t*)X, ldx, (int)(K / 8), total, (uint8_t*)Q, (uint8_t*)scales, K);
     return drn_launch_status();

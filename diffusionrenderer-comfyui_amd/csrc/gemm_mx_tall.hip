@@ -23,11 +23,13 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "drn_common.h"
+#include "mx_quant.h"
 
 namespace {
 
 constexpr int MXT_K = 128;                 // K step (elements = bytes)
 constexpr int EPI_PARTIAL = 3;             // internal: fp32 slice [blockIdx.y][M][N] to the workspace
+constexpr int EPI_GELU_MX = 4;             // internal: bf16(gelu(bf16(acc))) written as MXFP8 (Cv = elements [M, N], CS = scales)
 #ifndef MX_TALL_SHAPE_DEFAULT
 #define MX_TALL_SHAPE_DEFAULT 1            // 0: 256 x 64 (3 stages), 1: 128 x 128 (4 stages); DRN_MX_TALL_SHAPE overrides
 #endif
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_tall_kernel(const uint8_t* __r
                                                               const uint8_t* __restrict__ W, const uint8_t* __restrict__ SW,
                                                               void* Cv, int64_t M, int64_t N, int64_t K, int64_t ldc,
                                                               const bf16_t* __restrict__ gate, const bf16_t* R, int64_t ldr,
-                                                              int64_t rpb) {
+                                                              int64_t rpb, uint8_t* __restrict__ CS) {
     constexpr int A_BYTES = TM * MXT_K, W_BYTES = TN * MXT_K, S_OFF = A_BYTES + W_BYTES;
     constexpr int STAGE_BYTES = S_OFF + (TM + TN) * 4;
     constexpr int WN = TN / 32;                // waves across the columns (8 / WN down the rows), wave tile 64 x 32
@@ -175,6 +177,34 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_tall_kernel(const uint8_t* __r
     else kloop(std::integral_constant<int, 0>());
 
     // ---- epilogue: a lane holds columns n .. n + 3 of row m
+    if (EPI == EPI_GELU_MX) {
+        // the wave's 32 columns are ONE MX block per row: tiles nt = 0, 1 of the four lanes fq = 0..3 (lane ^ 16, lane ^ 32) with
+        // the same fr.  The bf16 result of the GELU epilogue, quantised as drn_mx_quant_bf16 would (gemm_mx.hip, drn.h).
+        uint8_t* CQ = reinterpret_cast<uint8_t*>(Cv);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int64_t m = m0 + wm * 64 + mt * 16 + fr;
+            uint32_t w[2][2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = gelu_erf_fast(rbf(acc[mt][t][r]));
+                w[t][0] = pack_bf2(v[0], v[1]);
+                w[t][1] = pack_bf2(v[2], v[3]);
+            }
+            uint32_t amax = max(max(mx_amax2(w[0][0]), mx_amax2(w[0][1])), max(mx_amax2(w[1][0]), mx_amax2(w[1][1])));
+            amax = max(amax, (uint32_t)__shfl_xor((int)amax, 16, 64));
+            amax = max(amax, (uint32_t)__shfl_xor((int)amax, 32, 64));
+            const int e = mx_block_exp(amax);
+            const float inv = mx_inv_scale(e);
+            const int64_t n = n0 + wn * 32 + fq * 4;
+            *reinterpret_cast<uint32_t*>(CQ + m * N + n) = mx_pack4(w[0][0], w[0][1], inv);
+            *reinterpret_cast<uint32_t*>(CQ + m * N + n + 16) = mx_pack4(w[1][0], w[1][1], inv);
+            if (fq == 0) CS[m * (N / 32) + (n >> 5)] = (uint8_t)(e + 127);
+        }
+        return;
+    }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
         const int64_t m = m0 + wm * 64 + mt * 16 + fr;
@@ -214,6 +244,7 @@ struct mx_args {
     int64_t ldr, rpb;
     int splits;
     hipStream_t st;
+    void* CS;                          // EPI_GELU_MX: the scale bytes (C = the elements)
 };
 
 template <int EPI, int TM, int TN, int NSTAGE>
@@ -230,7 +261,7 @@ int launch_shape(const mx_args& a) {
     const int64_t tiles = (a.M / TM) * (a.N / TN);
     gemm_mx_tall_kernel<EPI, TM, TN, NSTAGE><<<dim3((unsigned)tiles, (unsigned)a.splits), dim3(512), LDS, a.st>>>(
         (const uint8_t*)a.A, (const uint8_t*)a.SA, (const uint8_t*)a.W, (const uint8_t*)a.SW, a.C, a.M, a.N, a.K, a.ldc,
-        (const bf16_t*)a.gate, (const bf16_t*)a.residual, a.ldr, a.rpb);
+        (const bf16_t*)a.gate, (const bf16_t*)a.residual, a.ldr, a.rpb, (uint8_t*)a.CS);
     return drn_launch_status();
 }
 
@@ -310,7 +341,7 @@ extern "C" int drn_gemm_mxfp8_splitk_partials(const void* A, const void* SA, con
     DRN_CHECK_ARG(A && SA && W && SW && workspace && splits > 1 && shape_ok(M, N, K, rows_per_batch, splits));
     DRN_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)SA & 3) == 0 && ((uintptr_t)SW & 3) == 0);
     DRN_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
-    const mx_args a = {A, SA, W, SW, workspace, M, N, K, N, nullptr, nullptr, 0, M, splits, (hipStream_t)stream};
+    const mx_args a = {A, SA, W, SW, workspace, M, N, K, N, nullptr, nullptr, 0, M, splits, (hipStream_t)stream, nullptr};
     return launch<EPI_PARTIAL>(a);
 }
 
@@ -326,15 +357,34 @@ extern "C" int drn_gemm_mxfp8_splitk(const void* A, const void* SA, const void* 
         DRN_CHECK_ARG(gate && residual && ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual & 7) == 0 && ((uintptr_t)gate & 7) == 0);
     if (splits > 1) {
         DRN_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0);
-        const mx_args a = {A, SA, W, SW, workspace, M, N, K, N, nullptr, nullptr, 0, M, splits, (hipStream_t)stream};
+        const mx_args a = {A, SA, W, SW, workspace, M, N, K, N, nullptr, nullptr, 0, M, splits, (hipStream_t)stream, nullptr};
         const int rc = launch<EPI_PARTIAL>(a);
         if (rc != DRN_OK) return rc;
         return drn_gemm_splitk_reduce(workspace, splits, C, M, N, ldc, epilogue, gate, residual, ldr, rpb, stream);
     }
-    const mx_args a = {A, SA, W, SW, C, M, N, K, ldc, gate, residual, ldr, rpb, 1, (hipStream_t)stream};
+    const mx_args a = {A, SA, W, SW, C, M, N, K, ldc, gate, residual, ldr, rpb, 1, (hipStream_t)stream, nullptr};
     switch (epilogue) {
         case DRN_EPI_NONE: return launch<DRN_EPI_NONE>(a);
         case DRN_EPI_GELU: return launch<DRN_EPI_GELU>(a);
         default: return launch<DRN_EPI_GATE_RES>(a);
     }
+}
+
+// gemm_mx.hip: the 256 x 256 kernel with the GELU -> MX epilogue
+int drn_gemm_mx_gelu_mx_launch(const void* A, const void* SA, const void* W, const void* SW, void* CQ, void* CS, int64_t M, int64_t N,
+                               int64_t K, void* stream);
+
+// MLP-up with the quantise launch folded in: CQ | CS = drn_mx_quant_bf16(what DRN_EPI_GELU writes), bit for bit (drn.h)
+extern "C" int drn_gemm_mxfp8_gelu_mx(const void* A, const void* SA, const void* W, const void* SW, void* CQ, void* CS, int64_t M,
+                                      int64_t N, int64_t K, int64_t rows_per_batch, void* stream) {
+    DRN_CHECK_ARG(A && SA && W && SW && CQ && CS && M >= 1 && N >= 256 && N % 256 == 0 && K >= MXT_K && K % MXT_K == 0);
+    DRN_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)SA & 3) == 0 && ((uintptr_t)SW & 3) == 0);
+    DRN_CHECK_ARG(((uintptr_t)CQ & 3) == 0);
+    const int64_t rpb = (rows_per_batch > 0 && rows_per_batch <= M) ? rows_per_batch : M;
+    const int64_t Mb = (rpb < M && M % rpb == 0) ? rpb : M;
+    const int splits = drn_gemm_mxfp8_splitk_choice(Mb, N, K);
+    if (splits == 0) return drn_gemm_mx_gelu_mx_launch(A, SA, W, SW, CQ, CS, M, N, K, stream);
+    DRN_CHECK_ARG(splits == 1 && shape_ok(M, N, K, rpb, 1));          // sliced K: the GELU lives in the reduce launch, no MX form
+    const mx_args a = {A, SA, W, SW, CQ, M, N, K, N, nullptr, nullptr, 0, rpb, 1, (hipStream_t)stream, CS};
+    return launch<EPI_GELU_MX>(a);
 }

@@ -110,6 +110,10 @@ class HipDiT:
         # DRN_PER_LAUNCH=1: one ctypes call per kernel (the path the sharded engine and the traces use) instead of the
         # drn_dit_forward sequencer - same kernels, same bits (tests compare the two)
         self._per_launch = os.environ.get("DRN_PER_LAUNCH", "0") == "1"
+        # mxfp8: the producers (LayerNorm + modulate, attention, the GELU epilogue of MLP-up) write the quantised operand of the
+        # next block linear themselves - no quantise launch, the same bits (drn.h).  DRN_MX_FUSED=0: a quantise launch in front of
+        # every block linear (the A/B switch).  Sharded engines cannot be mxfp8; trace mode keeps the bf16 intermediates.
+        self._mx_fused = self._mx and os.environ.get("DRN_MX_FUSED", "1") != "0"
         # DRN_SP_SPLIT_RETURN=0: the return all-to-all as ONE collective after the whole attention (A/B runs)
         self._split_return = os.environ.get("DRN_SP_SPLIT_RETURN", "1") != "0"
 
@@ -289,6 +293,10 @@ class HipDiT:
                     kmax = max(D, ws["u"].shape[1])
                     ws["act"] = torch.empty(lib.drn_dit_forward_mx_act_bytes(B, S, D, ws["u"].shape[1]), dtype=torch.uint8, device=dev)
                     ws["act_q_bytes"] = n * kmax
+                    if self._mx_fused:
+                        # UQ | US: U as MXFP8 (MLP-up writes it while it reads AQ | AS)
+                        ws["uact"] = torch.empty(lib.drn_dit_forward_mx_u_bytes(B, S, ws["u"].shape[1]), dtype=torch.uint8, device=dev)
+                        ws["uact_q_bytes"] = n * ws["u"].shape[1]
                 ws["gemm_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-K partials (few tokens)
                 nb = lib.drn_dit_forward_attn_workspace_bytes(B, self.heads, S)
                 ws["attn_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-KV partials
@@ -408,12 +416,22 @@ class HipDiT:
         g.replay()
         return out.clone()                                       # the graph's output buffer is reused by the next replay
 
+    @staticmethod
+    def _mx_view(buf, q_bytes, rows, K):
+        """An MxTensor [rows, K] over a byte buffer laid out as drn_dit_forward is given AQ | AS / UQ | US: elements from the
+        start, scales from byte `q_bytes` (the offset the sequencer path passes as AS / US)."""
+        return N.MxTensor(buf[:rows * K].view(torch.float8_e4m3fn).view(rows, K),
+                          buf[q_bytes:q_bytes + rows * (K // 32)].view(rows, K // 32))
+
     def _lin(self, a, w, out, epilogue=N.EPI_NONE, gate=None, residual=None, rows_per_batch=None):
         """A block linear (q|k|v, out-proj, MLP-up, MLP-down): the bf16 GEMM, or with precision 'mxfp8' the quantisation of
         `a` followed by the MXFP8 GEMM against the weights quantised at load (native.gemm_mxfp8 picks the few-token kernel and its
         K slices from one clip's rows, as drn_dit_forward does)."""
         if not self._mx:
             return N.gemm(a, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch)
+        if isinstance(a, N.MxTensor):                            # a fused producer wrote the operand as MX already
+            return N.gemm_mxfp8(a, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch,
+                                splitk=None)
         key = tuple(a.shape)
         aq = N.mx_quant(a, out=self._mx_act.get(key))
         self._mx_act[key] = aq
@@ -542,6 +560,10 @@ class HipDiT:
                 a.precision = 1
                 a.AQ, a.AS = ws["act"].data_ptr(), ws["act"].data_ptr() + ws["act_q_bytes"]
                 a.act_bytes = ws["act"].numel()
+                if self._mx_fused:
+                    a.mx_fused = 1
+                    a.UQ, a.US = ws["uact"].data_ptr(), ws["uact"].data_ptr() + ws["uact_q_bytes"]
+                    a.u_act_bytes = ws["uact"].numel()
             N.dit_forward(a)
             return N.unpatchify(Y, B, self.out_ch, Tp, Hp, Wp, self.pt, self.ps)
         sharded = self.exchange != "none"
@@ -569,21 +591,31 @@ class HipDiT:
                         N.bcast_add(X, pending, rows_per_batch=rows)
                     pending = addvec[sb["idx"]]
                     continue
-                N.ln_modulate(X, shift, scale, out=Hb, add_vec=pending, rows_per_batch=rows)
+                # mxfp8 with fused producers (the launches of drn_dit_forward with mx_fused, in its order): h, O and U leave
+                # their producers as MXFP8; a site without a fused producer keeps bf16 + the quantise launch inside _lin
+                fusedmx = self._mx_fused and self.trace is None and not sharded
+                if fusedmx:
+                    hin = N.ln_modulate(X, shift, scale, add_vec=pending, rows_per_batch=rows,
+                                        out_mx=self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D))
+                else:
+                    hin = N.ln_modulate(X, shift, scale, out=Hb, add_vec=pending, rows_per_batch=rows)
                 pending = None
                 if sb["kind"] == "fa":
                     if self.exchange == "none":
                         QKV = ws["qkv"]
-                        self._lin(Hb, sb["wqkv"], QKV, rows_per_batch=rows)
+                        self._lin(hin, sb["wqkv"], QKV, rows_per_batch=rows)
                         q, k, v = QKV[:, :D], QKV[:, D:2 * D], QKV[:, 2 * D:]
                         N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
+                        omx = self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D) if fusedmx and N.attention_mx_available() else None
                         if B == 1:
-                            N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=O.unsqueeze(0), heads=self.heads)
+                            oin = N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=None if omx else O.unsqueeze(0),
+                                              heads=self.heads, out_mx=omx)
                         else:
                             Q3 = QKV.view(B, S, 3 * D)
-                            N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:], out=O.view(B, S, D), heads=self.heads)
-                        self._lin(O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
-                                  rows_per_batch=rows)
+                            oin = N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:], out=None if omx else O.view(B, S, D),
+                                              heads=self.heads, out_mx=omx)
+                        self._lin(oin if omx else O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate,
+                                  residual=X, rows_per_batch=rows)
                     else:
                         # sharded: the exchanges (and the projections that write / read their slabs) run clip by clip on this
                         # rank's band of each clip; every clip of a batch has the same sigma, hence the same gate row
@@ -595,8 +627,13 @@ class HipDiT:
                             band = slice(b * rows, (b + 1) * rows)
                             self._fa_sharded(sb, Hb[band], X[band], O[band], ws, plan, cos, sin, gate, fused)
                 else:
-                    self._lin(Hb, sb["w1"], U, epilogue=N.EPI_GELU, rows_per_batch=rows)
-                    self._lin(U, sb["w2"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
+                    uin = U
+                    if fusedmx and N.mx_gemm_plan(X.shape[0], U.shape[1], D, rows) <= 1:
+                        uin = N.gemm_mxfp8(hin, sb["w1"], epilogue=N.EPI_GELU, rows_per_batch=rows,
+                                           out_mx=self._mx_view(ws["uact"], ws["uact_q_bytes"], X.shape[0], U.shape[1]))
+                    else:
+                        self._lin(hin, sb["w1"], U, epilogue=N.EPI_GELU, rows_per_batch=rows)
+                    self._lin(uin, sb["w2"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
                               rows_per_batch=rows)
 
         if self.trace is not None:

@@ -37,7 +37,8 @@ class DitForwardArgs(Structure):              # drn_dit_forward_args (include/dr
                 ("X", c_void_p), ("H", c_void_p), ("QKV", c_void_p), ("O", c_void_p), ("U", c_void_p), ("Y", c_void_p),
                 ("gemm_ws", c_void_p), ("gemm_ws_bytes", c_int64), ("attn_ws", c_void_p), ("attn_ws_bytes", c_int64),
                 ("timer", c_void_p), ("eps", c_float), ("precision", c_int32),
-                ("AQ", c_void_p), ("AS", c_void_p), ("act_bytes", c_int64)]
+                ("AQ", c_void_p), ("AS", c_void_p), ("act_bytes", c_int64),
+                ("mx_fused", c_int32), ("reserved", c_int32), ("UQ", c_void_p), ("US", c_void_p), ("u_act_bytes", c_int64)]
 
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); must match include/drn.h one-to-one
@@ -50,6 +51,7 @@ SIGNATURES = {
     "drn_dit_forward_attn_workspace_bytes": [_L, _I, _L],
     "drn_dit_forward_mx_act_bytes": [_L, _L, _L, _L],
     "drn_dit_forward_mx_gemm_workspace_bytes": [_L, _L, _L, _L],
+    "drn_dit_forward_mx_u_bytes": [_L, _L, _L],
     "drn_timer_create": [_I, _I],
     "drn_timer_destroy": [_P],
     "drn_timer_count": [_P],
@@ -70,6 +72,13 @@ SIGNATURES = {
     "drn_gemm_force_res_prefetch": [_I],
     "drn_gemm_tall_force_shape": [_I],
     "drn_mx_quant_bf16": [_P, _L, _L, _L, _P, _P, _P],
+    "drn_mx_quant_calls": [_I],
+    "drn_gemm_mxfp8_gelu_mx": [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _P],
+    "drn_ln_modulate_mx": [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _F, _P],
+    "drn_splitk_gate_res_ln_modulate_mx": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _F, _P],
+    "drn_attention_bf16_mx": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _P],
+    "drn_attention_splitkv_bf16_mx": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _I, _P, _P],
+    "drn_attention_mx_available": [],
     "drn_gemm_mxfp8": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _P],
     "drn_gemm_mxfp8_splitk_choice": [_L, _L, _L],
     "drn_gemm_mxfp8_splitk": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _I, _P, _P],
@@ -97,6 +106,7 @@ SIGNATURES = {
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
              "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_mx_act_bytes": c_int64,
+             "drn_dit_forward_mx_u_bytes": c_int64, "drn_mx_quant_calls": c_int64,
              "drn_dit_forward_mx_gemm_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
              "drn_ln_force_kernel": None, "drn_attention_force_shape16": None}
 
@@ -342,6 +352,33 @@ def mx_quant(x, out=None):
     return out
 
 
+def mx_empty(M, K, device) -> MxTensor:
+    """An uninitialised MxTensor [M, K] (K % 32 == 0): the `out_mx` of a fused producer."""
+    if K % 32:
+        raise ValueError(f"MXFP8 needs K % 32 == 0 (K = {K})")
+    return MxTensor(torch.empty((M, K), dtype=torch.float8_e4m3fn, device=device),
+                    torch.empty((M, K // 32), dtype=torch.uint8, device=device))
+
+
+def _mx_out(out_mx, M, K, device) -> MxTensor:
+    """out_mx=True -> a fresh MxTensor; an MxTensor -> checked and reused."""
+    if out_mx is True:
+        return mx_empty(M, K, device)
+    assert isinstance(out_mx, MxTensor) and out_mx.q.shape == (M, K) and out_mx.q.is_contiguous()
+    assert out_mx.scales.shape == (M, K // 32) and out_mx.scales.is_contiguous()
+    return out_mx
+
+
+def mx_quant_calls(reset=False) -> int:
+    """Launches drn_mx_quant_bf16 has enqueued in this process so far (reset=True zeroes the counter after reading)."""
+    return int(load_library().drn_mx_quant_calls(1 if reset else 0))
+
+
+def attention_mx_available() -> bool:
+    """True when attention(..., out_mx=) has a kernel: the 16x16x32 body is selected (drn.h)."""
+    return bool(load_library().drn_attention_mx_available())
+
+
 def mx_gemm_plan(M, N, K, rows_per_batch=None) -> int:
     """How gemm_mxfp8 runs an [M, N, K] product: 0 = drn_gemm_mxfp8 (256 x 256 tiles), s >= 1 = the few-token kernel with s K
     slices (1 = unsplit, fused epilogue).  Decided by drn_gemm_mxfp8_splitk_choice from ONE clip's rows: clips stacked along the
@@ -351,10 +388,13 @@ def mx_gemm_plan(M, N, K, rows_per_batch=None) -> int:
     return int(load_library().drn_gemm_mxfp8_splitk_choice(Mb, N, K))
 
 
-def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None, splitk=None):
+def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None, splitk=None, out_mx=None):
     """out[M, N] = epi(dequant(a) @ dequant(w)^T) for MxTensors a [M, K], w [N, K].  N % 256 == 0, K % 128 == 0.
     splitk: None = mx_gemm_plan decides (drn_gemm_mxfp8, or the few-token kernel drn_gemm_mxfp8_splitk with its K slices);
-    0 = drn_gemm_mxfp8; k >= 1 = the few-token kernel with k slices."""
+    0 = drn_gemm_mxfp8; k >= 1 = the few-token kernel with k slices.
+    out_mx (True or an MxTensor [M, N]; epilogue EPI_GELU, splitk None): the result leaves as MXFP8 - the bytes of
+    mx_quant(out) - and that MxTensor is returned; no bf16 output is written (drn_gemm_mxfp8_gelu_mx).  Raises where the plan
+    slices K (mx_gemm_plan > 1): there the GELU lives in the reduce launch."""
     _bf16(out, gate, residual)
     M, K = a.shape
     N = w.shape[0]
@@ -362,6 +402,19 @@ def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows
         raise ValueError(f"MXFP8 GEMM: K of a ({K}) and w ({w.shape[1]}) differ")
     if N % 256 or K % 128:
         raise ValueError(f"MXFP8 GEMM needs N % 256 == 0 and K % 128 == 0 (N = {N}, K = {K})")
+    if out_mx is not None:
+        if epilogue != EPI_GELU or splitk is not None or out is not None:
+            raise ValueError("gemm_mxfp8(out_mx=) is the GELU epilogue under the automatic plan, without a bf16 output")
+        if mx_gemm_plan(M, N, K, rows_per_batch) > 1:
+            raise ValueError(f"gemm_mxfp8(out_mx=): the plan slices K at M={M} N={N} K={K} (no MX epilogue in the reduce launch)")
+        out_mx = _mx_out(out_mx, M, N, a.q.device)
+        t0 = _TIMER.begin("gemm") if _TIMER is not None else None
+        _check(load_library().drn_gemm_mxfp8_gelu_mx(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out_mx.q),
+                                                     _ptr(out_mx.scales), M, N, K, rows_per_batch if rows_per_batch else max(M, 1),
+                                                     _stream()), "drn_gemm_mxfp8_gelu_mx")
+        if t0 is not None:
+            _TIMER.end("gemm", t0, 2.0 * M * N * K, 1.03 * (M * K + N * K + M * N))
+        return out_mx
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.q.device)
     assert out.shape == (M, N) and out.stride(1) == 1
@@ -416,11 +469,20 @@ def gemv(x, w, out=None, add=None, mul=None, act=ACT_NONE):
     return out
 
 
-def ln_modulate(x, shift, scale, out=None, add_vec=None, rows_per_batch=None, eps=1e-6):
-    """out = bf16(bf16(LN(x) * bf16(1+scale)) + shift); if add_vec: x <- bf16(x + add_vec) in place first."""
+def ln_modulate(x, shift, scale, out=None, add_vec=None, rows_per_batch=None, eps=1e-6, out_mx=None):
+    """out = bf16(bf16(LN(x) * bf16(1+scale)) + shift); if add_vec: x <- bf16(x + add_vec) in place first.
+    out_mx (True or an MxTensor [rows, D]): the result leaves as MXFP8 - the bytes of mx_quant(out) - and that MxTensor is
+    returned; the bf16 `out` is written as well only when given (drn_ln_modulate_mx)."""
     _bf16(x, shift, scale, out, add_vec)
     rows, D = x.shape
     assert x.is_contiguous()
+    if out_mx is not None:
+        out_mx = _mx_out(out_mx, rows, D, x.device)
+        assert out is None or (out.shape == x.shape and out.is_contiguous())
+        _check(load_library().drn_ln_modulate_mx(_ptr(x), _ptr(add_vec), _ptr(shift), _ptr(scale), _ptr(out), _ptr(out_mx.q),
+                                                 _ptr(out_mx.scales), rows, D, rows_per_batch if rows_per_batch else max(rows, 1),
+                                                 eps, _stream()), "drn_ln_modulate_mx")
+        return out_mx
     if out is None:
         out = torch.empty_like(x)
     _check(load_library().drn_ln_modulate(_ptr(x), _ptr(add_vec), _ptr(shift), _ptr(scale), _ptr(out), rows, D,
@@ -488,16 +550,28 @@ def attention_plan(batch, heads, Sq, Sk):
     return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
 
 
-def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None):
+def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None, out_mx=None):
     """q: [B, Sq, H*128], k/v: [B, Sk, H*128] (token-strided views allowed) -> out [B, Sq, H*128].
-    kv_splits: None = automatic (attention_plan), 1 = single pass, n > 1 = split-KV + combine."""
+    kv_splits: None = automatic (attention_plan), 1 = single pass, n > 1 = split-KV + combine.
+    out_mx (True or an MxTensor [B * Sq, H*128]): the output leaves as MXFP8 - the bytes of mx_quant(out.view(B * Sq, -1)) - and
+    that MxTensor is returned; the bf16 `out` (contiguous) is written as well only when given.  Needs attention_mx_available()."""
     _bf16(q, k, v, out)
     B, Sq, HD = q.shape
     Sk = k.shape[1]
     H = heads if heads else HD // 128
     assert HD == H * 128 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
-    if out is None:
-        out = torch.empty((B, Sq, HD), dtype=torch.bfloat16, device=q.device)
+    mx = None
+    if out_mx is not None:
+        if not attention_mx_available():
+            raise RuntimeError("attention(out_mx=): the 32x32x16 body is selected and has no MX epilogue (drn.h)")
+        mx = _mx_out(out_mx, B * Sq, HD, q.device)
+        assert out is None or (out.shape == (B, Sq, HD) and out.is_contiguous())
+        oq, osc = mx.q.view(B, Sq, HD), mx.scales.view(B, Sq, HD // 32)
+        ldo, bso = HD, Sq * HD                 # the MX rows are contiguous; o (optional) must share that geometry
+    else:
+        if out is None:
+            out = torch.empty((B, Sq, HD), dtype=torch.bfloat16, device=q.device)
+        ldo, bso = out.stride(1), out.stride(0)
     if scale is None:
         scale = 1.0 / (128 ** 0.5)
     # the plan of ONE clip, applied to every clip of the batch: a split of the keys changes the summation order, so it must not
@@ -506,7 +580,11 @@ def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None):
     t0 = _TIMER.begin("attention") if _TIMER is not None else None
     lib = load_library()
     for q0, q1, ns in plan:
-        qs, os_, n = q[:, q0:q1], out[:, q0:q1], q1 - q0
+        qs, n = q[:, q0:q1], q1 - q0
+        o_ = _ptr(out[:, q0:q1]) if out is not None else None
+        # (o [, oq, os]): the _mx entries take the two MX pointers behind o, everything else is the same call
+        outs = (o_,) if mx is None else (o_, _ptr(oq[:, q0:q1]), _ptr(osc[:, q0:q1]))
+        geom = (B, H, n, Sk, q.stride(1), k.stride(1), v.stride(1), ldo, q.stride(0), k.stride(0), v.stride(0), bso, scale)
         if ns > 1:
             nbytes = lib.drn_attention_splitkv_workspace_bytes(B, H, n, ns)
             key = (q.device, nbytes)
@@ -515,18 +593,16 @@ def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None):
                 _SPLIT_WS.clear()
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
                 _SPLIT_WS[key] = ws
-            _check(lib.drn_attention_splitkv_bf16(_ptr(qs), _ptr(k), _ptr(v), _ptr(os_), B, H, n, Sk,
-                                                  q.stride(1), k.stride(1), v.stride(1), out.stride(1),
-                                                  q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale, ns,
-                                                  ws.data_ptr(), _stream()), "drn_attention_splitkv_bf16")
+            fn, name = ((lib.drn_attention_splitkv_bf16, "drn_attention_splitkv_bf16") if mx is None else
+                        (lib.drn_attention_splitkv_bf16_mx, "drn_attention_splitkv_bf16_mx"))
+            _check(fn(_ptr(qs), _ptr(k), _ptr(v), *outs, *geom, ns, ws.data_ptr(), _stream()), name)
         else:
-            _check(lib.drn_attention_bf16(_ptr(qs), _ptr(k), _ptr(v), _ptr(os_), B, H, n, Sk,
-                                          q.stride(1), k.stride(1), v.stride(1), out.stride(1),
-                                          q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale, _stream()),
-                   "drn_attention_bf16")
+            fn, name = ((lib.drn_attention_bf16, "drn_attention_bf16") if mx is None else
+                        (lib.drn_attention_bf16_mx, "drn_attention_bf16_mx"))
+            _check(fn(_ptr(qs), _ptr(k), _ptr(v), *outs, *geom, _stream()), name)
     if t0 is not None:
         _TIMER.end("attention", t0, 4.0 * B * H * Sq * Sk * 128, 2.0 * B * H * 128 * (2 * Sq + 2 * Sk))
-    return out
+    return out if mx is None else mx
 
 
 def patchify_concat(x, cond, with_mask, pt, ps, ldo):

@@ -113,6 +113,23 @@ int drn_gemm_tall_force_shape(int shape);
 /* X [M, K] bf16 with row stride ldx -> Q [M, K] e4m3 + scales [M, K / 32].  K % 32 == 0, ldx % 8 == 0, X 16-byte and Q 8-byte
  * aligned, M * K / 8 < 2^31. */
 int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q, void* scales, void* stream);
+/* host-side count of the launches drn_mx_quant_bf16 has enqueued in this process (reset != 0 zeroes it after reading): lets a
+ * test state "this forward issued no quantise launch" without a profiler.  A plain counter on the launch path (one host thread
+ * per process, as everywhere in this library).  It counts ENQUEUES, not executions: launches replayed from a captured graph
+ * (DRN_GRAPHS=1) are not counted, so the statement only holds for eager forwards. */
+int64_t drn_mx_quant_calls(int reset);
+/* ---- producers that write their result as MXFP8 themselves (the `_mx` entry points below and next to their bf16 twins).
+ * The one rule: a fused producer rounds its result to bf16 exactly where its twin rounds and applies the rule above to THAT bf16
+ * value, so (Q, scales) == drn_mx_quant_bf16(what the twin writes), bit for bit, and an MXFP8 forward with fused producers equals
+ * one with quantise launches.  Outputs are contiguous in the layouts above; the bf16 output pointer of an `_mx` entry may be NULL
+ * (not written).  Every `_mx` entry validates on the host and returns DRN_EINVAL before anything is launched. */
+/* MLP-up: CQ | CS [M, N] = MX(bf16(gelu_erf(bf16(dequant(A) . dequant(W)^T)))), dispatched by drn_gemm_mxfp8_splitk_choice on one
+ * clip's rows (rows_per_batch, or M) like drn_gemm_mxfp8 / drn_gemm_mxfp8_splitk(splits = 1): choice 0 = the 256 x 256 kernel
+ * (any M, ragged rows masked on store), 1 = the few-token kernel (either tile shape).  A choice > 1 (sliced K: the GELU then
+ * lives in the reduce launch, which has no MX form) returns DRN_EINVAL: callers keep bf16 + drn_mx_quant_bf16 for that shape.
+ * N % 256 == 0, K % 128 == 0, A / W 16-byte, scales and CQ 4-byte aligned. */
+int drn_gemm_mxfp8_gelu_mx(const void* A, const void* SA, const void* W, const void* SW, void* CQ, void* CS, int64_t M, int64_t N,
+                           int64_t K, int64_t rows_per_batch, void* stream);
 /* C[M, N] = epi(dequant(A) . dequant(W)^T) on v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulate, bf16 out; the epilogues of
  * drn_gemm_bf16 with the same rounding points (gate [batches, N] bf16, row r uses batch r / rows_per_batch; residual [M, ldr]
  * bf16, may alias C).  A / SA, W / SW in the layouts above.  Any M >= 1; N % 256 == 0 and K % 128 == 0 (DRN_EINVAL
@@ -169,6 +186,10 @@ int drn_gemv_bf16(const void* x, const void* W, void* y, int64_t N, int64_t K,
  * x,h: [rows, D] bf16; shift/scale/add_vec: [batches, D] bf16; batch = row / rows_per_batch. D % 8 == 0, D <= 8192. */
 int drn_ln_modulate(void* x, const void* add_vec, const void* shift, const void* scale, void* h,
                     int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream);
+/* the same with h written as MXFP8: hq [rows, D] e4m3 + hs [rows, D / 32] scales (h: bf16 as above, or NULL).  D % 32 == 0 on top
+ * of the contract above, hq 8-byte aligned.  drn_ln_force_kernel selects the form as for drn_ln_modulate (same bits). */
+int drn_ln_modulate_mx(void* x, const void* add_vec, const void* shift, const void* scale, void* h, void* hq, void* hs,
+                       int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream);
 /* ---- the sum of split-K partials, the gated residual (CleanGeneralDIT.py:517) and the NEXT sub-block's LayerNorm + modulate
  * (:481, :506) in one pass over [rows, D] (few-token shapes: drn_dit_forward uses it where a linear was split along K):
  *   x <- bf16(x + bf16(gate * bf16(sum_s partials[s]))) [; x <- bf16(x + add_vec)];  h = modulate(LN(x)).
@@ -177,6 +198,10 @@ int drn_ln_modulate(void* x, const void* add_vec, const void* shift, const void*
 int drn_splitk_gate_res_ln_modulate(const void* partials, int splits, void* x, const void* gate, const void* add_vec,
                                     const void* shift, const void* scale, void* h, int64_t rows, int64_t D,
                                     int64_t rows_per_batch, float eps, void* stream);
+/* the same with h as MXFP8 (hq, hs as drn_ln_modulate_mx; h may be NULL); D % 32 == 0. */
+int drn_splitk_gate_res_ln_modulate_mx(const void* partials, int splits, void* x, const void* gate, const void* add_vec,
+                                       const void* shift, const void* scale, void* h, void* hq, void* hs, int64_t rows, int64_t D,
+                                       int64_t rows_per_batch, float eps, void* stream);
 /* tuning hook (tests / A-B runs; no reference counterpart): the row statistics come from ONE summation tree that a
  * one-wave-per-row and a four-waves-per-row kernel share (same bits); -1 = chosen by row count, 0 / 1 force either. */
 void drn_ln_force_kernel(int which);
@@ -226,6 +251,24 @@ int drn_attention_splitkv_bf16(const void* q, const void* k, const void* v, void
                                int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
                                float scale, int nsplit, void* workspace, void* stream);
 int64_t drn_attention_splitkv_workspace_bytes(int batch, int heads, int64_t Sq, int nsplit);
+
+/* ---- both attentions with the output written as MXFP8: oq [rows, heads * 128] e4m3 + os [rows, heads * 4] scales, contiguous,
+ * where row = b * (bso / ldo) + query (so ldo == heads * 128 and bso % ldo == 0 are required even when o is NULL; a launch over a
+ * query sub-range of a plan passes o, oq and os advanced by its first row).  o: bf16 as above, or NULL.  oq 8-byte, os 4-byte
+ * aligned.  Only the 16x16x32 body has the epilogue (unsplit: in the kernel; split keys: in the combine pass): with the 32x32x16
+ * body selected (DRN_ATT16=0 / drn_attention_force_shape16(0)) these return DRN_EINVAL and drn_attention_mx_available() is 0 -
+ * callers then keep the bf16 output and drn_mx_quant_bf16 (the same bytes). */
+int drn_attention_bf16_mx(const void* q, const void* k, const void* v, void* o, void* oq, void* os,
+                          int batch, int heads, int64_t Sq, int64_t Sk,
+                          int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                          int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
+                          float scale, void* stream);
+int drn_attention_splitkv_bf16_mx(const void* q, const void* k, const void* v, void* o, void* oq, void* os,
+                                  int batch, int heads, int64_t Sq, int64_t Sk,
+                                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                  int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
+                                  float scale, int nsplit, void* workspace, void* stream);
+int drn_attention_mx_available(void);
 
 /* ---- how drn_dit_forward / the host wrapper cover the (q-block, head) grid of ONE clip with whole rounds of the 256 CUs:
  * plan[3 i + {0,1,2}] = (q_begin, q_end, kv_splits) for launch i; returns the number of launches (1 or 2).  The q-blocks that
@@ -277,6 +320,11 @@ typedef struct drn_dit_forward_args {
     void* AQ; void* AS; int64_t act_bytes;  /* precision 1: the quantised A operand of the next block linear, elements
                                            * [B S, max(D, hidden)] and scales [B S, max(D, hidden) / 32]; act_bytes = the bytes behind
                                            * both together (drn_dit_forward_mx_act_bytes) */
+    int32_t mx_fused;                     /* precision 1 only.  0: every block linear quantises its A operand by launch (above).
+                                           * 1: the producers write it as MX themselves - see below.  Anything else: DRN_EINVAL */
+    int32_t reserved;
+    void* UQ; void* US; int64_t u_act_bytes;  /* mx_fused 1: the MX form of U, elements [B S, hidden] and scales [B S, hidden / 32];
+                                           * u_act_bytes = the bytes behind both together (drn_dit_forward_mx_u_bytes) */
 } drn_dit_forward_args;
 int drn_dit_forward(const drn_dit_forward_args* args, void* stream);
 int64_t drn_dit_forward_args_bytes(void);     /* sizeof the two structs as this library was compiled (binding self-check) */
@@ -290,6 +338,18 @@ int64_t drn_dit_forward_attn_workspace_bytes(int64_t B, int heads, int64_t S);
  * LayerNorm pass exactly as the bf16 one does).  DRN_EINVAL before any launch when AQ / AS are NULL, act_bytes or gemm_ws_bytes
  * are short, a FA / MLP sub-block lacks weights or scales, or D / hidden are not multiples of 256. */
 int64_t drn_dit_forward_mx_act_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden);
+/* mx_fused == 1 (all-zero trailing fields = exactly the launches described above): no drn_mx_quant_bf16 launch where a producer
+ * can write MX itself.  The LayerNorm in front of a FA / MLP sub-block runs as drn_ln_modulate_mx /
+ * drn_splitk_gate_res_ln_modulate_mx into AQ | AS viewed as [B S, D] (H is not written; the final-layer LayerNorm and the scratch
+ * pass between two CA blocks stay bf16); q|k|v reads AQ | AS; attention writes O as MX into AQ | AS (drn_attention_*_mx; O is not
+ * written); out-proj reads it; MLP-up reads AQ | AS and writes U as MX into UQ | US (drn_gemm_mxfp8_gelu_mx; U is not written);
+ * MLP-down reads UQ | US.  A site without a fused producer - the 32x32x16 attention body selected, or an MLP-up whose
+ * drn_gemm_mxfp8_splitk_choice is > 1 - alone keeps its bf16 output and the quantise launch: the bytes are the same either way.
+ * (No site keeps its launch for a timing reason: every fused producer measured faster than producer + quantise launch at 256,
+ * 1024 and 18 432 rows per clip, DESIGN 4c.  Were one slower at a shape, the rule would be per site, from ONE clip's rows.)
+ * DRN_EINVAL before any launch when mx_fused is neither 0 nor 1, is 1 with precision 0, or UQ / US are NULL or u_act_bytes is
+ * below drn_dit_forward_mx_u_bytes (host-only sizer). */
+int64_t drn_dit_forward_mx_u_bytes(int64_t B, int64_t S, int64_t hidden);
 int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden);
 
 /* ---- per-launch timing inside drn_dit_forward (the roofline leg of bench.py; no reference counterpart): a pool of HIP event

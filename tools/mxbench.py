@@ -6,9 +6,13 @@ gemm:  the four block linears at M rows (default 18 432 = cfg 3): what native.ge
        --M 256 / --M 1024 (few tokens): also quantise + what native.gemm_mxfp8 picks (the few-token kernel of gemm_mx_tall.hip,
        its reduce launch included where it slices K) against quantise + drn_gemm_mxfp8 (the small-M path off); the weight copies
        are rotated over more than the 256 MB Infinity Cache.  --sweep adds both tile shapes at every power-of-two slice count.
+       Then, per producer that can write MXFP8 itself (LayerNorm + modulate -> q|k|v, attention -> out-proj, MLP-up's GELU ->
+       MLP-down): "producer + quantise launch + GEMM" against "fused producer + GEMM" (the same bits; drn.h).
 model: ms per step (DiT forward + Euler step) of the 28-block model at cfg 3 (57 x 576 x 1024, S = 18 432) and cfg 1 (256 x 256,
        S = 256) with precision bf16, mxfp8, and mxfp8 built under DRN_PER_LAUNCH=1 (one ctypes call per kernel; at cfg 1 also
-       with the small-M path off: the path of an mxfp8 engine before gemm_mx_tall.hip), synthetic weights."""
+       with the small-M path off: the path of an mxfp8 engine before gemm_mx_tall.hip), and mxfp8 built under DRN_MX_FUSED=0 (a
+       quantise launch in front of every block linear: the launches of an mxfp8 engine before the fused producers), synthetic
+       weights."""
 import argparse
 import os
 import sys
@@ -116,6 +120,82 @@ def bench_gemm(pkg, args):
         torch.cuda.empty_cache()
 
 
+def bench_producers(pkg, args):
+    """producer + drn_mx_quant_bf16 + consumer GEMM against fused producer + consumer GEMM, at M rows of the D = 4096 model."""
+    N = pkg.native
+    dev = torch.device("cuda")
+    M, D, Hd, heads = args.M, 4096, 16384, 32
+    g = torch.Generator(device="cpu").manual_seed(1)
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(torch.bfloat16).to(dev)
+
+    cold = max(args.cold, 3)
+    wq = {n: [N.mx_quant(rnd(nn, kk, scale=kk ** -0.5)) for _ in range(cold)]
+          for n, nn, kk in (("qkv", 3 * D, D), ("out", D, D), ("up", Hd, D), ("down", D, Hd))}
+    it = {"i": 0}
+
+    def nxt():
+        it["i"] = (it["i"] + 1) % cold
+        return it["i"]
+
+    x, shift, scale = rnd(M, D), rnd(1, D, scale=0.3), rnd(1, D, scale=0.3)
+    h, hmx = torch.empty_like(x), N.mx_empty(M, D, dev)
+    qkv = rnd(1, M, 3 * D)
+    q, k, v = qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:]
+    o, omx = torch.empty(1, M, D, dtype=torch.bfloat16, device=dev), N.mx_empty(M, D, dev)
+    u, umx = torch.empty(M, Hd, dtype=torch.bfloat16, device=dev), N.mx_empty(M, Hd, dev)
+    qkv_out = torch.empty(M, 3 * D, dtype=torch.bfloat16, device=dev)
+    gate, res = rnd(1, D, scale=0.5), rnd(M, D)
+    xo = torch.empty_like(res)                           # gated-residual output (not `res`: it would grow with every repetition)
+    aq = N.mx_quant(x)
+    up_fusable = N.mx_gemm_plan(M, Hd, D) <= 1
+
+    def ln_sep():
+        N.ln_modulate(x, shift, scale, out=h)
+        N.mx_quant(h, out=hmx)
+        N.gemm_mxfp8(hmx, wq["qkv"][nxt()], out=qkv_out)
+
+    def ln_fused():
+        N.ln_modulate(x, shift, scale, out_mx=hmx)
+        N.gemm_mxfp8(hmx, wq["qkv"][nxt()], out=qkv_out)
+
+    def at_sep():
+        N.attention(q, k, v, out=o, heads=heads)
+        N.mx_quant(o.view(M, D), out=omx)
+        N.gemm_mxfp8(omx, wq["out"][nxt()], out=xo, epilogue=N.EPI_GATE_RES, gate=gate, residual=res)
+
+    def at_fused():
+        N.attention(q, k, v, heads=heads, out_mx=omx)
+        N.gemm_mxfp8(omx, wq["out"][nxt()], out=xo, epilogue=N.EPI_GATE_RES, gate=gate, residual=res)
+
+    def up_sep():
+        N.gemm_mxfp8(aq, wq["up"][nxt()], out=u, epilogue=N.EPI_GELU)
+        N.mx_quant(u, out=umx)
+        N.gemm_mxfp8(umx, wq["down"][nxt()], out=xo, epilogue=N.EPI_GATE_RES, gate=gate, residual=res)
+
+    def up_fused():
+        N.gemm_mxfp8(aq, wq["up"][nxt()], epilogue=N.EPI_GELU, out_mx=umx)
+        N.gemm_mxfp8(umx, wq["down"][nxt()], out=xo, epilogue=N.EPI_GATE_RES, gate=gate, residual=res)
+
+    cases = [("LayerNorm -> q|k|v", ln_sep, ln_fused)]
+    if N.attention_mx_available():
+        cases.append(("attention -> out-proj", at_sep, at_fused))
+    if up_fusable:
+        cases.append(("MLP-up GELU -> MLP-down", up_sep, up_fused))
+    print(f"# producers, M = {M}: producer + quantise launch + GEMM | fused producer + GEMM, medians of {args.rounds} interleaved rounds")
+    for name, sep, fused in cases:
+        for f in (sep, fused):
+            timed(f, 3)
+        t = {"sep": [], "fused": []}
+        for _ in range(args.rounds):
+            t["sep"].append(timed(sep, args.reps))
+            t["fused"].append(timed(fused, args.reps))
+        ms, mf = sorted(t["sep"])[args.rounds // 2], sorted(t["fused"])[args.rounds // 2]
+        print(f"{name:24s}: {ms * 1e3:8.1f} us | {mf * 1e3:8.1f} us ({(mf - ms) * 1e3:+.1f} us, {mf / ms:.3f} x); "
+              f"spread {min(t['sep']) * 1e3:.1f}..{max(t['sep']) * 1e3:.1f} | {min(t['fused']) * 1e3:.1f}..{max(t['fused']) * 1e3:.1f}")
+
+
 def bench_model(pkg, args):
     N = pkg.native
     dev = torch.device("cuda")
@@ -128,6 +208,9 @@ def bench_model(pkg, args):
     os.environ["DRN_PER_LAUNCH"] = "1"                   # read at construction
     dits["mxfp8 per-launch"] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision="mxfp8")
     del os.environ["DRN_PER_LAUNCH"]
+    os.environ["DRN_MX_FUSED"] = "0"                     # read at construction: a quantise launch per block linear
+    dits["mxfp8 DRN_MX_FUSED=0"] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision="mxfp8")
+    del os.environ["DRN_MX_FUSED"]
     lib = N.load_library()
     del sd
     torch.cuda.empty_cache()
@@ -156,10 +239,10 @@ def bench_model(pkg, args):
             for p, f in runs.items():
                 t[p].append(timed(f, reps))
         med = {p: sorted(v)[len(v) // 2] for p, v in t.items()}
-        print(f"# model {cfg} (latent {F_}x{h}x{w}): bf16 {med['bf16']:.2f} ms/step | mxfp8 {med['mxfp8']:.2f} ms/step "
+        print(f"# model {cfg} (latent {F_}x{h}x{w}): bf16 {med['bf16']:.2f} ms/step | mxfp8 {med['mxfp8']:.3f} ms/step "
               f"({100 * (1 - med['mxfp8'] / med['bf16']):+.1f} % lower) | "
-              + " | ".join(f"{p} {v:.2f}" for p, v in med.items() if p not in ("bf16", "mxfp8"))
-              + " | spread (min..max) " + ", ".join(f"{p} {min(v):.2f}..{max(v):.2f}" for p, v in t.items()))
+              + " | ".join(f"{p} {v:.3f}" for p, v in med.items() if p not in ("bf16", "mxfp8"))
+              + " | spread (min..max) " + ", ".join(f"{p} {min(v):.3f}..{max(v):.3f}" for p, v in t.items()))
 
 
 def main():
@@ -177,6 +260,7 @@ def main():
     print(f"# device {torch.cuda.get_device_name()}")
     if "gemm" in args.what:
         bench_gemm(pkg, args)
+        bench_producers(pkg, args)
     if "model" in args.what:
         bench_model(pkg, args)
 
