@@ -11,24 +11,12 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from dit_refs import ATTN_REL_L2, _attn_check, _attn_ref, ulp_diff_ok          # comparators shared with the edge-geometry tests
 from oracle import dit_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-
-
-def ulp_diff_ok(out, ref, max_ulp=1, frac_exact=0.98, atol_rel=2e-3, mag=None):
-    """out, ref bf16: |out-ref| <= max_ulp bf16 ulps + atol_rel * rms(ref) (cancellation near zero), most exactly equal.
-    `mag`: magnitude of the terms the result was summed from (a residual add cancels: the ulp that matters is the terms')."""
-    o, r = out.float(), ref.float()
-    ulp = torch.maximum(r.abs(), o.abs()) * 2.0 ** -7
-    if mag is not None:
-        ulp = torch.maximum(ulp, mag.float() * 2.0 ** -7)
-    atol = atol_rel * r.pow(2).mean().sqrt()
-    bad = ((o - r).abs() > max_ulp * ulp + atol).sum().item()
-    exact = (out == ref).float().mean().item()
-    return bad == 0 and exact >= frac_exact, f"bad={bad} exact={exact:.5f}"
 
 
 @pytest.fixture(params=["32x32x16", "16x16x32"])
@@ -244,42 +232,6 @@ def test_qk_norm_rope_matches_oracle(pkg, gpu, heads, T, H, W):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def _attn_ref(q, k, v, heads):
-    B, Sq, HD = q.shape
-    qh = q.float().view(B, Sq, heads, 128).transpose(1, 2)
-    kh = k.float().view(B, -1, heads, 128).transpose(1, 2)
-    vh = v.float().view(B, -1, heads, 128).transpose(1, 2)
-    s = qh @ kh.transpose(-1, -2) / math.sqrt(128)
-    p = torch.softmax(s, -1)
-    o = p @ vh
-    _attn_ref.mag = ((p * p) @ (vh * vh)).sqrt().transpose(1, 2).reshape(B, Sq, HD)    # |terms| the output was summed from
-    return o.transpose(1, 2).reshape(B, Sq, HD)
-
-
-# Measured on MI355X (round 2, printed by every test below): rel-L2 against the fp32 answer 2.4e-3 .. 2.9e-3 - bf16 output
-# rounding alone is 1.7e-3 (uniform relative error of 2^-9 / sqrt 3 ... 2^-8 / sqrt 3), the rest is P rounded to bf16 for the PV
-# MFMA (the reference's SDPA does the same); against the fp32 answer ROUNDED to bf16: <= 2 bf16 ulp everywhere.
-ATTN_REL_L2 = 3.6e-3          # 1.25 x the largest measured value
-
-
-def _attn_check(out, ref, tag, rel=ATTN_REL_L2, max_ulp=2, frac_exact=0.5):
-    """out bf16 vs fp32 reference (call right after _attn_ref): rel-L2, and distance to the reference rounded to bf16 in bf16
-    ulps of max(|o|, sqrt(sum_k p_k^2 v_k^2)) - the output is a sum of terms p_k v_k with P rounded to bf16 for the PV product
-    (as in the reference's SDPA), so where the terms cancel the rounding error scales with the terms, not with the sum."""
-    e = rel_l2(out, ref)
-    r16 = ref.to(BF)
-    mag = _attn_ref.mag.to(out.device)
-    o, r = out.float(), r16.float()
-    ulp = torch.maximum(torch.maximum(r.abs(), o.abs()), mag) * 2.0 ** -7
-    worst = (o - r).abs() / ulp.clamp_min(1e-30)
-    exact = (out == r16).float().mean().item()
-    print(f"attention {tag}: rel-L2 {e:.3e}  max|diff| {(o - ref.float()).abs().max().item():.3e}  worst {worst.max().item():.2f} ulp  "
-          f"exact {exact:.4f}")
-    assert e < rel, (tag, e)
-    ok, msg = ulp_diff_ok(out, r16, max_ulp=max_ulp, frac_exact=frac_exact, atol_rel=0.0, mag=mag)
-    assert ok, (tag, msg)
-
-
 @pytest.mark.parametrize("heads,Sq,Sk", [(2, 256, 256), (2, 128, 128), (4, 300, 300), (1, 513, 77), (32, 256, 1024), (2, 512, 4160)])
 def test_attention_matches_fp32(pkg, gpu, heads, Sq, Sk, att_body):
     q = rnd((1, Sq, heads * 128), gpu, seed=29)
