@@ -606,6 +606,20 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __r
     }
 }
 
+// the combine pass of a split-KV launch (oq != NULL: the MX epilogue); attention_mx.hip's split-KV form writes the same partials
+// and ends in this launch too
+void drn_attention_combine_launch(const float* opart, const float* mlpart, void* o, int nsplit, int batch, int heads, int64_t Sq,
+                                  int64_t ldo, int64_t bso, float scale_log2e, void* oq, void* os, int64_t mx_bs, hipStream_t st) {
+    const int64_t items = (int64_t)batch * Sq * heads;
+    const dim3 grid((unsigned)((items + 3) / 4));
+    if (oq)
+        attention_combine_kernel<true><<<grid, dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch, heads, Sq, ldo, bso,
+                                                                   scale_log2e, (uint8_t*)oq, (uint8_t*)os, mx_bs);
+    else
+        attention_combine_kernel<false><<<grid, dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch, heads, Sq, ldo, bso,
+                                                                    scale_log2e, nullptr, nullptr, 0);
+}
+
 // attention16.hip: the same kernel on v_mfma_f32_16x16x32_bf16 (same grid, same arguments)
 void drn_attention16_launch(const void* q, const void* k, const void* v, void* o, int heads, int64_t Sq, int64_t Sk, int64_t ldq,
                             int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
@@ -672,16 +686,7 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
     attention_fwd_kernel<<<dim3((unsigned)total, 1, 1), dim3(512), 0, st>>>(
         (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk,
         bsv, bso, scale_log2e, (int)nqb, (int)total, nsplit, kv_chunk, opart, mlpart);
-    if (nsplit > 1) {
-        const int64_t items = (int64_t)batch * Sq * heads;
-        const dim3 grid((unsigned)((items + 3) / 4));
-        if (oq)
-            attention_combine_kernel<true><<<grid, dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch, heads, Sq, ldo, bso,
-                                                                       scale_log2e, (uint8_t*)oq, (uint8_t*)os, mx_bs);
-        else
-            attention_combine_kernel<false><<<grid, dim3(256), 0, st>>>(opart, mlpart, (bf16_t*)o, nsplit, batch, heads, Sq, ldo, bso,
-                                                                        scale_log2e, nullptr, nullptr, 0);
-    }
+    if (nsplit > 1) drn_attention_combine_launch(opart, mlpart, o, nsplit, batch, heads, Sq, ldo, bso, scale_log2e, oq, os, mx_bs, st);
     return drn_launch_status();
 }
 

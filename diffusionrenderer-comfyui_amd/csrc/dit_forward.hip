@@ -248,6 +248,32 @@ extern "C" int64_t drn_dit_forward_mx_u_bytes(int64_t B, int64_t S, int64_t hidd
     return B * S * hidden + B * S * (hidden / 32);
 }
 
+// the MXFP8 attention scratch: QQ | KQ | VT | QS | KS | VS, each rounded up to 256 bytes (drn.h)
+namespace {
+struct MxAttnLayout {
+    int64_t qq, kq, vt, qs, ks, vs, total, Sp;
+};
+int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
+MxAttnLayout mx_attn_layout(int64_t B, int64_t S, int64_t D) {
+    MxAttnLayout l;
+    l.Sp = (S + 127) / 128 * 128;
+    int64_t o = 0;
+    l.qq = o; o += up256(B * S * D);
+    l.kq = o; o += up256(B * S * D);
+    l.vt = o; o += up256(B * D * l.Sp);
+    l.qs = o; o += up256(B * S * (D / 32));
+    l.ks = o; o += up256(B * S * (D / 32));
+    l.vs = o; o += up256(B * D * (l.Sp / 32));
+    l.total = o;
+    return l;
+}
+}  // namespace
+
+extern "C" int64_t drn_dit_forward_mx_attn_bytes(int64_t B, int64_t S, int64_t D) {
+    if (B <= 0 || S <= 0 || D <= 0 || D % 128) return 0;
+    return mx_attn_layout(B, S, D).total;
+}
+
 extern "C" int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden) {
     const int64_t M = B * S;
     const int64_t shapes[4][2] = {{3 * D, D}, {D, D}, {hidden, D}, {D, hidden}};
@@ -282,6 +308,11 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
     DRN_CHECK_ARG(a->mx_fused == 0 || (a->mx_fused == 1 && a->precision == 1));
     const bool mxf = a->mx_fused == 1;                   // producers write the quantised operand of the next block linear themselves
     if (mxf) DRN_CHECK_ARG(a->UQ && a->US && a->u_act_bytes >= drn_dit_forward_mx_u_bytes(B, S, a->hidden));
+    DRN_CHECK_ARG(a->attn_precision == 0 || a->attn_precision == 1);
+    const bool amx = a->attn_precision == 1;             // MXFP8 self-attention (either precision of the block linears)
+    const MxAttnLayout al = mx_attn_layout(B, S, D);
+    if (amx) DRN_CHECK_ARG(a->mx_attn && ((uintptr_t)a->mx_attn & 255) == 0 && a->mx_attn_bytes >= al.total);
+    uint8_t* const mxa = (uint8_t*)a->mx_attn;
     const bf16_t* shift = (const bf16_t*)a->shift;
     const bf16_t* scale = (const bf16_t*)a->scale;
     const bf16_t* gate = (const bf16_t*)a->gate;
@@ -347,7 +378,35 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
             DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->QKV, M, 3 * D, D, DRN_EPI_NONE, nullptr, nullptr, stream, nullptr, hq, hs));
             // mx_fused: attention writes O as MX into AQ | AS (the q|k|v GEMM that read them has finished in stream order);
             // the 32x32x16 body has no MX epilogue: that site keeps bf16 O + the quantise launch (the same bytes)
-            const bool omx = mxf && drn_attention_mx_available();
+            const bool amx_site = amx && drn_attention_mxfp8_choice(a->heads, S) == 1;      // from ONE clip's tokens
+            const bool omx = mxf && (amx_site || drn_attention_mx_available());
+            if (amx_site) {
+                // MXFP8 attention: q and k leave norm + RoPE as MX, v is transposed and quantised along the keys, then the same
+                // plan on the block-scaled kernels (split keys: the same partials and combine pass)
+                DRN_TRY(drn_qk_norm_rope_mx(q, k, sb->qn, sb->kn, a->cos, a->sin, mxa + al.qq, mxa + al.qs, mxa + al.kq, mxa + al.ks, M,
+                                            a->heads, 3 * D, 3 * D, S, 0, a->eps, 0, stream));
+                DRN_TRY(drn_mx_quant_vt(v, mxa + al.vt, mxa + al.vs, (int)B, a->heads, S, 3 * D, S * 3 * D, stream));
+                Scope tsc((drn_timer*)a->timer, 1, 4.0 * B * a->heads * S * S * 128, 1.0 * B * a->heads * 128 * (4.0 * S), (hipStream_t)stream);
+                int64_t plan[6];
+                const int n = drn_attention_plan(a->heads, S, S, plan);
+                for (int p = 0; p < n; ++p) {
+                    const int64_t q0 = plan[3 * p], nq = plan[3 * p + 1] - q0;
+                    const int ns = (int)plan[3 * p + 2];
+                    const uint8_t* qqs = mxa + al.qq + q0 * D;
+                    const uint8_t* qss = mxa + al.qs + q0 * (D / 32);
+                    bf16_t* os = omx ? nullptr : (bf16_t*)a->O + q0 * D;
+                    uint8_t* oq = omx ? (uint8_t*)a->AQ + q0 * D : nullptr;
+                    uint8_t* osc = omx ? (uint8_t*)a->AS + q0 * (D / 32) : nullptr;
+                    if (ns > 1) {
+                        if (!a->attn_ws || drn_attention_splitkv_workspace_bytes((int)B, a->heads, nq, ns) > a->attn_ws_bytes) return DRN_EINVAL;
+                        DRN_TRY(drn_attention_splitkv_mxfp8(qqs, qss, mxa + al.kq, mxa + al.ks, mxa + al.vt, mxa + al.vs, os, oq, osc, (int)B,
+                                                            a->heads, nq, S, S, S, D, S * D, sm_scale, ns, a->attn_ws, stream));
+                    } else {
+                        DRN_TRY(drn_attention_mxfp8(qqs, qss, mxa + al.kq, mxa + al.ks, mxa + al.vt, mxa + al.vs, os, oq, osc, (int)B, a->heads,
+                                                    nq, S, S, S, D, S * D, sm_scale, stream));
+                    }
+                }
+            } else {
             DRN_TRY(drn_qk_norm_rope(q, k, sb->qn, sb->kn, a->cos, a->sin, M, a->heads, 3 * D, 3 * D, S, 0, a->eps, stream));
             {
                 Scope tsc((drn_timer*)a->timer, 1, 4.0 * B * a->heads * S * S * 128, 2.0 * B * a->heads * 128 * (4.0 * S), (hipStream_t)stream);
@@ -376,6 +435,7 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
                                                    S * 3 * D, S * D, sm_scale, stream));
                     }
                 }
+            }
             }
             DRN_TRY(fwd_lin(a, a->O, sb->w_b, sb->s_b, a->X, M, D, D, DRN_EPI_GATE_RES, gt, a->X, stream, fuse ? &deferred : nullptr,
                             omx ? a->AQ : nullptr, omx ? a->AS : nullptr));

@@ -513,11 +513,17 @@ extern "C" int drn_rmsnorm(const void* x, const void* w, void* y, int64_t rows, 
 // per-head RMSNorm(q,k) + RoPE, in place.  8 lanes per 128-wide head row (lane j owns elements 8j..8j+7 and
 // 64+8j..64+8j+7, i.e. both members of every rotate_half pair), 8 head rows per wave.
 // CleanGeneralDIT.py:288-295 (norm), :45-84 (RoPE; cos/sin tables are host-built bf16).
+// MX = true (a second instantiation: the bf16 one is untouched): the result is (also) written as MXFP8, QQ | QS and KQ | KS contiguous
+// [tokens, heads * 128] e4m3 + [tokens, heads * 4] scales (drn.h: the bytes of drn_mx_quant_bf16 on what the bf16 form writes); the
+// in-place bf16 result only when write_bf16.  A 32-element block is the lo (or hi) halves of the four lanes j .. j ^ 3.
+template <bool MX>
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ q, bf16_t* __restrict__ k,
                                                            const bf16_t* __restrict__ wq, const bf16_t* __restrict__ wk,
                                                            const bf16_t* __restrict__ cs, const bf16_t* __restrict__ sn,
                                                            int64_t tokens, int heads, int64_t ldq, int64_t ldk,
-                                                           int64_t tpb, int64_t pos_offset, float eps) {
+                                                           int64_t tpb, int64_t pos_offset, float eps,
+                                                           uint8_t* __restrict__ QQ, uint8_t* __restrict__ QS,
+                                                           uint8_t* __restrict__ KQ, uint8_t* __restrict__ KS, int write_bf16) {
     const int lane = threadIdx.x & 63;
     const int hr = lane >> 3, j = lane & 7;
     const int hgroups = (heads + 7) / 8;
@@ -572,7 +578,34 @@ __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ 
                 hi[i] = rbf(rbf(b * ch[i]) + rbf(a * sh[i]));
             }
         }
-        if (act) {
+        if (MX) {
+            uint32_t al = 0, ah = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                al = max(al, mx_abs_bits(lo[i]));
+                ah = max(ah, mx_abs_bits(hi[i]));
+            }
+            al = max(al, (uint32_t)__shfl_xor((int)al, 1, 64));
+            ah = max(ah, (uint32_t)__shfl_xor((int)ah, 1, 64));
+            al = max(al, (uint32_t)__shfl_xor((int)al, 2, 64));
+            ah = max(ah, (uint32_t)__shfl_xor((int)ah, 2, 64));
+            const int el = mx_block_exp(al), eh = mx_block_exp(ah);
+            const float il = mx_inv_scale(el), ih = mx_inv_scale(eh);
+            if (act) {
+                const int64_t r = tok * heads + head;
+                uint8_t* eq = (which ? KQ : QQ) + r * 128;
+                uint8_t* es = (which ? KS : QS) + r * 4;
+                *reinterpret_cast<uint2*>(eq + 8 * j) =
+                    make_uint2(mx_pack4f(lo[0], lo[1], lo[2], lo[3], il), mx_pack4f(lo[4], lo[5], lo[6], lo[7], il));
+                *reinterpret_cast<uint2*>(eq + 64 + 8 * j) =
+                    make_uint2(mx_pack4f(hi[0], hi[1], hi[2], hi[3], ih), mx_pack4f(hi[4], hi[5], hi[6], hi[7], ih));
+                if ((j & 3) == 0) {
+                    es[j >> 2] = (uint8_t)(el + 127);
+                    es[2 + (j >> 2)] = (uint8_t)(eh + 127);
+                }
+            }
+        }
+        if (act && (!MX || write_bf16)) {
             *reinterpret_cast<uint4*>(base + 8 * j) = pack8(lo);
             *reinterpret_cast<uint4*>(base + 64 + 8 * j) = pack8(hi);
         }
@@ -589,9 +622,26 @@ extern "C" int drn_qk_norm_rope(void* q, void* k, const void* wq, const void* wk
     const int64_t items = tokens * ((heads + 7) / 8) * ((q ? 1 : 0) + (k ? 1 : 0));
     int64_t blocks = (items + 3) / 4;
     if (blocks > 8192) blocks = 8192;
-    qk_norm_rope_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(
+    qk_norm_rope_kernel<false><<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(
         (bf16_t*)q, (bf16_t*)k, (const bf16_t*)wq, (const bf16_t*)wk, (const bf16_t*)cos, (const bf16_t*)sin, tokens,
-        heads, ldq, ldk, tokens_per_batch, pos_offset, eps);
+        heads, ldq, ldk, tokens_per_batch, pos_offset, eps, nullptr, nullptr, nullptr, nullptr, 1);
+    return drn_launch_status();
+}
+
+extern "C" int drn_qk_norm_rope_mx(void* q, void* k, const void* wq, const void* wk, const void* cos, const void* sin, void* qq,
+                                   void* qs, void* kq, void* ks, int64_t tokens, int heads, int64_t ldq, int64_t ldk,
+                                   int64_t tokens_per_batch, int64_t pos_offset, float eps, int write_bf16, void* stream) {
+    DRN_CHECK_ARG((q || k) && (!q || (wq && qq && qs)) && (!k || (wk && kq && ks)) && tokens >= 0 && heads > 0 && ldq % 8 == 0 &&
+                  ldk % 8 == 0 && tokens_per_batch > 0 && (write_bf16 == 0 || write_bf16 == 1));
+    DRN_CHECK_ARG((cos == nullptr) == (sin == nullptr));
+    DRN_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)qq & 7) == 0 && ((uintptr_t)kq & 7) == 0);
+    if (tokens == 0) return DRN_OK;
+    const int64_t items = tokens * ((heads + 7) / 8) * ((q ? 1 : 0) + (k ? 1 : 0));
+    int64_t blocks = (items + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    qk_norm_rope_kernel<true><<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(
+        (bf16_t*)q, (bf16_t*)k, (const bf16_t*)wq, (const bf16_t*)wk, (const bf16_t*)cos, (const bf16_t*)sin, tokens,
+        heads, ldq, ldk, tokens_per_batch, pos_offset, eps, (uint8_t*)qq, (uint8_t*)qs, (uint8_t*)kq, (uint8_t*)ks, write_bf16);
     return drn_launch_status();
 }
 

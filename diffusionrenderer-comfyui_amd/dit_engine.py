@@ -31,6 +31,7 @@ from .parallel import ShardPlan, allgather_rows_, alltoall_bands_, alltoall_rows
 
 
 PRECISIONS = ("bf16", "mxfp8")
+ATTENTION_PRECISIONS = ("bf16", "mxfp8")
 
 
 def _pad_cols(w: torch.Tensor, mult: int) -> torch.Tensor:
@@ -55,10 +56,21 @@ def _pad_rows(w: torch.Tensor, mult: int) -> torch.Tensor:
 
 class HipDiT:
     def __init__(self, net: dict, state_dict: Dict[str, torch.Tensor], device=None, prefix: str = "net.",
-                 process_group=None, precision: Optional[str] = None):
+                 process_group=None, precision: Optional[str] = None, attention_precision: Optional[str] = None):
         """precision: "bf16" (default) or "mxfp8" (opt-in: the q|k|v, out-proj, MLP-up and MLP-down GEMMs of every block run on
-        MXFP8 operands quantised on the device, drn.h; everything else stays bf16).  None = $DRN_DIT_PRECISION, else "bf16"."""
+        MXFP8 operands quantised on the device, drn.h; everything else stays bf16).  None = $DRN_DIT_PRECISION, else "bf16".
+        attention_precision: "bf16" (default) or "mxfp8" (opt-in, independent of `precision`: both products of the self-attention
+        run on e4m3 operands, drn.h "MXFP8 self-attention", at the sites where drn_attention_mxfp8_choice says they pay: from 2048
+        tokens per clip; smaller clips keep the bf16 attention, bit for bit).  None = $DRN_ATT_PRECISION, else "bf16"."""
         import os
+        if attention_precision is None:
+            attention_precision = os.environ.get("DRN_ATT_PRECISION", "") or "bf16"
+        if attention_precision not in ATTENTION_PRECISIONS:
+            raise ValueError(f"unknown attention precision {attention_precision!r}: expected one of {ATTENTION_PRECISIONS}")
+        if attention_precision == "mxfp8" and process_group is not None:
+            raise ValueError("attention_precision='mxfp8' with a process_group (sequence parallelism) is not built yet")
+        self.attention_precision = attention_precision
+        self._amx = attention_precision == "mxfp8"
         if precision is None:
             precision = os.environ.get("DRN_DIT_PRECISION", "") or "bf16"
         if precision not in PRECISIONS:
@@ -298,6 +310,20 @@ class HipDiT:
                         ws["uact"] = torch.empty(lib.drn_dit_forward_mx_u_bytes(B, S, ws["u"].shape[1]), dtype=torch.uint8, device=dev)
                         ws["uact_q_bytes"] = n * ws["u"].shape[1]
                 ws["gemm_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-K partials (few tokens)
+                if self._amx:
+                    # MXFP8 attention: QQ | KQ | VT | QS | KS | VS in one buffer, laid out as drn_dit_forward reads it (drn.h)
+                    buf = torch.empty(lib.drn_dit_forward_mx_attn_bytes(B, S, D), dtype=torch.uint8, device=dev)
+                    Sp = (S + 127) // 128 * 128
+                    f8, up, off, views = torch.float8_e4m3fn, (lambda v: (v + 255) // 256 * 256), 0, []
+                    for nbytes, shape, dt in ((n * D, (n, D), f8), (n * D, (n, D), f8), (B * D * Sp, (B, self.heads, 128, Sp), f8),
+                                              (n * D // 32, (n, D // 32), None), (n * D // 32, (n, D // 32), None),
+                                              (B * D * Sp // 32, (B, self.heads, 128, Sp // 32), None)):
+                        v = buf[off:off + nbytes]
+                        views.append((v.view(dt) if dt is not None else v).view(shape))
+                        off += up(nbytes)
+                    assert off == buf.numel()
+                    ws["mx_attn"] = buf
+                    ws["mx_attn_views"] = (N.MxTensor(views[0], views[3]), N.MxTensor(views[1], views[4]), views[2], views[5])
                 nb = lib.drn_dit_forward_attn_workspace_bytes(B, self.heads, S)
                 ws["attn_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-KV partials
             elif self.exchange == "a2a":
@@ -564,6 +590,9 @@ class HipDiT:
                     a.mx_fused = 1
                     a.UQ, a.US = ws["uact"].data_ptr(), ws["uact"].data_ptr() + ws["uact_q_bytes"]
                     a.u_act_bytes = ws["uact"].numel()
+            if self._amx:
+                a.attn_precision = 1
+                a.mx_attn, a.mx_attn_bytes = ws["mx_attn"].data_ptr(), ws["mx_attn"].numel()
             N.dit_forward(a)
             return N.unpatchify(Y, B, self.out_ch, Tp, Hp, Wp, self.pt, self.ps)
         sharded = self.exchange != "none"
@@ -605,15 +634,26 @@ class HipDiT:
                         QKV = ws["qkv"]
                         self._lin(hin, sb["wqkv"], QKV, rows_per_batch=rows)
                         q, k, v = QKV[:, :D], QKV[:, D:2 * D], QKV[:, 2 * D:]
-                        N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
-                        omx = self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D) if fusedmx and N.attention_mx_available() else None
-                        if B == 1:
-                            oin = N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=None if omx else O.unsqueeze(0),
-                                              heads=self.heads, out_mx=omx)
+                        amx = self._amx and N.attention_mxfp8_choice(self.heads, S)      # per site, from ONE clip's tokens
+                        omx = (self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D)
+                               if fusedmx and (amx or N.attention_mx_available()) else None)
+                        if amx:
+                            # MXFP8 attention (the launches of drn_dit_forward with attn_precision 1): q and k leave norm + RoPE
+                            # as MX (trace mode keeps the bf16 q and k as well), v is transposed and quantised along the keys
+                            qm, km, vt, vs = ws["mx_attn_views"]
+                            N.qk_norm_rope_mx(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S,
+                                              write_bf16=self.trace is not None, out_q=qm, out_k=km)
+                            N.mx_quant_vt(QKV.view(B, S, 3 * D)[:, :, 2 * D:], self.heads, out=(vt, vs))
+                            oin = N.attention_mxfp8(qm, km, vt, vs, B, S, S, out=None if omx else O.view(B, S, D), out_mx=omx)
                         else:
-                            Q3 = QKV.view(B, S, 3 * D)
-                            oin = N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:], out=None if omx else O.view(B, S, D),
-                                              heads=self.heads, out_mx=omx)
+                            N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
+                            if B == 1:
+                                oin = N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=None if omx else O.unsqueeze(0),
+                                                  heads=self.heads, out_mx=omx)
+                            else:
+                                Q3 = QKV.view(B, S, 3 * D)
+                                oin = N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:],
+                                                  out=None if omx else O.view(B, S, D), heads=self.heads, out_mx=omx)
                         self._lin(oin if omx else O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate,
                                   residual=X, rows_per_batch=rows)
                     else:

@@ -133,8 +133,10 @@ class CleanDiffusionRendererModel:
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:5]} unexpected {unexpected[:5]} "
                                f"shape mismatch {bad[:5]}")
         # config key "dit_precision": "bf16" (default) or the opt-in "mxfp8" block linears; absent -> $DRN_DIT_PRECISION / bf16
+        # config key "dit_attention_precision": "bf16" (default) or the opt-in "mxfp8" self-attention; absent -> $DRN_ATT_PRECISION / bf16
         self.net = HipDiT(self.config["net"], state_dict, device=self.device, process_group=self.process_group,
-                          precision=self.config.get("dit_precision"))
+                          precision=self.config.get("dit_precision"),
+                          attention_precision=self.config.get("dit_attention_precision"))
         return missing, unexpected
 
     def _get_tensor_kwargs(self):

@@ -38,7 +38,8 @@ class DitForwardArgs(Structure):              # drn_dit_forward_args (include/dr
                 ("gemm_ws", c_void_p), ("gemm_ws_bytes", c_int64), ("attn_ws", c_void_p), ("attn_ws_bytes", c_int64),
                 ("timer", c_void_p), ("eps", c_float), ("precision", c_int32),
                 ("AQ", c_void_p), ("AS", c_void_p), ("act_bytes", c_int64),
-                ("mx_fused", c_int32), ("reserved", c_int32), ("UQ", c_void_p), ("US", c_void_p), ("u_act_bytes", c_int64)]
+                ("mx_fused", c_int32), ("reserved", c_int32), ("UQ", c_void_p), ("US", c_void_p), ("u_act_bytes", c_int64),
+                ("attn_precision", c_int32), ("reserved2", c_int32), ("mx_attn", c_void_p), ("mx_attn_bytes", c_int64)]
 
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); must match include/drn.h one-to-one
@@ -79,6 +80,14 @@ SIGNATURES = {
     "drn_attention_bf16_mx": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _P],
     "drn_attention_splitkv_bf16_mx": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _I, _P, _P],
     "drn_attention_mx_available": [],
+    "drn_attention_mxfp8_params": [POINTER(c_int), POINTER(c_float), POINTER(c_int)],
+    "drn_attention_mxfp8_choice": [_I, _L],
+    "drn_attention_mxfp8_force": [_I],
+    "drn_qk_norm_rope_mx": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _L, _L, _L, _F, _I, _P],
+    "drn_mx_quant_vt": [_P, _P, _P, _I, _I, _L, _L, _L, _P],
+    "drn_attention_mxfp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _F, _P],
+    "drn_attention_splitkv_mxfp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _F, _I, _P, _P],
+    "drn_dit_forward_mx_attn_bytes": [_L, _L, _L],
     "drn_gemm_mxfp8": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _P],
     "drn_gemm_mxfp8_splitk_choice": [_L, _L, _L],
     "drn_gemm_mxfp8_splitk": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _I, _P, _P],
@@ -106,7 +115,7 @@ SIGNATURES = {
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
              "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_mx_act_bytes": c_int64,
-             "drn_dit_forward_mx_u_bytes": c_int64, "drn_mx_quant_calls": c_int64,
+             "drn_dit_forward_mx_u_bytes": c_int64, "drn_mx_quant_calls": c_int64, "drn_dit_forward_mx_attn_bytes": c_int64,
              "drn_dit_forward_mx_gemm_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
              "drn_ln_force_kernel": None, "drn_attention_force_shape16": None}
 
@@ -602,6 +611,117 @@ def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None, out_mx=
             _check(fn(_ptr(qs), _ptr(k), _ptr(v), *outs, *geom, _stream()), name)
     if t0 is not None:
         _TIMER.end("attention", t0, 4.0 * B * H * Sq * Sk * 128, 2.0 * B * H * 128 * (2 * Sq + 2 * Sk))
+    return out if mx is None else mx
+
+
+# ----------------------------------------------------------------------------------------------- MXFP8 self-attention
+def attention_mxfp8_params():
+    """(key_tile, rescale_thr, pexp) of the MXFP8 attention kernel as built (drn_attention_mxfp8_params; host-only)."""
+    kt, thr, pe = c_int(), c_float(), c_int()
+    _check(load_library().drn_attention_mxfp8_params(kt, thr, pe), "drn_attention_mxfp8_params")
+    return kt.value, thr.value, pe.value
+
+
+def attention_mxfp8_choice(heads, S) -> bool:
+    """Whether a self-attention site of S tokens per clip runs on the MXFP8 kernels when the switch is on (drn_attention_mxfp8_choice:
+    the rule drn_dit_forward applies; host-only)."""
+    return bool(load_library().drn_attention_mxfp8_choice(heads, S))
+
+
+def attention_mxfp8_force(on: int) -> int:
+    """1 = every site of an engine with the switch on takes the MXFP8 kernels, 0 = the measured rule (default); returns the
+    previous setting (tests / A-B runs)."""
+    return int(load_library().drn_attention_mxfp8_force(on))
+
+
+def qk_norm_rope_mx(q, k, wq, wk, cos, sin, heads, tokens_per_batch=None, pos_offset=0, eps=1e-6, write_bf16=False,
+                    out_q=None, out_k=None):
+    """qk_norm_rope with the result written as MXFP8: returns (MxTensor of q or None, MxTensor of k or None), contiguous
+    [tokens, heads*128]; the in-place bf16 result is written as well only with write_bf16 (drn_qk_norm_rope_mx)."""
+    _bf16(q, k, wq, wk, cos, sin)
+    ref = q if q is not None else k
+    tokens = ref.shape[0]
+    for t in (q, k):
+        if t is not None:
+            assert t.shape == (tokens, heads * 128) and t.stride(1) == 1
+    mq = _mx_out(out_q if out_q is not None else True, tokens, heads * 128, ref.device) if q is not None else None
+    mk = _mx_out(out_k if out_k is not None else True, tokens, heads * 128, ref.device) if k is not None else None
+    _check(load_library().drn_qk_norm_rope_mx(_ptr(q), _ptr(k), _ptr(wq), _ptr(wk), _ptr(cos), _ptr(sin),
+                                              _ptr(mq.q) if mq else None, _ptr(mq.scales) if mq else None,
+                                              _ptr(mk.q) if mk else None, _ptr(mk.scales) if mk else None, tokens, heads,
+                                              q.stride(0) if q is not None else 0, k.stride(0) if k is not None else 0,
+                                              tokens_per_batch if tokens_per_batch else max(tokens, 1), pos_offset, eps,
+                                              1 if write_bf16 else 0, _stream()), "drn_qk_norm_rope_mx")
+    return mq, mk
+
+
+def mx_quant_vt(v, heads=None, out=None):
+    """v [B, Sk, H*128] bf16 (token- / batch-strided view allowed) -> (vt [B, H, 128, Skp] e4m3, vs [B, H, 128, Skp/32] uint8): V
+    transposed and quantised along the keys, zero-padded to Skp = Sk rounded up to 128 (drn_mx_quant_vt).  out: a (vt, vs) pair."""
+    _bf16(v)
+    B, Sk, HD = v.shape
+    H = heads if heads else HD // 128
+    assert HD == H * 128 and v.stride(2) == 1
+    Skp = (Sk + 127) // 128 * 128
+    if out is None:
+        out = (torch.empty((B, H, 128, Skp), dtype=torch.float8_e4m3fn, device=v.device),
+               torch.empty((B, H, 128, Skp // 32), dtype=torch.uint8, device=v.device))
+    vt, vs = out
+    assert vt.shape == (B, H, 128, Skp) and vt.is_contiguous() and vs.shape == (B, H, 128, Skp // 32) and vs.is_contiguous()
+    _check(load_library().drn_mx_quant_vt(_ptr(v), _ptr(vt), _ptr(vs), B, H, Sk, v.stride(1), v.stride(0), _stream()),
+           "drn_mx_quant_vt")
+    return vt, vs
+
+
+def attention_mxfp8(qm, km, vt, vs, B, Sq, Sk, q_bs=None, k_bs=None, out=None, scale=None, kv_splits=None, out_mx=None):
+    """MXFP8 attention (drn_attention_mxfp8 / drn_attention_splitkv_mxfp8).  qm / km: MxTensors [rows, H*128] with clip b's queries
+    from row b * q_bs (default Sq) and keys from row b * k_bs (default Sk); vt / vs from mx_quant_vt for (B, H, Sk).
+    -> out [B, Sq, H*128] bf16, or with out_mx (True or an MxTensor [B * Sq, H*128]) that MxTensor (bf16 `out` only when given).
+    kv_splits as attention()."""
+    _bf16(out)
+    HD = qm.q.shape[1]
+    H = HD // 128
+    q_bs = Sq if q_bs is None else q_bs
+    k_bs = Sk if k_bs is None else k_bs
+    Skp = (Sk + 127) // 128 * 128
+    assert HD == H * 128 and km.q.shape[1] == HD and qm.q.is_contiguous() and km.q.is_contiguous()
+    assert qm.q.shape[0] >= (B - 1) * q_bs + Sq and km.q.shape[0] >= (B - 1) * k_bs + Sk
+    assert vt.shape == (B, H, 128, Skp) and vt.is_contiguous() and vs.shape == (B, H, 128, Skp // 32) and vs.is_contiguous()
+    dev = qm.q.device
+    mx = None
+    if out_mx is not None:
+        mx = _mx_out(out_mx, B * Sq, HD, dev)
+        assert out is None or (out.shape == (B, Sq, HD) and out.is_contiguous())
+        oq, osc = mx.q.view(B, Sq, HD), mx.scales.view(B, Sq, HD // 32)
+        ldo, bso = HD, Sq * HD
+    else:
+        if out is None:
+            out = torch.empty((B, Sq, HD), dtype=torch.bfloat16, device=dev)
+        ldo, bso = out.stride(1), out.stride(0)
+    if scale is None:
+        scale = 1.0 / (128 ** 0.5)
+    plan = attention_plan(1, H, Sq, Sk) if kv_splits is None else [(0, Sq, int(kv_splits))]
+    t0 = _TIMER.begin("attention") if _TIMER is not None else None
+    lib = load_library()
+    for q0, q1, ns in plan:
+        n = q1 - q0
+        ops = (_ptr(qm.q[q0:]), _ptr(qm.scales[q0:]), _ptr(km.q), _ptr(km.scales), _ptr(vt), _ptr(vs),
+               _ptr(out[:, q0:q1]) if out is not None else None,
+               _ptr(oq[:, q0:q1]) if mx is not None else None, _ptr(osc[:, q0:q1]) if mx is not None else None)
+        geom = (B, H, n, Sk, q_bs, k_bs, ldo, bso, scale)
+        if ns > 1:
+            nbytes = lib.drn_attention_splitkv_workspace_bytes(B, H, n, ns)
+            key = (dev, nbytes)
+            ws = _SPLIT_WS.get(key)
+            if ws is None:
+                _SPLIT_WS.clear()
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                _SPLIT_WS[key] = ws
+            _check(lib.drn_attention_splitkv_mxfp8(*ops, *geom, ns, ws.data_ptr(), _stream()), "drn_attention_splitkv_mxfp8")
+        else:
+            _check(lib.drn_attention_mxfp8(*ops, *geom, _stream()), "drn_attention_mxfp8")
+    if t0 is not None:
+        _TIMER.end("attention", t0, 4.0 * B * H * Sq * Sk * 128, 1.0 * B * H * 128 * (2 * Sq + 2 * Sk))
     return out if mx is None else mx
 
 

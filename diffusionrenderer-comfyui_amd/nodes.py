@@ -53,13 +53,17 @@ class LoadDiffusionRendererModel:
                                        {"tooltip": "Models are loaded from 'ComfyUI/models/diffusion_models'"})},
                 "optional": {"dit_precision": (["bf16", "mxfp8"],
                                                {"default": "bf16",
-                                                "tooltip": "mxfp8: opt-in MXFP8 block linears (faster, ~4x the bf16 error)"})}}
+                                                "tooltip": "mxfp8: opt-in MXFP8 block linears (faster, ~4x the bf16 error)"}),
+                             "attention_precision": (["bf16", "mxfp8"],
+                                                     {"default": "bf16",
+                                                      "tooltip": "mxfp8: opt-in MXFP8 self-attention (Q, K, V and P as e4m3; "
+                                                                 "costs accuracy, see DESIGN 4c)"})}}
 
     RETURN_TYPES = ("DIFFUSION_RENDERER_PIPELINE",)
     FUNCTION = "load_pipeline"
     CATEGORY = "Cosmos1"
 
-    def load_pipeline(self, model, dit_precision="bf16"):
+    def load_pipeline(self, model, dit_precision="bf16", attention_precision="bf16"):
         import folder_paths
         import comfy.model_management as mm
         import comfy.utils
@@ -78,7 +82,8 @@ class LoadDiffusionRendererModel:
         state_dict = comfy.utils.load_torch_file(checkpoint_path, safe_load=True)
         if "model" in state_dict:
             state_dict = state_dict["model"]
-        model_instance = CleanDiffusionRendererModel(dict(get_inverse_renderer_config(), dit_precision=dit_precision), device=device)
+        model_instance = CleanDiffusionRendererModel(dict(get_inverse_renderer_config(), dit_precision=dit_precision,
+                                                              dit_attention_precision=attention_precision), device=device)
         model_instance.load_state_dict(state_dict, strict=True)     # repack to the HIP layouts, weights stay on GPU
         del state_dict
         mm.soft_empty_cache()

@@ -270,6 +270,55 @@ int drn_attention_splitkv_bf16_mx(const void* q, const void* k, const void* v, v
                                   float scale, int nsplit, void* workspace, void* stream);
 int drn_attention_mx_available(void);
 
+/* ---- MXFP8 self-attention (opt-in, HipDiT(attention_precision="mxfp8"); csrc/attention_mx.hip; no reference counterpart): both
+ * products of the attention run on v_mfma_scale_f32_16x16x128_f8f6f4 with e4m3 operands, the online softmax stays fp32.  The one
+ * rule of the MX producers holds: a producer rounds to bf16 where its twin rounds and applies the block rule to THAT value.
+ * Formats (elements e4m3fn, scales E8M0 bytes, rule as above):
+ *   Q, K: elements [rows, heads * 128], scales [rows, heads * 4] - one per 32 consecutive elements of the head dim - contiguous.
+ *   V:    stored TRANSPOSED and quantised along the keys: elements VT[b][head][128][Skp], scales VS[b][head][128][Skp / 32], Skp =
+ *         Sk rounded up to 128; a block is 32 consecutive keys of one (head, d); keys >= Sk count as zeros (element byte 0), an
+ *         all-zero block gets scale byte 0.
+ *   P:    rne_e4m3(p 2^PEXP) under the fixed operand scale 2^-PEXP, p = exp2((s - m) scale log2(e)); s = the fp32 accumulator of
+ *         dequant(q) . dequant(k); m = the query's reference maximum: kept while a key tile's maximum is within RESCALE_THR (log2
+ *         units) of it, else replaced by that tile's maximum, per query (2^THR 2^PEXP <= 448).  The denominator is the sum of the
+ *         QUANTISED p, so numerator and denominator see the same rounding.
+ *   Output: bf16 `o` and / or MXFP8 `oq` | `os`, exactly as drn_attention_bf16_mx (any one of o, oq may be NULL; os goes with oq).
+ * drn_attention_mxfp8_params (host-only): the key tile, RESCALE_THR and PEXP the kernel was built with. */
+int drn_attention_mxfp8_params(int* key_tile, float* rescale_thr, int* pexp);
+/* Which self-attention sites of a forward with the switch on take these kernels (host-only, a pure function of one clip's tokens
+ * like drn_gemm_mxfp8_splitk_choice): 1 from 2048 tokens per clip, else 0 = that site runs the bf16 attention exactly as with the
+ * switch off (measured: slower at 256 tokens, equal at 1024, ahead from 2048).  drn_dit_forward and the per-launch host
+ * path both ask it.  drn_attention_mxfp8_force (tests / A-B runs): 1 = every site, 0 = the rule (default), anything else only
+ * queries; returns the previous setting. */
+int drn_attention_mxfp8_choice(int heads, int64_t S);
+int drn_attention_mxfp8_force(int on);
+/* drn_qk_norm_rope with the result written as MXFP8: qq | qs and kq | ks, contiguous [tokens, heads * 128] / [tokens, heads * 4] -
+ * the bytes of drn_mx_quant_bf16 on what drn_qk_norm_rope writes.  Same strided q / k views, pos_offset, tokens_per_batch; q or k
+ * may be NULL (then its outputs are not touched).  write_bf16 (0 / 1): whether the in-place bf16 result is written as well.
+ * q / k 16-byte, qq / kq 8-byte aligned. */
+int drn_qk_norm_rope_mx(void* q, void* k, const void* wq, const void* wk, const void* cos, const void* sin,
+                        void* qq, void* qs, void* kq, void* ks,
+                        int64_t tokens, int heads, int64_t ldq, int64_t ldk, int64_t tokens_per_batch,
+                        int64_t pos_offset, float eps, int write_bf16, void* stream);
+/* v: the bf16 view [batch][Sk][heads][128] (token stride ldv, batch stride bsv, head h at offset h * 128: e.g. the v slice of the
+ * fused QKV output) -> vt | vs in the V layout above, zero padding up to Skp included.  ldv, bsv % 8 == 0, v / vt 16-byte, vs
+ * 4-byte aligned. */
+int drn_mx_quant_vt(const void* v, void* vt, void* vs, int batch, int heads, int64_t Sk, int64_t ldv, int64_t bsv, void* stream);
+/* non-causal attention, head_dim 128, on the operands above.  Any Sq >= 1, Sk >= 1 (rows past Sq are not stored, keys past Sk are
+ * masked).  Clips are stacked along the rows: clip b's queries start at row b * q_bs of qq | qs, its keys at row b * k_bs of
+ * kq | ks; vt | vs are those drn_mx_quant_vt writes for (batch, heads, Sk).  A launch over a query sub-range of a plan passes qq,
+ * qs, o, oq and os advanced by its first row (as drn_attention_bf16_mx documents).  o [batch, Sq, heads, 128] by ldo / bso.
+ * The split-KV form writes the fp32 partials of drn_attention_splitkv_bf16 (workspace: drn_attention_splitkv_workspace_bytes) and
+ * ends in the same combine pass, MX epilogue included.  scale > 0; qq / kq / vt / o 16-byte, oq 8-byte, scales 4-byte aligned;
+ * ldo, bso % 8 == 0; with oq: ldo == heads * 128 and bso % ldo == 0.  Anything else: DRN_EINVAL, nothing launched. */
+int drn_attention_mxfp8(const void* qq, const void* qs, const void* kq, const void* ks, const void* vt, const void* vs,
+                        void* o, void* oq, void* os, int batch, int heads, int64_t Sq, int64_t Sk,
+                        int64_t q_bs, int64_t k_bs, int64_t ldo, int64_t bso, float scale, void* stream);
+int drn_attention_splitkv_mxfp8(const void* qq, const void* qs, const void* kq, const void* ks, const void* vt, const void* vs,
+                                void* o, void* oq, void* os, int batch, int heads, int64_t Sq, int64_t Sk,
+                                int64_t q_bs, int64_t k_bs, int64_t ldo, int64_t bso, float scale,
+                                int nsplit, void* workspace, void* stream);
+
 /* ---- how drn_dit_forward / the host wrapper cover the (q-block, head) grid of ONE clip with whole rounds of the 256 CUs:
  * plan[3 i + {0,1,2}] = (q_begin, q_end, kv_splits) for launch i; returns the number of launches (1 or 2).  The q-blocks that
  * fill whole rounds run unsplit, a fractional last round runs as a second launch with its keys split (split-KV + combine).
@@ -316,7 +365,7 @@ typedef struct drn_dit_forward_args {
     void* timer;                          /* drn_timer_create handle or NULL */
     float eps;
     int32_t precision;                    /* 0: bf16 block linears; 1: MXFP8 (subs carry e4m3 weights + scales; patch embed, final
-                                           * layer, AdaLN and attention stay bf16) */
+                                           * layer and AdaLN stay bf16; the attention has its own switch, attn_precision) */
     void* AQ; void* AS; int64_t act_bytes;  /* precision 1: the quantised A operand of the next block linear, elements
                                            * [B S, max(D, hidden)] and scales [B S, max(D, hidden) / 32]; act_bytes = the bytes behind
                                            * both together (drn_dit_forward_mx_act_bytes) */
@@ -325,6 +374,10 @@ typedef struct drn_dit_forward_args {
     int32_t reserved;
     void* UQ; void* US; int64_t u_act_bytes;  /* mx_fused 1: the MX form of U, elements [B S, hidden] and scales [B S, hidden / 32];
                                            * u_act_bytes = the bytes behind both together (drn_dit_forward_mx_u_bytes) */
+    int32_t attn_precision;               /* 0: bf16 self-attention (all-zero trailing fields = exactly the launches above);
+                                           * 1: MXFP8 self-attention (below), with either precision of the block linears */
+    int32_t reserved2;
+    void* mx_attn; int64_t mx_attn_bytes; /* attn_precision 1: scratch for QQ | QS | KQ | KS | VT | VS (drn_dit_forward_mx_attn_bytes) */
 } drn_dit_forward_args;
 int drn_dit_forward(const drn_dit_forward_args* args, void* stream);
 int64_t drn_dit_forward_args_bytes(void);     /* sizeof the two structs as this library was compiled (binding self-check) */
@@ -350,6 +403,13 @@ int64_t drn_dit_forward_mx_act_bytes(int64_t B, int64_t S, int64_t D, int64_t hi
  * DRN_EINVAL before any launch when mx_fused is neither 0 nor 1, is 1 with precision 0, or UQ / US are NULL or u_act_bytes is
  * below drn_dit_forward_mx_u_bytes (host-only sizer). */
 int64_t drn_dit_forward_mx_u_bytes(int64_t B, int64_t S, int64_t hidden);
+/* attn_precision == 1: a FA sub-block runs the q|k|v GEMM, drn_qk_norm_rope_mx (write_bf16 0) and drn_mx_quant_vt into `mx_attn`,
+ * the plan loop on drn_attention_mxfp8 / drn_attention_splitkv_mxfp8, then out-proj; with mx_fused the output goes to AQ | AS as MX
+ * (O is not written), else to O as bf16.  mx_attn holds, in this order and each 256-byte aligned from a 256-byte aligned base: QQ
+ * [B S, D], KQ [B S, D], VT [B][heads][128][Sp], QS [B S, D / 32], KS [B S, D / 32], VS [B][heads][128][Sp / 32], Sp = S rounded up
+ * to 128 (host-only sizer below).  DRN_EINVAL before any launch when attn_precision is neither 0 nor 1, or is 1 with mx_attn NULL,
+ * misaligned or mx_attn_bytes short. */
+int64_t drn_dit_forward_mx_attn_bytes(int64_t B, int64_t S, int64_t D);
 int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden);
 
 /* ---- per-launch timing inside drn_dit_forward (the roofline leg of bench.py; no reference counterpart): a pool of HIP event

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """MXFP8 against bf16 on one box, interleaved in ONE process (CDNA guide rule 24), random data.
-    python tools/mxbench.py [gemm] [model] [--M ROWS] [--rounds R] [--cold C] [--sweep]
+    python tools/mxbench.py [gemm] [model] [attn] [--M ROWS] [--rounds R] [--cold C] [--sweep]
 gemm:  the four block linears at M rows (default 18 432 = cfg 3): what native.gemm runs in bf16 against drn_mx_quant_bf16 of the
        activation + drn_gemm_mxfp8 (and each of the two alone); the quantiser in GB/s against the HBM peak.
        --M 256 / --M 1024 (few tokens): also quantise + what native.gemm_mxfp8 picks (the few-token kernel of gemm_mx_tall.hip,
@@ -12,7 +12,10 @@ model: ms per step (DiT forward + Euler step) of the 28-block model at cfg 3 (57
        S = 256) with precision bf16, mxfp8, and mxfp8 built under DRN_PER_LAUNCH=1 (one ctypes call per kernel; at cfg 1 also
        with the small-M path off: the path of an mxfp8 engine before gemm_mx_tall.hip), and mxfp8 built under DRN_MX_FUSED=0 (a
        quantise launch in front of every block linear: the launches of an mxfp8 engine before the fused producers), synthetic
-       weights."""
+       weights; and both precisions of the block linears with attention_precision="mxfp8" (the MXFP8 self-attention).
+attn:  one self-attention site of the 32-head model at S = 256, 1024, 2048 and 18 432 tokens: qk_norm_rope + attention on the bf16
+       16x16x32 body (the yardstick) against qk_norm_rope_mx + mx_quant_vt + attention_mxfp8 (the two producer launches counted),
+       each under the attention plan of its shape, interleaved; every run is printed, then median and max - min spread."""
 import argparse
 import os
 import sys
@@ -196,6 +199,63 @@ def bench_producers(pkg, args):
               f"spread {min(t['sep']) * 1e3:.1f}..{max(t['sep']) * 1e3:.1f} | {min(t['fused']) * 1e3:.1f}..{max(t['fused']) * 1e3:.1f}")
 
 
+def bench_attn(pkg, args):
+    N = pkg.native
+    dev = torch.device("cuda")
+    heads, D = 32, 4096
+    g = torch.Generator(device="cpu").manual_seed(2)
+    wq = torch.randn(128, generator=g).to(torch.bfloat16).to(dev)
+    wk = torch.randn(128, generator=g).to(torch.bfloat16).to(dev)
+    kt, thr, pexp = N.attention_mxfp8_params()
+    print(f"# attention, heads {heads}: bf16 = qk_norm_rope + attention (16x16x32 body) | mxfp8 = qk_norm_rope_mx + mx_quant_vt + "
+          f"attention_mxfp8 (key tile {kt}, rescale threshold {thr:g}, pexp {pexp}); {args.rounds} interleaved rounds")
+    for S in (256, 1024, 2048, 18432):
+        src = (torch.randn(S, 3 * D, generator=g)).to(torch.bfloat16).to(dev)
+        qkv = src.clone()
+        ang = torch.rand(S, 128, generator=g) * 6.28
+        cos, sin = ang.cos().to(torch.bfloat16).to(dev), ang.sin().to(torch.bfloat16).to(dev)
+        q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
+        o = torch.empty(1, S, D, dtype=torch.bfloat16, device=dev)
+        qm, km = N.mx_empty(S, D, dev), N.mx_empty(S, D, dev)
+        vtvs = N.mx_quant_vt(v.unsqueeze(0), heads)
+
+        def run_bf16():
+            N.qk_norm_rope(q, k, wq, wk, cos, sin, heads)            # (in place: the values drift towards the norm's fixed point;
+            N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=o, heads=heads)     #  the time does not depend on them)
+
+        def run_mx():
+            N.qk_norm_rope_mx(q, k, wq, wk, cos, sin, heads, out_q=qm, out_k=km)
+            N.mx_quant_vt(v.unsqueeze(0), heads, out=vtvs)
+            N.attention_mxfp8(qm, km, vtvs[0], vtvs[1], 1, S, S, out=o)
+
+        def run_mx_kernel():
+            N.attention_mxfp8(qm, km, vtvs[0], vtvs[1], 1, S, S, out=o)
+
+        def run_bf16_kernel():
+            N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=o, heads=heads)
+
+        cases = [("bf16", run_bf16), ("mxfp8", run_mx), ("bf16 kernel alone", run_bf16_kernel), ("mxfp8 kernel alone", run_mx_kernel)]
+        reps = args.reps if S >= 18432 else 5 * args.reps
+        for _, f in cases:
+            timed(f, 3)
+        t = {c: [] for c, _ in cases}
+        for _ in range(args.rounds):
+            for c, f in cases:
+                qkv.copy_(src)
+                t[c].append(timed(f, reps))
+        med = {c: sorted(v)[len(v) // 2] for c, v in t.items()}
+        spread = max(t["bf16"]) - min(t["bf16"])
+        print(f"S={S:5d} plan {N.attention_plan(1, heads, S, S)}")
+        for c, _ in cases:
+            print(f"    {c:18s}: runs " + " ".join(f"{x:.4f}" for x in t[c]) + f" ms | median {med[c]:.4f} ms")
+        fl = 4.0 * heads * S * S * 128
+        print(f"    median mxfp8 - bf16 = {med['mxfp8'] - med['bf16']:+.4f} ms ({med['mxfp8'] / med['bf16']:.3f} x); bf16 spread (max - min) "
+              f"{spread:.4f} ms; kernels alone: bf16 {fl / med['bf16 kernel alone'] / 1e9:.0f} TF, mxfp8 {fl / med['mxfp8 kernel alone'] / 1e9:.0f} TF; "
+              f"faster by more than the spread: {'yes' if med['bf16'] - med['mxfp8'] > spread else 'no'}")
+        del src, qkv, o, qm, km, vtvs
+        torch.cuda.empty_cache()
+
+
 def bench_model(pkg, args):
     N = pkg.native
     dev = torch.device("cuda")
@@ -211,6 +271,10 @@ def bench_model(pkg, args):
     os.environ["DRN_MX_FUSED"] = "0"                     # read at construction: a quantise launch per block linear
     dits["mxfp8 DRN_MX_FUSED=0"] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision="mxfp8")
     del os.environ["DRN_MX_FUSED"]
+    lib0 = N.load_library()
+    lib0.drn_attention_mxfp8_force(1)                    # every site on the MXFP8 kernels (the engine's own rule keeps bf16 below 2048 tokens)
+    for prec in ("bf16", "mxfp8"):                       # the MXFP8 self-attention switch, under both precisions of the block linears
+        dits[f"{prec} + attention mxfp8"] = pkg.dit_engine.HipDiT(net, sd, device=dev, precision=prec, attention_precision="mxfp8")
     lib = N.load_library()
     del sd
     torch.cuda.empty_cache()
@@ -243,6 +307,12 @@ def bench_model(pkg, args):
               f"({100 * (1 - med['mxfp8'] / med['bf16']):+.1f} % lower) | "
               + " | ".join(f"{p} {v:.3f}" for p, v in med.items() if p not in ("bf16", "mxfp8"))
               + " | spread (min..max) " + ", ".join(f"{p} {min(v):.3f}..{max(v):.3f}" for p, v in t.items()))
+        for base in ("bf16", "mxfp8"):
+            on, off = f"{base} + attention mxfp8", base
+            spread = max(t[off]) - min(t[off])
+            print(f"#   attention mxfp8 under {base} linears: runs " + " ".join(f"{v:.3f}" for v in t[on]) + f" | switch off runs "
+                  + " ".join(f"{v:.3f}" for v in t[off]) + f" | median {med[on]:.3f} vs {med[off]:.3f} ms/step, spread of the switch-off "
+                  f"runs {spread:.3f}: faster by more than the spread: {'yes' if med[off] - med[on] > spread else 'no'}")
 
 
 def main():
@@ -261,6 +331,8 @@ def main():
     if "gemm" in args.what:
         bench_gemm(pkg, args)
         bench_producers(pkg, args)
+    if "attn" in args.what:
+        bench_attn(pkg, args)
     if "model" in args.what:
         bench_model(pkg, args)
 
