@@ -24,6 +24,7 @@
 // so on every SIMD one wave feeds the matrix pipe while its partner's VALU work fills the issue slots between its MFMAs.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 #include "mx_quant.h"
 
 // Build switches (A/B timing of variants in one process: tools/kbench.py --lib; the shipped library uses the defaults):
@@ -606,8 +607,7 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __r
     }
 }
 
-// the combine pass of a split-KV launch (oq != NULL: the MX epilogue); attention_mx.hip's split-KV form writes the same partials
-// and ends in this launch too
+// the combine pass of a split-KV launch (drn_launchers.h)
 void drn_attention_combine_launch(const float* opart, const float* mlpart, void* o, int nsplit, int batch, int heads, int64_t Sq,
                                   int64_t ldo, int64_t bso, float scale_log2e, void* oq, void* os, int64_t mx_bs, hipStream_t st) {
     const int64_t items = (int64_t)batch * Sq * heads;
@@ -620,11 +620,6 @@ void drn_attention_combine_launch(const float* opart, const float* mlpart, void*
                                                                     scale_log2e, nullptr, nullptr, 0);
 }
 
-// attention16.hip: the same kernel on v_mfma_f32_16x16x32_bf16 (same grid, same arguments)
-void drn_attention16_launch(const void* q, const void* k, const void* v, void* o, int heads, int64_t Sq, int64_t Sk, int64_t ldq,
-                            int64_t ldk, int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
-                            float scale_log2e, int nqb, int64_t total, int nsplit, int64_t kv_chunk, float* opart, float* mlpart,
-                            hipStream_t st, void* oq, void* os, int64_t mx_bs);
 // default since round 3: the 16x16x32 body (tools/kbench.py attn --shapes 0,1: 4.21-4.33 vs 4.46-4.62 ms at cfg 3, in the model
 // 121.8 vs 124.6 ms of attention per step; both bodies pass the same tests).  DRN_ATT16=0 selects the 32x32x16 body below.
 #ifndef ATT_DEFAULT_SHAPE16
@@ -656,37 +651,20 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
     DRN_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 15) == 0);
     // the tile DMA addresses a K / V row as a 32-bit byte offset from the tile's first row (64 rows x ld x 2 B)
     DRN_CHECK_ARG(ldk > 0 && ldv > 0 && 64 * ldk * 2 < (1ll << 32) && 64 * ldv * 2 < (1ll << 32));
-    int64_t mx_bs = 0;
-    if (oq) {
-        // MX output: rows of heads * 128 elements, contiguous; clip b starts bso / ldo rows after clip b - 1 (the bf16 geometry)
-        DRN_CHECK_ARG(os && attention_shape16() && ldo == (int64_t)heads * 128 && bso >= 0 && bso % ldo == 0);
-        DRN_CHECK_ARG(((uintptr_t)oq & 7) == 0 && ((uintptr_t)os & 3) == 0);
-        mx_bs = bso / ldo;
-        DRN_CHECK_ARG(batch == 1 || mx_bs >= Sq);
-    }
+    AttnLaunch L;
+    DRN_TRY(drn_attention_prologue(&L, oq, os, attention_shape16(), batch, heads, Sq, Sk, ldo, bso, scale, nsplit, workspace, QROWS, KVT));
     if (Sq == 0) return DRN_OK;
-    int64_t kv_chunk = Sk;
-    if (nsplit > 1) {
-        DRN_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && batch <= 65535);
-        kv_chunk = ((Sk + nsplit - 1) / nsplit + KVT - 1) / KVT * KVT;
-        nsplit = (int)((Sk + kv_chunk - 1) / kv_chunk);                       // no empty chunk
-    }
-    const int64_t nqb = (Sq + QROWS - 1) / QROWS;
-    const int64_t total = nqb * heads * batch * nsplit;
-    DRN_CHECK_ARG(total < (1ll << 31));
-    const float scale_log2e = scale * 1.44269504088896340736f;
-    float* opart = (float*)workspace;
-    float* mlpart = opart ? opart + (int64_t)nsplit * batch * Sq * heads * 128 : nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (attention_shape16()) {
         // (a launch whose keys are split writes fp32 partials: the MX epilogue is the combine kernel's)
-        drn_attention16_launch(q, k, v, o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale_log2e, (int)nqb, total, nsplit,
-                               kv_chunk, opart, mlpart, st, nsplit > 1 ? nullptr : oq, os, mx_bs);
+        drn_attention16_launch(q, k, v, o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, L.scale_log2e, (int)L.nqb, L.total,
+                               L.nsplit, L.kv_chunk, L.opart, L.mlpart, st, L.nsplit > 1 ? nullptr : oq, os, L.mx_bs);
     } else
-    attention_fwd_kernel<<<dim3((unsigned)total, 1, 1), dim3(512), 0, st>>>(
+    attention_fwd_kernel<<<dim3((unsigned)L.total, 1, 1), dim3(512), 0, st>>>(
         (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk,
-        bsv, bso, scale_log2e, (int)nqb, (int)total, nsplit, kv_chunk, opart, mlpart);
-    if (nsplit > 1) drn_attention_combine_launch(opart, mlpart, o, nsplit, batch, heads, Sq, ldo, bso, scale_log2e, oq, os, mx_bs, st);
+        bsv, bso, L.scale_log2e, (int)L.nqb, (int)L.total, L.nsplit, L.kv_chunk, L.opart, L.mlpart);
+    if (L.nsplit > 1)
+        drn_attention_combine_launch(L.opart, L.mlpart, o, L.nsplit, batch, heads, Sq, ldo, bso, L.scale_log2e, oq, os, L.mx_bs, st);
     return drn_launch_status();
 }
 

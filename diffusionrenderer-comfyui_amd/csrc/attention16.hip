@@ -21,6 +21,7 @@
 // free the slot; hand-counted s_waitcnt lgkmcnt (V fragment = 2 LDS reads, K fragment = 1).  The last 8 reads of M(t) fetch the
 // first V key step of tile t for M(t+1) and stay in flight across S(t).
 #include "drn_common.h"
+#include "drn_launchers.h"
 #include "mx_quant.h"
 
 #define QROWS 256

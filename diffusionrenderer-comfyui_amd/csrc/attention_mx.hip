@@ -24,11 +24,8 @@
 // zero-padded to a multiple of 128 keys by its producer.
 #include <type_traits>
 #include "drn_common.h"
+#include "drn_launchers.h"
 #include "mx_quant.h"
-
-// attention.hip: the merge of split-KV partials (bf16 and / or MX output)
-void drn_attention_combine_launch(const float* opart, const float* mlpart, void* o, int nsplit, int batch, int heads, int64_t Sq,
-                                  int64_t ldo, int64_t bso, float scale_log2e, void* oq, void* os, int64_t mx_bs, hipStream_t st);
 
 #ifndef ATTMX_RESCALE_THR
 #define ATTMX_RESCALE_THR 4     // log2 units
@@ -353,42 +350,24 @@ int attention_mx_launch(const void* qq, const void* qs, const void* kq, const vo
     DRN_CHECK_ARG(((uintptr_t)qq & 15) == 0 && ((uintptr_t)kq & 15) == 0 && ((uintptr_t)vt & 15) == 0);
     DRN_CHECK_ARG(((uintptr_t)qs & 3) == 0 && ((uintptr_t)ks & 3) == 0 && ((uintptr_t)vs & 3) == 0);
     DRN_CHECK_ARG(ldo % 8 == 0 && bso % 8 == 0 && ldo >= (int64_t)heads * 128 && ((uintptr_t)o & 15) == 0);
-    int64_t mx_bs = 0;
-    if (oq) {
-        // MX output: rows of heads * 128 elements, contiguous; clip b starts bso / ldo rows after clip b - 1 (the bf16 geometry)
-        DRN_CHECK_ARG(os && ldo == (int64_t)heads * 128 && bso >= 0 && bso % ldo == 0);
-        DRN_CHECK_ARG(((uintptr_t)oq & 7) == 0 && ((uintptr_t)os & 3) == 0);
-        mx_bs = bso / ldo;
-        DRN_CHECK_ARG(batch == 1 || mx_bs >= Sq);
-    }
+    AttnLaunch L;
+    DRN_TRY(drn_attention_prologue(&L, oq, os, true, batch, heads, Sq, Sk, ldo, bso, scale, nsplit, workspace, QROWS, KT));
     if (Sq == 0) return DRN_OK;
-    int64_t kv_chunk = Sk;
-    if (nsplit > 1) {
-        DRN_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && batch <= 65535);
-        kv_chunk = ((Sk + nsplit - 1) / nsplit + KT - 1) / KT * KT;
-        nsplit = (int)((Sk + kv_chunk - 1) / kv_chunk);                       // no empty chunk
-    }
     const int64_t Skp = (Sk + KT - 1) / KT * KT;
-    const int64_t nqb = (Sq + QROWS - 1) / QROWS;
-    const int64_t total = nqb * heads * batch * nsplit;
-    DRN_CHECK_ARG(total < (1ll << 31));
-    const float scale_log2e = scale * 1.44269504088896340736f;
-    float* opart = (float*)workspace;
-    float* mlpart = opart ? opart + (int64_t)nsplit * batch * Sq * heads * 128 : nullptr;
     hipStream_t st = (hipStream_t)stream;
     // (a launch whose keys are split writes fp32 partials: the MX epilogue is the combine kernel's)
-    if (oq && nsplit == 1)
-        attention_mx_kernel<true><<<dim3((unsigned)total), dim3(512), 0, st>>>(
+    if (oq && L.nsplit == 1)
+        attention_mx_kernel<true><<<dim3((unsigned)L.total), dim3(512), 0, st>>>(
             (const uint8_t*)qq, (const uint8_t*)qs, (const uint8_t*)kq, (const uint8_t*)ks, (const uint8_t*)vt, (const uint8_t*)vs,
-            (bf16_t*)o, heads, Sq, Sk, q_bs, k_bs, Skp, ldo, bso, scale_log2e, (int)nqb, (int)total, nsplit, kv_chunk, opart, mlpart,
-            (uint8_t*)oq, (uint8_t*)os, mx_bs);
+            (bf16_t*)o, heads, Sq, Sk, q_bs, k_bs, Skp, ldo, bso, L.scale_log2e, (int)L.nqb, (int)L.total, L.nsplit, L.kv_chunk, L.opart,
+            L.mlpart, (uint8_t*)oq, (uint8_t*)os, L.mx_bs);
     else
-        attention_mx_kernel<false><<<dim3((unsigned)total), dim3(512), 0, st>>>(
+        attention_mx_kernel<false><<<dim3((unsigned)L.total), dim3(512), 0, st>>>(
             (const uint8_t*)qq, (const uint8_t*)qs, (const uint8_t*)kq, (const uint8_t*)ks, (const uint8_t*)vt, (const uint8_t*)vs,
-            (bf16_t*)o, heads, Sq, Sk, q_bs, k_bs, Skp, ldo, bso, scale_log2e, (int)nqb, (int)total, nsplit, kv_chunk, opart, mlpart,
-            nullptr, nullptr, 0);
-    if (nsplit > 1)
-        drn_attention_combine_launch(opart, mlpart, o, nsplit, batch, heads, Sq, ldo, bso, scale_log2e, oq, os, mx_bs, st);
+            (bf16_t*)o, heads, Sq, Sk, q_bs, k_bs, Skp, ldo, bso, L.scale_log2e, (int)L.nqb, (int)L.total, L.nsplit, L.kv_chunk, L.opart,
+            L.mlpart, nullptr, nullptr, 0);
+    if (L.nsplit > 1)
+        drn_attention_combine_launch(L.opart, L.mlpart, o, L.nsplit, batch, heads, Sq, ldo, bso, L.scale_log2e, oq, os, L.mx_bs, st);
     return drn_launch_status();
 }
 

@@ -18,6 +18,7 @@
 // Accumulation order per output element = conv_igemm.hip's (K ascending, 32 per MFMA): results are bit-identical.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 #include "conv_geom.h"
 #define BETWEEN_PROLOGUE_STEPS() ADVANCE()
 #include "gemm256s_core.h"

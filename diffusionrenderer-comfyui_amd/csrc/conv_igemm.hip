@@ -18,6 +18,7 @@
 // D = Wfrag x Afrag so a lane owns 4 consecutive output channels of one position).
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 
 #define BM 128
 #define BN 128
@@ -181,12 +182,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const bf16_t* __rest
         }
     }
 }
-
-// conv256s.hip: the streamed 256x256 kernel for the big convolutions
-bool drn_conv256s_ok(const ConvGeom& g, int C, int N, int64_t ldc, int64_t ldr, bool has_residual, bool out_f32, const void* y,
-                     const void* residual);
-int drn_conv256s_launch(const void* x, const void* w, const void* bias, void* y, const void* residual, const ConvGeom& g, int C,
-                        int N, int64_t ldw, int64_t ldc, int64_t ldr, void* stream);
 
 // drn_conv_force_tile: -1 automatic, 0 the 128x128 kernel always, 1 the 256x256 streamed kernel wherever it can run (also
 // below its size threshold).  drn_conv_last_tile: which kernel the last drn_conv3d_igemm call launched (tests / tools).

@@ -7,11 +7,7 @@
 // Why it exists: a forward is ~570 launches; through ctypes + torch wrappers each costs the host 6-12 us, which at S = 256
 // (cfg 1: a 6.8 ms GPU step) made the host the bound of the denoising loop.  From C the same launches cost the host ~2 ms.
 // Host code only (no kernel lives in this file).
-#include <stdlib.h>
 #include "drn_common.h"
-
-// attention.hip: 1 when the selected attention body has the MX epilogue (drn_attention_bf16_mx would run)
-extern "C" int drn_attention_mx_available(void);
 
 // ---- how to cover the (q-block, head) grid with whole rounds of the 256 CUs (was native.attention_plan; measured cost model)
 static const int kCUs = 256;
@@ -140,81 +136,6 @@ struct Scope {                                           // event pair around on
 };
 }  // namespace
 
-#define DRN_TRY(expr)                  \
-    do {                               \
-        const int rc_ = (expr);        \
-        if (rc_ != DRN_OK) return rc_; \
-    } while (0)
-
-// out = epi(A . W^T) exactly as native.gemm dispatches it: split-K for few-token products (decided from ONE clip's rows).
-// `defer`: a split-K product with the gated-residual epilogue may stop after its slices (returns *defer = split count): the
-// caller folds sum + epilogue into the next LayerNorm pass (drn_splitk_gate_res_ln_modulate: the same bits).
-static int fwd_gemm(const drn_dit_forward_args* a, const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K,
-                    int64_t lda, int64_t ldc, int epi, const void* gate, const void* residual, int64_t ldr, void* stream,
-                    int* defer = nullptr) {
-    const int64_t rpb = a->S;
-    const int64_t Mb = (rpb > 0 && rpb < M && M % rpb == 0) ? rpb : M;
-    const int splits = Mb <= 1024 ? drn_gemm_splitk_choice(Mb, N, K) : 1;
-    Scope sc((drn_timer*)a->timer, 0, 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N * (residual ? 2 : 1)), (hipStream_t)stream);
-    if (defer) *defer = 0;
-    if (splits > 1) {
-        if (!a->gemm_ws || drn_gemm_splitk_workspace_bytes(M, N, splits) > a->gemm_ws_bytes) return DRN_EINVAL;
-        if (defer && epi == DRN_EPI_GATE_RES && N == a->D && N > 1024 && ldc == N && ldr == N && residual == C) {
-            *defer = splits;
-            return drn_gemm_bf16_splitk_partials(A, W, M, N, K, lda, K, rpb, splits, a->gemm_ws, stream);
-        }
-        return drn_gemm_bf16_splitk(A, W, C, M, N, K, lda, K, ldc, epi, gate, residual, ldr, rpb, splits, a->gemm_ws, stream);
-    }
-    return drn_gemm_bf16(A, W, C, M, N, K, lda, K, ldc, epi, gate, residual, ldr, rpb, stream);
-}
-
-// The same for a block linear of a precision-1 (MXFP8) forward: quantise A into AQ | AS, then the MXFP8 product chosen as
-// native.gemm_mxfp8 chooses it (drn_gemm_mxfp8_splitk_choice on ONE clip's rows): drn_gemm_mxfp8 (0), the fused few-token kernel
-// (1) or its K slices (> 1; `defer` as in fwd_gemm, same conditions).
-// mx_fused forwards: QA | QSA != NULL = the producer of A wrote it as MX there already (no quantise launch; A is not read);
-// CQ | CS != NULL (MLP-up) = the GELU result leaves as MX through drn_gemm_mxfp8_gelu_mx where that entry has a kernel
-// (*c_is_mx = 1), else as bf16 into C (*c_is_mx = 0: the consumer quantises by launch, the same bytes).
-static int fwd_gemm_mx(const drn_dit_forward_args* a, const void* A, const void* W, const void* SW, void* C, int64_t M, int64_t N,
-                       int64_t K, int64_t lda, int64_t ldc, int epi, const void* gate, const void* residual, int64_t ldr,
-                       void* stream, int* defer = nullptr, const void* QA = nullptr, const void* QSA = nullptr, void* CQ = nullptr,
-                       void* CS = nullptr, int* c_is_mx = nullptr) {
-    const int64_t rpb = a->S;
-    const int64_t Mb = (rpb > 0 && rpb < M && M % rpb == 0) ? rpb : M;
-    if (defer) *defer = 0;
-    if (c_is_mx) *c_is_mx = 0;
-    if (!QA) {
-        DRN_TRY(drn_mx_quant_bf16(A, M, K, lda, a->AQ, a->AS, stream));
-        QA = a->AQ;
-        QSA = a->AS;
-    }
-    const int splits = drn_gemm_mxfp8_splitk_choice(Mb, N, K);
-    Scope sc((drn_timer*)a->timer, 0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (residual ? 2 : 1), (hipStream_t)stream);
-    if (CQ && epi == DRN_EPI_GELU && splits <= 1) {
-        if (c_is_mx) *c_is_mx = 1;
-        return drn_gemm_mxfp8_gelu_mx(QA, QSA, W, SW, CQ, CS, M, N, K, rpb, stream);
-    }
-    if (splits == 0) return drn_gemm_mxfp8(QA, QSA, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, stream);
-    if (splits > 1) {
-        if (!a->gemm_ws || drn_gemm_splitk_workspace_bytes(M, N, splits) > a->gemm_ws_bytes) return DRN_EINVAL;
-        if (defer && epi == DRN_EPI_GATE_RES && N == a->D && N > 1024 && ldc == N && ldr == N && residual == C) {
-            *defer = splits;
-            return drn_gemm_mxfp8_splitk_partials(QA, QSA, W, SW, M, N, K, rpb, splits, a->gemm_ws, stream);
-        }
-    }
-    return drn_gemm_mxfp8_splitk(QA, QSA, W, SW, C, M, N, K, ldc, epi, gate, residual, ldr, rpb, splits, a->gemm_ws, stream);
-}
-
-// a block linear in the precision of the forward
-static int fwd_lin(const drn_dit_forward_args* a, const void* A, const void* W, const void* SW, void* C, int64_t M, int64_t N,
-                   int64_t K, int epi, const void* gate, const void* residual, void* stream, int* defer = nullptr,
-                   const void* QA = nullptr, const void* QSA = nullptr, void* CQ = nullptr, void* CS = nullptr,
-                   int* c_is_mx = nullptr) {
-    const int64_t ldr = residual ? N : 0;
-    if (a->precision == 1)
-        return fwd_gemm_mx(a, A, W, SW, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer, QA, QSA, CQ, CS, c_is_mx);
-    return fwd_gemm(a, A, W, C, M, N, K, K, N, epi, gate, residual, ldr, stream, defer);
-}
-
 extern "C" int64_t drn_dit_forward_attn_workspace_bytes(int64_t B, int heads, int64_t S) {
     int64_t plan[6];
     const int n = drn_attention_plan(heads, S, S, plan);
@@ -227,13 +148,16 @@ extern "C" int64_t drn_dit_forward_attn_workspace_bytes(int64_t B, int heads, in
     return need;
 }
 
+// the fp32 slices of one bf16 linear [B S, N, K] (0 when it is not split)
+static int64_t bf16_splitk_bytes(int64_t B, int64_t S, int64_t N, int64_t K) {
+    return drn_gemm_splitk_workspace_bytes(B * S, N, S <= 1024 ? drn_gemm_splitk_choice(S, N, K) : 1);
+}
+
 extern "C" int64_t drn_dit_forward_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden, int64_t n_final, int64_t kpad) {
-    const int64_t M = B * S;
     const int64_t shapes[6][2] = {{D, kpad}, {3 * D, D}, {D, D}, {hidden, D}, {D, hidden}, {n_final, D}};
     int64_t need = 0;
     for (int i = 0; i < 6; ++i) {
-        const int splits = S <= 1024 ? drn_gemm_splitk_choice(S, shapes[i][0], shapes[i][1]) : 1;
-        const int64_t b = drn_gemm_splitk_workspace_bytes(M, shapes[i][0], splits);
+        const int64_t b = bf16_splitk_bytes(B, S, shapes[i][0], shapes[i][1]);
         need = b > need ? b : need;
     }
     return need;
@@ -248,30 +172,25 @@ extern "C" int64_t drn_dit_forward_mx_u_bytes(int64_t B, int64_t S, int64_t hidd
     return B * S * hidden + B * S * (hidden / 32);
 }
 
-// the MXFP8 attention scratch: QQ | KQ | VT | QS | KS | VS, each rounded up to 256 bytes (drn.h)
-namespace {
-struct MxAttnLayout {
-    int64_t qq, kq, vt, qs, ks, vs, total, Sp;
-};
-int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
-MxAttnLayout mx_attn_layout(int64_t B, int64_t S, int64_t D) {
-    MxAttnLayout l;
-    l.Sp = (S + 127) / 128 * 128;
+// the MXFP8 attention scratch: QQ | KQ | VT | QS | KS | VS, each rounded up to 256 bytes (drn.h): the ONE statement of the layout;
+// out = the six byte offsets in that order, the total, Sp
+extern "C" int drn_dit_forward_mx_attn_layout(int64_t B, int64_t S, int64_t D, int64_t* out) {
+    DRN_CHECK_ARG(out && B > 0 && S > 0 && D > 0 && D % 128 == 0);
+    const int64_t Sp = (S + 127) / 128 * 128;
+    const int64_t bytes[6] = {B * S * D, B * S * D, B * D * Sp, B * S * (D / 32), B * S * (D / 32), B * D * (Sp / 32)};
     int64_t o = 0;
-    l.qq = o; o += up256(B * S * D);
-    l.kq = o; o += up256(B * S * D);
-    l.vt = o; o += up256(B * D * l.Sp);
-    l.qs = o; o += up256(B * S * (D / 32));
-    l.ks = o; o += up256(B * S * (D / 32));
-    l.vs = o; o += up256(B * D * (l.Sp / 32));
-    l.total = o;
-    return l;
+    for (int i = 0; i < 6; ++i) {
+        out[i] = o;
+        o += (bytes[i] + 255) / 256 * 256;
+    }
+    out[6] = o;
+    out[7] = Sp;
+    return DRN_OK;
 }
-}  // namespace
 
 extern "C" int64_t drn_dit_forward_mx_attn_bytes(int64_t B, int64_t S, int64_t D) {
-    if (B <= 0 || S <= 0 || D <= 0 || D % 128) return 0;
-    return mx_attn_layout(B, S, D).total;
+    int64_t l[8];
+    return drn_dit_forward_mx_attn_layout(B, S, D, l) == DRN_OK ? l[6] : 0;
 }
 
 extern "C" int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden) {
@@ -289,174 +208,266 @@ extern "C" int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S,
 extern "C" int64_t drn_dit_forward_args_bytes(void) { return (int64_t)sizeof(drn_dit_forward_args); }
 extern "C" int64_t drn_dit_sub_bytes(void) { return (int64_t)sizeof(drn_dit_sub); }
 
-extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
+// ---- the sequencer
+// launch decisions that change a summation order come from the rows of ONE clip (batch-invariant results): rows_per_batch where
+// M is whole clips of it, else M
+static int64_t clip_rows(int64_t M, int64_t rows_per_batch) {
+    return (rows_per_batch > 0 && rows_per_batch < M && M % rows_per_batch == 0) ? rows_per_batch : M;
+}
+
+namespace {
+struct MxPtr {                                           // an MXFP8 matrix: elements | scales (q == NULL: none)
+    void* q;
+    void* s;
+};
+
+// C [M, N] = epi(A [M, K] . W [N, K]^T), every operand contiguous (lda = K, ldc = ldr = N).  Filled by name at the call sites
+// (designated initialisers); a field left out is NULL / false
+struct Linear {
+    const void* a;                                       // A as bf16 ...
+    MxPtr a_mx;                                          // ... or (precision 1) written as MX by its producer already: `a` is not read
+    const void* w;
+    const void* sw;                                      // precision 1: the E8M0 scales of w
+    void* c;                                             // C as bf16 ...
+    MxPtr c_mx;                                          // ... or (MLP-up of an mx_fused forward) as MX, where that entry has a kernel
+    int64_t M, N, K;
+    int epi;
+    const void* gate;
+    const void* residual;
+    // a split-K product with the gated-residual epilogue may stop after its slices: the next LayerNorm pass folds sum + epilogue
+    // in (drn_splitk_gate_res_ln_modulate: the same bits).  The per-launch host path never defers; the tests compare the two.
+    bool may_defer;
+};
+
+struct Forward {
+    const drn_dit_forward_args* a;
+    void* stream;
+    int64_t M;                                           // B S rows
+    int64_t al[8];                                       // attn_precision 1: drn_dit_forward_mx_attn_layout
+    const bf16_t* pending;                               // the broadcast cross-attention residual not yet added to X
+    int deferred;                                        // > 0: X still lacks sum(partials) + gate/residual of the last linear
+    const bf16_t* deferred_gate;
+
+    drn_timer* timer() const { return (drn_timer*)a->timer; }
+    bool defers(const Linear& l) const {
+        return l.may_defer && l.epi == DRN_EPI_GATE_RES && l.N == a->D && l.N > 1024 && l.residual == l.c;
+    }
+
+    // LayerNorm + modulate of X into H, folding a deferred split-K epilogue in.  mx_out (mx_fused, in front of a FA / MLP
+    // sub-block): the result goes to AQ | AS as MXFP8 [M, D] instead (H is not written): the q|k|v / MLP-up linear reads it there.
+    int ln_next(const bf16_t* shift, const bf16_t* scale, bool mx_out) {
+        const int64_t D = a->D, S = a->S;
+        int rc;
+        if (deferred && mx_out)
+            rc = drn_splitk_gate_res_ln_modulate_mx(a->gemm_ws, deferred, a->X, deferred_gate, pending, shift, scale, nullptr, a->AQ,
+                                                    a->AS, M, D, S, a->eps, stream);
+        else if (deferred)
+            rc = drn_splitk_gate_res_ln_modulate(a->gemm_ws, deferred, a->X, deferred_gate, pending, shift, scale, a->H, M, D, S, a->eps,
+                                                 stream);
+        else if (mx_out)
+            rc = drn_ln_modulate_mx(a->X, pending, shift, scale, nullptr, a->AQ, a->AS, M, D, S, a->eps, stream);
+        else
+            rc = drn_ln_modulate(a->X, pending, shift, scale, a->H, M, D, S, a->eps, stream);
+        deferred = 0;
+        pending = nullptr;
+        return rc;
+    }
+
+    // out = epi(A . W^T) exactly as native.gemm dispatches it: split-K for few-token products
+    int linear_bf16(const Linear& l) {
+        const int64_t M = l.M, N = l.N, K = l.K, rpb = a->S, ldr = l.residual ? N : 0;
+        const int64_t Mb = clip_rows(M, rpb);
+        const int splits = Mb <= 1024 ? drn_gemm_splitk_choice(Mb, N, K) : 1;
+        Scope sc(timer(), 0, 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N * (l.residual ? 2 : 1)), (hipStream_t)stream);
+        if (splits > 1 && defers(l)) {
+            deferred = splits;
+            deferred_gate = (const bf16_t*)l.gate;
+            return drn_gemm_bf16_splitk_partials(l.a, l.w, M, N, K, K, K, rpb, splits, a->gemm_ws, stream);
+        }
+        if (splits > 1)
+            return drn_gemm_bf16_splitk(l.a, l.w, l.c, M, N, K, K, K, N, l.epi, l.gate, l.residual, ldr, rpb, splits, a->gemm_ws, stream);
+        return drn_gemm_bf16(l.a, l.w, l.c, M, N, K, K, K, N, l.epi, l.gate, l.residual, ldr, rpb, stream);
+    }
+
+    // The same for a block linear of a precision-1 (MXFP8) forward: quantise A into AQ | AS unless its producer wrote it as MX,
+    // then the MXFP8 product chosen as native.gemm_mxfp8 chooses it (drn_gemm_mxfp8_splitk_choice): drn_gemm_mxfp8 (0), the fused
+    // few-token kernel (1) or its K slices (> 1).  With c_mx the GELU result leaves as MX through drn_gemm_mxfp8_gelu_mx where that
+    // entry has a kernel (*c_is_mx = true), else as bf16 into c (the consumer quantises by launch, the same bytes).
+    int linear_mx(const Linear& l, bool* c_is_mx) {
+        const int64_t M = l.M, N = l.N, K = l.K, rpb = a->S, ldr = l.residual ? N : 0;
+        MxPtr A = l.a_mx;
+        if (!A.q) {
+            DRN_TRY(drn_mx_quant_bf16(l.a, M, K, K, a->AQ, a->AS, stream));
+            A = {a->AQ, a->AS};
+        }
+        const int splits = drn_gemm_mxfp8_splitk_choice(clip_rows(M, rpb), N, K);
+        Scope sc(timer(), 0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (l.residual ? 2 : 1), (hipStream_t)stream);
+        if (c_is_mx) *c_is_mx = l.c_mx.q && l.epi == DRN_EPI_GELU && splits <= 1;
+        if (c_is_mx && *c_is_mx) return drn_gemm_mxfp8_gelu_mx(A.q, A.s, l.w, l.sw, l.c_mx.q, l.c_mx.s, M, N, K, rpb, stream);
+        if (splits == 0) return drn_gemm_mxfp8(A.q, A.s, l.w, l.sw, l.c, M, N, K, N, l.epi, l.gate, l.residual, ldr, rpb, stream);
+        if (splits > 1 && defers(l)) {
+            deferred = splits;
+            deferred_gate = (const bf16_t*)l.gate;
+            return drn_gemm_mxfp8_splitk_partials(A.q, A.s, l.w, l.sw, M, N, K, rpb, splits, a->gemm_ws, stream);
+        }
+        return drn_gemm_mxfp8_splitk(A.q, A.s, l.w, l.sw, l.c, M, N, K, N, l.epi, l.gate, l.residual, ldr, rpb, splits, a->gemm_ws, stream);
+    }
+
+    // a block linear in the precision of the forward
+    int linear(const Linear& l, bool* c_is_mx = nullptr) { return a->precision == 1 ? linear_mx(l, c_is_mx) : linear_bf16(l); }
+
+    // The self-attention of a sub-block on q | k | v in QKV (row stride 3D): norm + RoPE, then ONE walk of the plan.
+    // mx_ops: MXFP8 attention - q and k leave norm + RoPE as MX, v is transposed and quantised along the keys (all into mx_attn),
+    // then the block-scaled kernels; else the bf16 kernels on QKV.  o_mx: the output goes to AQ | AS as MX (O is not written; the
+    // q|k|v GEMM that read them has finished in stream order), else to O as bf16.  Split keys: the same partials and combine pass.
+    int self_attention(const drn_dit_sub* sb, bool mx_ops, bool o_mx) {
+        const int64_t S = a->S, D = a->D, ld = 3 * D, bs = S * 3 * D;
+        const int B = (int)a->B, heads = a->heads;
+        const float sm_scale = (float)(1.0 / sqrt(128.0));      // the double -> float conversion of the host wrapper (native.attention)
+        bf16_t* q = (bf16_t*)a->QKV;
+        bf16_t* k = q + D;
+        bf16_t* v = q + 2 * D;
+        uint8_t *mxa = nullptr, *kq = nullptr, *vt = nullptr, *ks = nullptr, *vs = nullptr;      // MX operands: mx_ops only
+        if (mx_ops) {
+            mxa = (uint8_t*)a->mx_attn;
+            kq = mxa + al[1], vt = mxa + al[2], ks = mxa + al[4], vs = mxa + al[5];
+            DRN_TRY(drn_qk_norm_rope_mx(q, k, sb->qn, sb->kn, a->cos, a->sin, mxa + al[0], mxa + al[3], kq, ks, M, heads, ld, ld, S, 0,
+                                        a->eps, 0, stream));
+            DRN_TRY(drn_mx_quant_vt(v, vt, vs, B, heads, S, ld, bs, stream));
+        } else {
+            DRN_TRY(drn_qk_norm_rope(q, k, sb->qn, sb->kn, a->cos, a->sin, M, heads, ld, ld, S, 0, a->eps, stream));
+        }
+        Scope sc(timer(), 1, 4.0 * B * heads * S * S * 128, (mx_ops ? 1.0 : 2.0) * B * heads * 128 * (4.0 * S), (hipStream_t)stream);
+        int64_t plan[6];
+        const int n = drn_attention_plan(heads, S, S, plan);
+        for (int p = 0; p < n; ++p) {
+            // a launch over the queries [q0, q0 + nq) of every clip: q, O and the MX rows advance by q0 rows
+            const int64_t q0 = plan[3 * p], nq = plan[3 * p + 1] - q0;
+            const int ns = (int)plan[3 * p + 2];
+            bf16_t* o = o_mx ? nullptr : (bf16_t*)a->O + q0 * D;
+            uint8_t* oq = o_mx ? (uint8_t*)a->AQ + q0 * D : nullptr;
+            uint8_t* os = o_mx ? (uint8_t*)a->AS + q0 * (D / 32) : nullptr;
+            if (mx_ops) {
+                const uint8_t* qq = mxa + al[0] + q0 * D;
+                const uint8_t* qs = mxa + al[3] + q0 * (D / 32);
+                DRN_TRY(ns > 1 ? drn_attention_splitkv_mxfp8(qq, qs, kq, ks, vt, vs, o, oq, os, B, heads, nq, S, S, S, D, S * D, sm_scale, ns,
+                                                             a->attn_ws, stream)
+                               : drn_attention_mxfp8(qq, qs, kq, ks, vt, vs, o, oq, os, B, heads, nq, S, S, S, D, S * D, sm_scale, stream));
+            } else if (o_mx) {
+                DRN_TRY(ns > 1 ? drn_attention_splitkv_bf16_mx(q + q0 * ld, k, v, nullptr, oq, os, B, heads, nq, S, ld, ld, ld, D, bs, bs, bs,
+                                                               S * D, sm_scale, ns, a->attn_ws, stream)
+                               : drn_attention_bf16_mx(q + q0 * ld, k, v, nullptr, oq, os, B, heads, nq, S, ld, ld, ld, D, bs, bs, bs, S * D,
+                                                       sm_scale, stream));
+            } else {
+                DRN_TRY(ns > 1 ? drn_attention_splitkv_bf16(q + q0 * ld, k, v, o, B, heads, nq, S, ld, ld, ld, D, bs, bs, bs, S * D, sm_scale,
+                                                            ns, a->attn_ws, stream)
+                               : drn_attention_bf16(q + q0 * ld, k, v, o, B, heads, nq, S, ld, ld, ld, D, bs, bs, bs, S * D, sm_scale, stream));
+            }
+        }
+        return DRN_OK;
+    }
+};
+
+// every argument and workspace check of a forward: nothing is enqueued before this returns DRN_OK
+int validate(const drn_dit_forward_args* a, int64_t al[8]) {
     DRN_CHECK_ARG(a && a->struct_bytes == (int64_t)sizeof(drn_dit_forward_args));
     DRN_CHECK_ARG(a->S > 0 && a->B > 0 && a->D > 0 && a->heads > 0 && a->D == (int64_t)a->heads * 128 && a->hidden > 0);
     DRN_CHECK_ARG(a->n_sub >= 0 && (a->n_sub == 0 || a->subs) && a->X && a->H && a->QKV && a->O && a->U && a->Y);
     DRN_CHECK_ARG(a->P && a->w_patch && a->w_final && a->final_shift && a->final_scale && a->shift && a->scale && a->gate);
-    const int64_t S = a->S, B = a->B, D = a->D, M = B * S;
+    const int64_t S = a->S, B = a->B, D = a->D;
     DRN_CHECK_ARG(a->precision == 0 || a->precision == 1);
-    if (a->precision == 1) {                             // everything the MXFP8 block linears need, before anything is launched
+    // the split-K slices of every linear this forward runs (patch embed and final layer are bf16 in either precision)
+    int64_t need = drn_dit_forward_gemm_workspace_bytes(B, S, D, a->hidden, a->n_final, a->kpad);
+    if (a->precision == 1) {
         DRN_CHECK_ARG(D % 256 == 0 && a->hidden % 256 == 0 && a->AQ && a->AS);
         DRN_CHECK_ARG(a->act_bytes >= drn_dit_forward_mx_act_bytes(B, S, D, a->hidden));
-        const int64_t need = drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, a->hidden);
-        DRN_CHECK_ARG(need == 0 || (a->gemm_ws && a->gemm_ws_bytes >= need));
-        for (int i = 0; i < a->n_sub; ++i)
-            if (a->subs[i].kind == DRN_SUB_FA || a->subs[i].kind == DRN_SUB_MLP)
-                DRN_CHECK_ARG(a->subs[i].w_a && a->subs[i].w_b && a->subs[i].s_a && a->subs[i].s_b);
+        const int64_t ends[3] = {bf16_splitk_bytes(B, S, D, a->kpad), bf16_splitk_bytes(B, S, a->n_final, D),
+                                 drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, a->hidden)};
+        need = ends[0];
+        for (int i = 1; i < 3; ++i) need = ends[i] > need ? ends[i] : need;
     }
+    DRN_CHECK_ARG(need == 0 || (a->gemm_ws && a->gemm_ws_bytes >= need));
     DRN_CHECK_ARG(a->mx_fused == 0 || (a->mx_fused == 1 && a->precision == 1));
-    const bool mxf = a->mx_fused == 1;                   // producers write the quantised operand of the next block linear themselves
-    if (mxf) DRN_CHECK_ARG(a->UQ && a->US && a->u_act_bytes >= drn_dit_forward_mx_u_bytes(B, S, a->hidden));
+    if (a->mx_fused) DRN_CHECK_ARG(a->UQ && a->US && a->u_act_bytes >= drn_dit_forward_mx_u_bytes(B, S, a->hidden));
     DRN_CHECK_ARG(a->attn_precision == 0 || a->attn_precision == 1);
-    const bool amx = a->attn_precision == 1;             // MXFP8 self-attention (either precision of the block linears)
-    const MxAttnLayout al = mx_attn_layout(B, S, D);
-    if (amx) DRN_CHECK_ARG(a->mx_attn && ((uintptr_t)a->mx_attn & 255) == 0 && a->mx_attn_bytes >= al.total);
-    uint8_t* const mxa = (uint8_t*)a->mx_attn;
-    const bf16_t* shift = (const bf16_t*)a->shift;
-    const bf16_t* scale = (const bf16_t*)a->scale;
-    const bf16_t* gate = (const bf16_t*)a->gate;
-    const float sm_scale = (float)(1.0 / sqrt(128.0));      // the double -> float conversion of the host wrapper (native.attention)
-
-    // patch embedding (CleanGeneralDIT.py:386/:417): X = P . w_patch^T
-    DRN_TRY(fwd_gemm(a, a->P, a->w_patch, a->X, M, D, a->kpad, a->kpad, D, DRN_EPI_NONE, nullptr, nullptr, 0, stream));
-
-    const bf16_t* pending = nullptr;                     // the broadcast cross-attention residual not yet added to X
-    int deferred = 0;                                    // > 0: X still lacks sum(partials) + gate/residual of the last linear
-    const bf16_t* deferred_gate = nullptr;
-    static int fuse = -1;
-    if (fuse < 0) {
-        const char* e = getenv("DRN_FUSE_SPLITK_LN");    // 0: the split-K epilogue and the LayerNorm as two launches (A/B runs)
-        fuse = (e && e[0] == '0') ? 0 : 1;
+    if (a->attn_precision == 1) {
+        DRN_TRY(drn_dit_forward_mx_attn_layout(B, S, D, al));
+        DRN_CHECK_ARG(a->mx_attn && ((uintptr_t)a->mx_attn & 255) == 0 && a->mx_attn_bytes >= al[6]);
     }
-    // LayerNorm + modulate of X into H, folding a deferred split-K epilogue in.  MXOUT (mx_fused, in front of a FA / MLP
-    // sub-block): the result goes to AQ | AS as MXFP8 [M, D] instead (H is not written): the q|k|v / MLP-up linear reads it there.
-#define LN_NEXT(SH, SC, MXOUT)                                                                                        \
-    do {                                                                                                              \
-        if (deferred) {                                                                                               \
-            if (MXOUT)                                                                                                \
-                DRN_TRY(drn_splitk_gate_res_ln_modulate_mx(a->gemm_ws, deferred, a->X, deferred_gate, pending, SH, SC, nullptr,   \
-                                                           a->AQ, a->AS, M, D, S, a->eps, stream));                   \
-            else                                                                                                      \
-                DRN_TRY(drn_splitk_gate_res_ln_modulate(a->gemm_ws, deferred, a->X, deferred_gate, pending, SH, SC, a->H, M, D,   \
-                                                        S, a->eps, stream));                                          \
-            deferred = 0;                                                                                             \
-        } else if (MXOUT) {                                                                                           \
-            DRN_TRY(drn_ln_modulate_mx(a->X, pending, SH, SC, nullptr, a->AQ, a->AS, M, D, S, a->eps, stream));       \
-        } else {                                                                                                      \
-            DRN_TRY(drn_ln_modulate(a->X, pending, SH, SC, a->H, M, D, S, a->eps, stream));                           \
-        }                                                                                                             \
-        pending = nullptr;                                                                                            \
-    } while (0)
-    const void* hq = mxf ? a->AQ : nullptr;              // the MX operand LN_NEXT left for q|k|v / MLP-up
-    const void* hs = mxf ? a->AS : nullptr;
+    bool any_fa = false;
     for (int i = 0; i < a->n_sub; ++i) {
         const drn_dit_sub* sb = &a->subs[i];
-        const bf16_t* sh = shift + (int64_t)sb->site * a->shift_site_stride;
-        const bf16_t* sc = scale + (int64_t)sb->site * a->scale_site_stride;
-        const bf16_t* gt = gate + (int64_t)sb->site * a->gate_site_stride;
+        DRN_CHECK_ARG(sb->kind == DRN_SUB_FA || sb->kind == DRN_SUB_CA || sb->kind == DRN_SUB_MLP);
         if (sb->kind == DRN_SUB_CA) {
             DRN_CHECK_ARG(a->addvec && sb->ca_index >= 0);
-            if (pending) {
-                // two cross-attention blocks in a row (not in FA-CA-MLP): X must be complete before the stand-alone add
-                if (deferred) {
-                    DRN_TRY(drn_splitk_gate_res_ln_modulate(a->gemm_ws, deferred, a->X, deferred_gate, nullptr, sh, sc, a->H, M, D, S,
-                                                            a->eps, stream));       // (H is scratch here)
-                    deferred = 0;
-                }
-                DRN_TRY(drn_bcast_add(a->X, pending, M, D, S, stream));
-            }
-            pending = (const bf16_t*)a->addvec + (int64_t)sb->ca_index * a->addvec_stride;
             continue;
         }
-        LN_NEXT(sh, sc, mxf);
+        DRN_CHECK_ARG(sb->w_a && sb->w_b && (a->precision == 0 || (sb->s_a && sb->s_b)));
         if (sb->kind == DRN_SUB_FA) {
-            DRN_CHECK_ARG(sb->w_a && sb->w_b && sb->qn && sb->kn && a->cos && a->sin);
-            bf16_t* q = (bf16_t*)a->QKV;
-            bf16_t* k = q + D;
-            bf16_t* v = q + 2 * D;
-            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->QKV, M, 3 * D, D, DRN_EPI_NONE, nullptr, nullptr, stream, nullptr, hq, hs));
-            // mx_fused: attention writes O as MX into AQ | AS (the q|k|v GEMM that read them has finished in stream order);
+            DRN_CHECK_ARG(sb->qn && sb->kn && a->cos && a->sin);
+            any_fa = true;
+        }
+    }
+    if (any_fa) {                                        // the split-KV partials of the plan's split launch
+        const int64_t att = drn_dit_forward_attn_workspace_bytes(B, a->heads, S);
+        DRN_CHECK_ARG(att == 0 || (a->attn_ws && a->attn_ws_bytes >= att));
+    }
+    return DRN_OK;
+}
+}  // namespace
+
+extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
+    Forward f = {};
+    DRN_TRY(validate(a, f.al));
+    f.a = a;
+    f.stream = stream;
+    const int64_t D = a->D, M = f.M = a->B * a->S;
+    const bool mxf = a->mx_fused == 1;                   // producers write the quantised operand of the next block linear themselves
+    const MxPtr none = {nullptr, nullptr}, act = {a->AQ, a->AS}, uact = {a->UQ, a->US};
+    const MxPtr h_mx = mxf ? act : none;                 // the MX operand ln_next leaves for q|k|v / MLP-up
+
+    // patch embedding (CleanGeneralDIT.py:386/:417): X = P . w_patch^T
+    DRN_TRY(f.linear_bf16({.a = a->P, .w = a->w_patch, .c = a->X, .M = M, .N = D, .K = a->kpad, .epi = DRN_EPI_NONE}));
+
+    for (int i = 0; i < a->n_sub; ++i) {
+        const drn_dit_sub* sb = &a->subs[i];
+        const bf16_t* sh = (const bf16_t*)a->shift + (int64_t)sb->site * a->shift_site_stride;
+        const bf16_t* sc = (const bf16_t*)a->scale + (int64_t)sb->site * a->scale_site_stride;
+        const bf16_t* gt = (const bf16_t*)a->gate + (int64_t)sb->site * a->gate_site_stride;
+        if (sb->kind == DRN_SUB_CA) {
+            if (f.pending) {
+                // two cross-attention blocks in a row (not in FA-CA-MLP): X must be complete before the stand-alone add
+                if (f.deferred) {
+                    DRN_TRY(drn_splitk_gate_res_ln_modulate(a->gemm_ws, f.deferred, a->X, f.deferred_gate, nullptr, sh, sc, a->H, M, D,
+                                                            a->S, a->eps, stream));       // (H is scratch here)
+                    f.deferred = 0;
+                }
+                DRN_TRY(drn_bcast_add(a->X, f.pending, M, D, a->S, stream));
+            }
+            f.pending = (const bf16_t*)a->addvec + (int64_t)sb->ca_index * a->addvec_stride;
+            continue;
+        }
+        DRN_TRY(f.ln_next(sh, sc, mxf));
+        if (sb->kind == DRN_SUB_FA) {
+            DRN_TRY(f.linear({.a = a->H, .a_mx = h_mx, .w = sb->w_a, .sw = sb->s_a, .c = a->QKV, .M = M, .N = 3 * D, .K = D,
+                              .epi = DRN_EPI_NONE}));
             // the 32x32x16 body has no MX epilogue: that site keeps bf16 O + the quantise launch (the same bytes)
-            const bool amx_site = amx && drn_attention_mxfp8_choice(a->heads, S) == 1;      // from ONE clip's tokens
-            const bool omx = mxf && (amx_site || drn_attention_mx_available());
-            if (amx_site) {
-                // MXFP8 attention: q and k leave norm + RoPE as MX, v is transposed and quantised along the keys, then the same
-                // plan on the block-scaled kernels (split keys: the same partials and combine pass)
-                DRN_TRY(drn_qk_norm_rope_mx(q, k, sb->qn, sb->kn, a->cos, a->sin, mxa + al.qq, mxa + al.qs, mxa + al.kq, mxa + al.ks, M,
-                                            a->heads, 3 * D, 3 * D, S, 0, a->eps, 0, stream));
-                DRN_TRY(drn_mx_quant_vt(v, mxa + al.vt, mxa + al.vs, (int)B, a->heads, S, 3 * D, S * 3 * D, stream));
-                Scope tsc((drn_timer*)a->timer, 1, 4.0 * B * a->heads * S * S * 128, 1.0 * B * a->heads * 128 * (4.0 * S), (hipStream_t)stream);
-                int64_t plan[6];
-                const int n = drn_attention_plan(a->heads, S, S, plan);
-                for (int p = 0; p < n; ++p) {
-                    const int64_t q0 = plan[3 * p], nq = plan[3 * p + 1] - q0;
-                    const int ns = (int)plan[3 * p + 2];
-                    const uint8_t* qqs = mxa + al.qq + q0 * D;
-                    const uint8_t* qss = mxa + al.qs + q0 * (D / 32);
-                    bf16_t* os = omx ? nullptr : (bf16_t*)a->O + q0 * D;
-                    uint8_t* oq = omx ? (uint8_t*)a->AQ + q0 * D : nullptr;
-                    uint8_t* osc = omx ? (uint8_t*)a->AS + q0 * (D / 32) : nullptr;
-                    if (ns > 1) {
-                        if (!a->attn_ws || drn_attention_splitkv_workspace_bytes((int)B, a->heads, nq, ns) > a->attn_ws_bytes) return DRN_EINVAL;
-                        DRN_TRY(drn_attention_splitkv_mxfp8(qqs, qss, mxa + al.kq, mxa + al.ks, mxa + al.vt, mxa + al.vs, os, oq, osc, (int)B,
-                                                            a->heads, nq, S, S, S, D, S * D, sm_scale, ns, a->attn_ws, stream));
-                    } else {
-                        DRN_TRY(drn_attention_mxfp8(qqs, qss, mxa + al.kq, mxa + al.ks, mxa + al.vt, mxa + al.vs, os, oq, osc, (int)B, a->heads,
-                                                    nq, S, S, S, D, S * D, sm_scale, stream));
-                    }
-                }
-            } else {
-            DRN_TRY(drn_qk_norm_rope(q, k, sb->qn, sb->kn, a->cos, a->sin, M, a->heads, 3 * D, 3 * D, S, 0, a->eps, stream));
-            {
-                Scope tsc((drn_timer*)a->timer, 1, 4.0 * B * a->heads * S * S * 128, 2.0 * B * a->heads * 128 * (4.0 * S), (hipStream_t)stream);
-                int64_t plan[6];
-                const int n = drn_attention_plan(a->heads, S, S, plan);
-                for (int p = 0; p < n; ++p) {
-                    const int64_t q0 = plan[3 * p], nq = plan[3 * p + 1] - q0;
-                    const int ns = (int)plan[3 * p + 2];
-                    const bf16_t* qs = q + q0 * 3 * D;
-                    bf16_t* os = (bf16_t*)a->O + q0 * D;
-                    uint8_t* oq = omx ? (uint8_t*)a->AQ + q0 * D : nullptr;
-                    uint8_t* osc = omx ? (uint8_t*)a->AS + q0 * (D / 32) : nullptr;
-                    if (ns > 1) {
-                        if (!a->attn_ws || drn_attention_splitkv_workspace_bytes((int)B, a->heads, nq, ns) > a->attn_ws_bytes) return DRN_EINVAL;
-                        if (omx)
-                            DRN_TRY(drn_attention_splitkv_bf16_mx(qs, k, v, nullptr, oq, osc, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D,
-                                                                  D, S * 3 * D, S * 3 * D, S * 3 * D, S * D, sm_scale, ns, a->attn_ws, stream));
-                        else
-                        DRN_TRY(drn_attention_splitkv_bf16(qs, k, v, os, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D, D, S * 3 * D,
-                                                           S * 3 * D, S * 3 * D, S * D, sm_scale, ns, a->attn_ws, stream));
-                    } else if (omx) {
-                        DRN_TRY(drn_attention_bf16_mx(qs, k, v, nullptr, oq, osc, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D, D, S * 3 * D,
-                                                      S * 3 * D, S * 3 * D, S * D, sm_scale, stream));
-                    } else {
-                        DRN_TRY(drn_attention_bf16(qs, k, v, os, (int)B, a->heads, nq, S, 3 * D, 3 * D, 3 * D, D, S * 3 * D, S * 3 * D,
-                                                   S * 3 * D, S * D, sm_scale, stream));
-                    }
-                }
-            }
-            }
-            DRN_TRY(fwd_lin(a, a->O, sb->w_b, sb->s_b, a->X, M, D, D, DRN_EPI_GATE_RES, gt, a->X, stream, fuse ? &deferred : nullptr,
-                            omx ? a->AQ : nullptr, omx ? a->AS : nullptr));
-            deferred_gate = gt;
-        } else if (sb->kind == DRN_SUB_MLP) {
-            DRN_CHECK_ARG(sb->w_a && sb->w_b);
+            const bool mx_ops = a->attn_precision == 1 && drn_attention_mxfp8_choice(a->heads, a->S) == 1;      // from ONE clip's tokens
+            const bool o_mx = mxf && (mx_ops || drn_attention_mx_available());
+            DRN_TRY(f.self_attention(sb, mx_ops, o_mx));
+            DRN_TRY(f.linear({.a = a->O, .a_mx = o_mx ? act : none, .w = sb->w_b, .sw = sb->s_b, .c = a->X, .M = M, .N = D, .K = D,
+                              .epi = DRN_EPI_GATE_RES, .gate = gt, .residual = a->X, .may_defer = true}));
+        } else {
             // mx_fused: MLP-up reads AQ | AS and writes U as MX into UQ | US (a second buffer: written while AQ is read) where the
             // GELU -> MX epilogue exists; a sliced MLP-up writes bf16 U and MLP-down quantises it by launch
-            int umx = 0;
-            DRN_TRY(fwd_lin(a, a->H, sb->w_a, sb->s_a, a->U, M, a->hidden, D, DRN_EPI_GELU, nullptr, nullptr, stream, nullptr, hq, hs,
-                            mxf ? a->UQ : nullptr, mxf ? a->US : nullptr, &umx));
-            DRN_TRY(fwd_lin(a, a->U, sb->w_b, sb->s_b, a->X, M, D, a->hidden, DRN_EPI_GATE_RES, gt, a->X, stream,
-                            fuse ? &deferred : nullptr, umx ? a->UQ : nullptr, umx ? a->US : nullptr));
-            deferred_gate = gt;
-        } else {
-            return DRN_EINVAL;
+            bool u_mx = false;
+            DRN_TRY(f.linear({.a = a->H, .a_mx = h_mx, .w = sb->w_a, .sw = sb->s_a, .c = a->U, .c_mx = mxf ? uact : none, .M = M,
+                              .N = a->hidden, .K = D, .epi = DRN_EPI_GELU}, &u_mx));
+            DRN_TRY(f.linear({.a = a->U, .a_mx = u_mx ? uact : none, .w = sb->w_b, .sw = sb->s_b, .c = a->X, .M = M, .N = D,
+                              .K = a->hidden, .epi = DRN_EPI_GATE_RES, .gate = gt, .residual = a->X, .may_defer = true}));
         }
     }
     // final layer (CleanGeneralDIT.py:583-590): LN + modulate with the first 2D of the LoRA vector, Linear(D -> n_final)
-    LN_NEXT((const bf16_t*)a->final_shift, (const bf16_t*)a->final_scale, false);
-#undef LN_NEXT
-    DRN_TRY(fwd_gemm(a, a->H, a->w_final, a->Y, M, a->n_final, D, D, a->n_final, DRN_EPI_NONE, nullptr, nullptr, 0, stream));
-    return DRN_OK;
+    DRN_TRY(f.ln_next((const bf16_t*)a->final_shift, (const bf16_t*)a->final_scale, false));
+    return f.linear_bf16({.a = a->H, .w = a->w_final, .c = a->Y, .M = M, .N = a->n_final, .K = D, .epi = DRN_EPI_NONE});
 }

@@ -98,6 +98,12 @@ __device__ __forceinline__ float wave_sum(float v) {
         if (!(cond)) return DRN_EINVAL; \
     } while (0)
 
+#define DRN_TRY(expr)                  \
+    do {                               \
+        const int rc_ = (expr);        \
+        if (rc_ != DRN_OK) return rc_; \
+    } while (0)
+
 static inline int drn_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? DRN_OK : (int)e;

@@ -15,6 +15,7 @@
 // Workgroup ids are remapped so that each XCD (own L2) walks a contiguous band of tiles, 8 tile-rows deep.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 
 #define BM 128
 #define BN 128
@@ -213,16 +214,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_kernel(const float* 
     }
 }
 
-// gemm256s.hip: 256x256x64 tile, streamed schedule (tile kernel 1; 3 and 4 are accepted as aliases by drn_gemm_force_tile)
-int drn_gemm256s_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
-                          int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,
-                          void* stream, const int64_t* blk);
-
-// gemm144.hip: 144x256x64 kernel (token bands of sequence parallelism: M = 2304 k)
-int drn_gemm144_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
-                         int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,
-                         void* stream, const int64_t* blk);
-
 // Tile choice by a wave-quantisation model (measured on MI355X).  Time unit = one 256^2 workgroup owning a CU for the whole
 // K loop.  128^2 workgroups run two per CU at ~1000 vs ~1300 TF/s: a full round of 512 takes ~0.65 units.  A 144x256
 // workgroup does 56 % of the work of a 256^2 one at 0.85-1.0x its rate: DRN_GEMM144_COST = 0.64 units (measured: M = 2304
@@ -233,9 +224,6 @@ int drn_gemm144_dispatch(const void* A, const void* W, void* C, int64_t M, int64
 static int g_force_tile = -1;
 extern "C" void drn_gemm_force_tile(int tile) { g_force_tile = tile; }
 static int tall_choice(int64_t M, int64_t N, int64_t K);          // few-token kernel (gemm_tall.hip), defined with the split-K rules
-int drn_gemm_tall_dispatch(const void* A, const void* W, void* C, float* partial, int64_t M, int64_t N, int64_t K, int64_t lda,
-                           int64_t ldw, int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr,
-                           int64_t rpb, int splits, void* stream);
 
 static int pick_gemm_tile(int64_t M, int64_t N, double* cost_out = nullptr) {
     static int mode256 = -1, mode144 = -1;
@@ -425,9 +413,6 @@ extern "C" int64_t drn_gemm_splitk_workspace_bytes(int64_t M, int64_t N, int spl
 // gemm_tall.hip: one clip of 256 tokens - a workgroup owns all 256 rows x 64 columns over the whole K (no slices where N / 64
 // workgroups fill the chip: QKV 192, MLP-up 256), or over a K slice (out-proj, MLP-down: 64 tiles x 4).  Returns the slice
 // count (1 = unsplit, fused epilogue), 0 = not this kernel.  DRN_GEMM_TALL=0 switches it off (A/B runs).
-int drn_gemm_tall_dispatch(const void* A, const void* W, void* C, float* partial, int64_t M, int64_t N, int64_t K, int64_t lda,
-                           int64_t ldw, int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr,
-                           int64_t rpb, int splits, void* stream);
 static int tall_choice(int64_t M, int64_t N, int64_t K) {
     static int mode = -1;
     if (mode < 0) {
@@ -458,9 +443,6 @@ static int splitk256_choice(int64_t M, int64_t N, int64_t K) {
         if (tiles * s <= 256 && (K / BK) % s == 0 && K / s >= 1024) best = s;
     return (best && tiles * best >= 192) ? best : 0;
 }
-
-int drn_gemm256s_partial(const void* A, const void* W, float* partial, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
-                         int splits, void* stream, bool wring_ok);
 
 extern "C" int drn_gemm_splitk_choice(int64_t M, int64_t N, int64_t K) {
     if (N % BN != 0 || K % BK != 0 || M <= 0) return 1;

@@ -13,6 +13,7 @@
 // one counted s_waitcnt vmcnt per K step.  XOR-swizzled rows as in gemm256s.hip.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 
 #define TM 144
 #define TN 256

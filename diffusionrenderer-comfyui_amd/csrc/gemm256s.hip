@@ -42,6 +42,7 @@
 // wave -> quadrant map and blocked operand layouts: gemm256s_core.h.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 
 // G256S_ABL: timing-only ablations (results WRONG; shipped with 0): 8 = no epilogue math / stores, 64 = no gate / residual loads,
 // 128 = no C stores (16 / 32: the hand-over waits, gemm256s_core.h)

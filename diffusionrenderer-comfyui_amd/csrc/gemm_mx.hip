@@ -17,6 +17,7 @@
 // the 16x16 shape (col = lane & 15, row = 4 * (lane >> 4) + r) then gives a lane 4 consecutive output COLUMNS of one row.
 #include <type_traits>
 #include "drn_common.h"
+#include "drn_launchers.h"
 #include "mx_quant.h"
 
 namespace {

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "drn_common.h"
+#include "drn_launchers.h"
 #include "mx_quant.h"
 
 namespace {
@@ -303,10 +304,6 @@ bool shape_ok(int64_t M, int64_t N, int64_t K, int64_t rpb, int splits) {
 
 }  // namespace
 
-// gemm.hip: sum of fp32 slices [splits][M][N] + epilogue (gemm_splitk_epilogue_kernel)
-int drn_gemm_splitk_reduce(const void* workspace, int splits, void* C, int64_t M, int64_t N, int64_t ldc, int epilogue,
-                           const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch, void* stream);
-
 extern "C" int drn_gemm_mxfp8_force_small_m(int on) {
     const int was = small_m_on();
     if (on >= 0) g_small_m = on ? 1 : 0;
@@ -369,10 +366,6 @@ extern "C" int drn_gemm_mxfp8_splitk(const void* A, const void* SA, const void* 
         default: return launch<DRN_EPI_GATE_RES>(a);
     }
 }
-
-// gemm_mx.hip: the 256 x 256 kernel with the GELU -> MX epilogue
-int drn_gemm_mx_gelu_mx_launch(const void* A, const void* SA, const void* W, const void* SW, void* CQ, void* CS, int64_t M, int64_t N,
-                               int64_t K, void* stream);
 
 // MLP-up with the quantise launch folded in: CQ | CS = drn_mx_quant_bf16(what DRN_EPI_GELU writes), bit for bit (drn.h)
 extern "C" int drn_gemm_mxfp8_gelu_mx(const void* A, const void* SA, const void* W, const void* SW, void* CQ, void* CS, int64_t M,

@@ -29,6 +29,7 @@
 // TM + TN at TM x TN = 16 384 outputs per workgroup.
 #include <stdlib.h>
 #include "drn_common.h"
+#include "drn_launchers.h"
 
 #define BK 64
 #define EPI_PARTIAL 3                      // internal: fp32 slice [blockIdx.y][M][N] to the workspace

@@ -21,6 +21,8 @@ token-local except self-attention.  There the ranks trade token bands for heads 
 attends over ALL tokens of heads/world heads) and trade back afterwards; when the world size does not divide the
 head count, K/V rows (after RMSNorm + RoPE) are all-gathered instead (parallel.py).
 """
+import ctypes
+import math
 from typing import Dict, Optional
 
 import torch
@@ -116,7 +118,6 @@ class HipDiT:
         self._time_cache = {}
         self._ctx_cache = {}
         self._ws = {}
-        self._graphs = {}
         self._mx_act = {}          # mxfp8: (rows, K) -> MxTensor, the quantised A operand of the next block linear
         self.trace = None          # tests: dict filled with per-sub-block activations "block{i}.{j}" -> [S, D]
         # DRN_PER_LAUNCH=1: one ctypes call per kernel (the path the sharded engine and the traces use) instead of the
@@ -311,19 +312,16 @@ class HipDiT:
                         ws["uact_q_bytes"] = n * ws["u"].shape[1]
                 ws["gemm_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-K partials (few tokens)
                 if self._amx:
-                    # MXFP8 attention: QQ | KQ | VT | QS | KS | VS in one buffer, laid out as drn_dit_forward reads it (drn.h)
-                    buf = torch.empty(lib.drn_dit_forward_mx_attn_bytes(B, S, D), dtype=torch.uint8, device=dev)
-                    Sp = (S + 127) // 128 * 128
-                    f8, up, off, views = torch.float8_e4m3fn, (lambda v: (v + 255) // 256 * 256), 0, []
-                    for nbytes, shape, dt in ((n * D, (n, D), f8), (n * D, (n, D), f8), (B * D * Sp, (B, self.heads, 128, Sp), f8),
-                                              (n * D // 32, (n, D // 32), None), (n * D // 32, (n, D // 32), None),
-                                              (B * D * Sp // 32, (B, self.heads, 128, Sp // 32), None)):
-                        v = buf[off:off + nbytes]
-                        views.append((v.view(dt) if dt is not None else v).view(shape))
-                        off += up(nbytes)
-                    assert off == buf.numel()
+                    # MXFP8 attention: QQ | KQ | VT | QS | KS | VS in one buffer, at the offsets drn_dit_forward reads them (drn.h)
+                    lay = (ctypes.c_int64 * 8)()
+                    N._check(lib.drn_dit_forward_mx_attn_layout(B, S, D, lay), "drn_dit_forward_mx_attn_layout")
+                    buf = torch.empty(lay[6], dtype=torch.uint8, device=dev)
+                    Sp = lay[7]
+                    shapes = ((n, D), (n, D), (B, self.heads, 128, Sp), (n, D // 32), (n, D // 32), (B, self.heads, 128, Sp // 32))
+                    views = [buf[off:off + math.prod(shape)].view(shape) for off, shape in zip(lay, shapes)]
+                    qq, kq, vt = (v.view(torch.float8_e4m3fn) for v in views[:3])
                     ws["mx_attn"] = buf
-                    ws["mx_attn_views"] = (N.MxTensor(views[0], views[3]), N.MxTensor(views[1], views[4]), views[2], views[5])
+                    ws["mx_attn_views"] = (N.MxTensor(qq, views[3]), N.MxTensor(kq, views[4]), vt, views[5])
                 nb = lib.drn_dit_forward_attn_workspace_bytes(B, self.heads, S)
                 ws["attn_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-KV partials
             elif self.exchange == "a2a":
@@ -401,46 +399,7 @@ class HipDiT:
             else:
                 cv = torch.stack([self.context_vectors(c) for c in cis], 1)       # [n_ca, B, D]
                 addvec = (gates.unsqueeze(1) * cv).contiguous()
-        if self._graphable(S, world) and B == 1:
-            return self._graph_forward(x, cond, mod, modf, addvec, Tp, Hp, Wp)
         return self._run(x, cond, mod, modf, addvec, Tp, Hp, Wp, plan)
-
-    # ------------------------------------------------------------------ hipGraph replay for launch-bound (small) shapes
-    def _graphable(self, S, world) -> bool:
-        """Replay the ~300 launches of a small-shape forward as one hipGraph (DRN_GRAPHS=1).  Measured: no gain - even at
-        S = 256 the eager launches run ahead of the GPU once nothing synchronises inside the denoising loop."""
-        import os
-        return (self.exchange == "none" and S <= 4096 and self.trace is None and N._TIMER is None
-                and os.environ.get("DRN_GRAPHS", "0") == "1")     # opt-in: measured null on MI355X (13.64 vs 13.66 ms at S=256)
-
-    def _graph_forward(self, x, cond, mod, modf, addvec, Tp, Hp, Wp):
-        key = (tuple(x.shape), tuple(cond.shape), addvec is not None)
-        ent = self._graphs.get(key)
-        if ent is None:
-            st = {"x": x.clone(), "cond": cond.clone(), "mod": mod.clone(), "modf": modf.clone(),
-                  "addvec": addvec.clone() if addvec is not None else None}
-            plan = ShardPlan(Tp * Hp * Wp, 0, 1)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                        # warm-up outside capture (workspaces, code objects)
-                self._run(st["x"], st["cond"], st["mod"], st["modf"], st["addvec"], Tp, Hp, Wp, plan)
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self._run(st["x"], st["cond"], st["mod"], st["modf"], st["addvec"], Tp, Hp, Wp, plan)
-            ent = (g, st, out)
-            if len(self._graphs) >= 4:
-                self._graphs.clear()
-            self._graphs[key] = ent
-        g, st, out = ent
-        st["x"].copy_(x)
-        st["cond"].copy_(cond)
-        st["mod"].copy_(mod)
-        st["modf"].copy_(modf)
-        if addvec is not None:
-            st["addvec"].copy_(addvec)
-        g.replay()
-        return out.clone()                                       # the graph's output buffer is reused by the next replay
 
     @staticmethod
     def _mx_view(buf, q_bytes, rows, K):
@@ -540,14 +499,96 @@ class HipDiT:
             N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=O.unsqueeze(0), heads=self.heads)
         N.gemm(O, sb["wo"], out=X, epilogue=N.EPI_GATE_RES, gate=gate, residual=X)
 
+    def _sequencer_args(self, ws, P, S, B, *, mod, modf, batched, addvec, rope):
+        """The argument block of drn_dit_forward for this workspace (raw pointers: the caller keeps every tensor alive).
+        mod / modf: the AdaLN tables of one sigma; batched: None for one clip, else their per-clip expansions (modB, modfB, gateB)
+        of _run; rope: (cos, sin)."""
+        D = self.D
+        X, Hb, O, U, Y = ws["x"], ws["h"], ws["o"], ws["u"], ws["y"]
+        a = N.DitForwardArgs()
+        a.S, a.B, a.D, a.hidden, a.heads = S, B, D, U.shape[1], self.heads
+        a.n_sub, a.subs = len(self._subs_c), self._subs_c
+        if B == 1:
+            a.shift, a.scale, a.gate = mod.data_ptr(), mod.data_ptr() + 2 * D, mod.data_ptr() + 4 * D
+            assert mod.stride(1) == 1
+            a.shift_site_stride = a.scale_site_stride = a.gate_site_stride = mod.stride(0)    # (rows of a batched sigma table)
+            a.final_shift, a.final_scale = modf.data_ptr(), modf.data_ptr() + 2 * D
+        else:
+            modB, modfB, gateB = batched
+            a.shift, a.scale, a.gate = modB.data_ptr(), modB.data_ptr() + 2 * B * D, gateB.data_ptr()
+            a.shift_site_stride = a.scale_site_stride = 2 * B * D
+            a.gate_site_stride = B * D
+            a.final_shift, a.final_scale = modfB.data_ptr(), modfB.data_ptr() + 2 * B * D
+        if addvec is not None:
+            a.addvec, a.addvec_stride = addvec.data_ptr(), addvec[0].numel()
+        a.cos, a.sin = rope[0].data_ptr(), rope[1].data_ptr()
+        a.P, a.kpad, a.w_patch = P.data_ptr(), self.kpad, self.w_patch.data_ptr()
+        a.w_final, a.n_final = self.w_final.data_ptr(), self.w_final.shape[0]
+        a.X, a.H, a.QKV, a.O, a.U, a.Y = (t.data_ptr() for t in (X, Hb, ws["qkv"], O, U, Y))
+        gws, aws = ws["gemm_ws"], ws["attn_ws"]
+        a.gemm_ws, a.gemm_ws_bytes = (gws.data_ptr(), gws.numel()) if gws is not None else (None, 0)
+        a.attn_ws, a.attn_ws_bytes = (aws.data_ptr(), aws.numel()) if aws is not None else (None, 0)
+        a.eps = 1e-6
+        if self._mx:
+            a.precision = 1
+            a.AQ, a.AS = ws["act"].data_ptr(), ws["act"].data_ptr() + ws["act_q_bytes"]
+            a.act_bytes = ws["act"].numel()
+            if self._mx_fused:
+                a.mx_fused = 1
+                a.UQ, a.US = ws["uact"].data_ptr(), ws["uact"].data_ptr() + ws["uact_q_bytes"]
+                a.u_act_bytes = ws["uact"].numel()
+        if self._amx:
+            a.attn_precision = 1
+            a.mx_attn, a.mx_attn_bytes = ws["mx_attn"].data_ptr(), ws["mx_attn"].numel()
+        return a
+
+    def _fa_local(self, sb, hin, ws, cos, sin, gate, S, B, fusedmx):
+        """Self-attention sub-block without an exchange, launch by launch (the launches of drn_dit_forward, in its order).
+        hin: the modulated input (bf16 H, or the MxTensor a fused LayerNorm wrote)."""
+        D = self.D
+        X, O, QKV = ws["x"], ws["o"], ws["qkv"]
+        self._lin(hin, sb["wqkv"], QKV, rows_per_batch=S)
+        q, k, v = QKV[:, :D], QKV[:, D:2 * D], QKV[:, 2 * D:]
+        amx = self._amx and N.attention_mxfp8_choice(self.heads, S)      # per site, from ONE clip's tokens
+        # fused producers: O leaves the attention as MXFP8; the 32x32x16 body has no MX epilogue and keeps bf16 + the quantise launch
+        omx = (self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D)
+               if fusedmx and (amx or N.attention_mx_available()) else None)
+        if amx:
+            # MXFP8 attention (the launches of drn_dit_forward with attn_precision 1): q and k leave norm + RoPE
+            # as MX (trace mode keeps the bf16 q and k as well), v is transposed and quantised along the keys
+            qm, km, vt, vs = ws["mx_attn_views"]
+            N.qk_norm_rope_mx(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S,
+                              write_bf16=self.trace is not None, out_q=qm, out_k=km)
+            N.mx_quant_vt(QKV.view(B, S, 3 * D)[:, :, 2 * D:], self.heads, out=(vt, vs))
+            oin = N.attention_mxfp8(qm, km, vt, vs, B, S, S, out=None if omx else O.view(B, S, D), out_mx=omx)
+        else:
+            N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
+            Q3 = QKV.view(B, S, 3 * D)
+            oin = N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:], out=None if omx else O.view(B, S, D),
+                              heads=self.heads, out_mx=omx)
+        self._lin(oin if omx else O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gate, residual=X, rows_per_batch=S)
+
+    def _mlp(self, sb, hin, ws, gate, rows, fusedmx):
+        """GPT-2 feed-forward sub-block.  Fused producers: U leaves MLP-up as MXFP8 where the GELU -> MX epilogue exists; a sliced
+        MLP-up keeps bf16 U and the quantise launch inside _lin."""
+        X, U = ws["x"], ws["u"]
+        uin = U
+        if fusedmx and N.mx_gemm_plan(X.shape[0], U.shape[1], self.D, rows) <= 1:
+            uin = N.gemm_mxfp8(hin, sb["w1"], epilogue=N.EPI_GELU, rows_per_batch=rows,
+                               out_mx=self._mx_view(ws["uact"], ws["uact_q_bytes"], X.shape[0], U.shape[1]))
+        else:
+            self._lin(hin, sb["w1"], U, epilogue=N.EPI_GELU, rows_per_batch=rows)
+        self._lin(uin, sb["w2"], X, epilogue=N.EPI_GATE_RES, gate=gate, residual=X, rows_per_batch=rows)
+
     def _run(self, x, cond, mod, modf, addvec, Tp, Hp, Wp, plan):
-        """The kernel sequence of one forward (all shapes / pointers fixed for a given input shape -> capturable)."""
+        """The kernel sequence of one forward (all shapes / pointers fixed for a given input shape)."""
         D = self.D
         S, rows, world = plan.S, plan.rows, plan.world
         B = x.shape[0]                                           # B > 1 only without an exchange (rows == S)
         cos, sin = self.rope(Tp, Hp, Wp)
         ws = self._workspace(S, rows, B)
-        X, Hb, O, U, Y = ws["x"], ws["h"], ws["o"], ws["u"], ws["y"]
+        X, Hb, O, Y = ws["x"], ws["h"], ws["o"], ws["y"]
+        modB = modfB = gateB = None
         if B > 1:
             # shift | scale rows per clip for the batched LayerNorm pass: [sites, 2, B, D] (one sigma -> B equal rows)
             modB = mod[:, :2 * D].reshape(-1, 2, 1, D).expand(-1, 2, B, D).contiguous()
@@ -556,46 +597,13 @@ class HipDiT:
 
         # the latent is tiny: every rank patchifies it all and keeps its own token band
         P = N.patchify_concat(x, cond, self.with_mask, self.pt, self.ps, self.kpad)
-        if self.exchange == "none" and self.trace is None and not self._per_launch:
+        sharded = self.exchange != "none"
+        if not sharded and self.trace is None and not self._per_launch:
             # one GPU: the whole launch sequence below is enqueued by ONE C call (csrc/dit_forward.hip: same kernels, same
             # arguments, same order -> same bits; ~570 ctypes round trips less per forward)
-            a = N.DitForwardArgs()
-            a.S, a.B, a.D, a.hidden, a.heads = S, B, D, U.shape[1], self.heads
-            a.n_sub, a.subs = len(self._subs_c), self._subs_c
-            if B == 1:
-                a.shift, a.scale, a.gate = mod.data_ptr(), mod.data_ptr() + 2 * D, mod.data_ptr() + 4 * D
-                assert mod.stride(1) == 1
-                a.shift_site_stride = a.scale_site_stride = a.gate_site_stride = mod.stride(0)    # (rows of a batched sigma table)
-                a.final_shift, a.final_scale = modf.data_ptr(), modf.data_ptr() + 2 * D
-            else:
-                a.shift, a.scale, a.gate = modB.data_ptr(), modB.data_ptr() + 2 * B * D, gateB.data_ptr()
-                a.shift_site_stride = a.scale_site_stride = 2 * B * D
-                a.gate_site_stride = B * D
-                a.final_shift, a.final_scale = modfB.data_ptr(), modfB.data_ptr() + 2 * B * D
-            if addvec is not None:
-                a.addvec, a.addvec_stride = addvec.data_ptr(), addvec[0].numel()
-            a.cos, a.sin = cos.data_ptr(), sin.data_ptr()
-            a.P, a.kpad, a.w_patch = P.data_ptr(), self.kpad, self.w_patch.data_ptr()
-            a.w_final, a.n_final = self.w_final.data_ptr(), self.w_final.shape[0]
-            a.X, a.H, a.QKV, a.O, a.U, a.Y = (t.data_ptr() for t in (X, Hb, ws["qkv"], O, U, Y))
-            gws, aws = ws["gemm_ws"], ws["attn_ws"]
-            a.gemm_ws, a.gemm_ws_bytes = (gws.data_ptr(), gws.numel()) if gws is not None else (None, 0)
-            a.attn_ws, a.attn_ws_bytes = (aws.data_ptr(), aws.numel()) if aws is not None else (None, 0)
-            a.eps = 1e-6
-            if self._mx:
-                a.precision = 1
-                a.AQ, a.AS = ws["act"].data_ptr(), ws["act"].data_ptr() + ws["act_q_bytes"]
-                a.act_bytes = ws["act"].numel()
-                if self._mx_fused:
-                    a.mx_fused = 1
-                    a.UQ, a.US = ws["uact"].data_ptr(), ws["uact"].data_ptr() + ws["uact_q_bytes"]
-                    a.u_act_bytes = ws["uact"].numel()
-            if self._amx:
-                a.attn_precision = 1
-                a.mx_attn, a.mx_attn_bytes = ws["mx_attn"].data_ptr(), ws["mx_attn"].numel()
-            N.dit_forward(a)
+            N.dit_forward(self._sequencer_args(ws, P, S, B, mod=mod, modf=modf, batched=(modB, modfB, gateB) if B > 1 else None,
+                                               addvec=addvec, rope=(cos, sin)))
             return N.unpatchify(Y, B, self.out_ch, Tp, Hp, Wp, self.pt, self.ps)
-        sharded = self.exchange != "none"
         if sharded and B > 1:
             for b in range(B):                                   # this rank's band of every clip (P holds whole clips)
                 N.gemm(plan.band(P[b * S:(b + 1) * S]), self.w_patch, out=X[b * rows:(b + 1) * rows])
@@ -603,80 +611,46 @@ class HipDiT:
             N.gemm(plan.band(P) if B == 1 else P, self.w_patch, out=X, rows_per_batch=rows)
 
         pending = None
-        site = 0
         nk = len(self.kinds)
         fused = None                                             # a2a exchange: blocked-layout GEMMs instead of regroup passes
-        for subs in self.blocks:
-            for sb in subs:
-                m = mod[site]
-                shift, scale, gate = m[:D], m[D:2 * D], m[2 * D:]
-                if B > 1:
-                    shift, scale = modB[site, 0], modB[site, 1]
-                if self.trace is not None and site > 0:
-                    self.trace[f"block{(site - 1) // nk}.{(site - 1) % nk}"] = self._traced(X, pending, B)
-                site += 1
-                if sb["kind"] == "ca":
-                    if pending is not None:
-                        N.bcast_add(X, pending, rows_per_batch=rows)
-                    pending = addvec[sb["idx"]]
-                    continue
-                # mxfp8 with fused producers (the launches of drn_dit_forward with mx_fused, in its order): h, O and U leave
-                # their producers as MXFP8; a site without a fused producer keeps bf16 + the quantise launch inside _lin
-                fusedmx = self._mx_fused and self.trace is None and not sharded
-                if fusedmx:
-                    hin = N.ln_modulate(X, shift, scale, add_vec=pending, rows_per_batch=rows,
-                                        out_mx=self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D))
-                else:
-                    hin = N.ln_modulate(X, shift, scale, out=Hb, add_vec=pending, rows_per_batch=rows)
-                pending = None
-                if sb["kind"] == "fa":
-                    if self.exchange == "none":
-                        QKV = ws["qkv"]
-                        self._lin(hin, sb["wqkv"], QKV, rows_per_batch=rows)
-                        q, k, v = QKV[:, :D], QKV[:, D:2 * D], QKV[:, 2 * D:]
-                        amx = self._amx and N.attention_mxfp8_choice(self.heads, S)      # per site, from ONE clip's tokens
-                        omx = (self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D)
-                               if fusedmx and (amx or N.attention_mx_available()) else None)
-                        if amx:
-                            # MXFP8 attention (the launches of drn_dit_forward with attn_precision 1): q and k leave norm + RoPE
-                            # as MX (trace mode keeps the bf16 q and k as well), v is transposed and quantised along the keys
-                            qm, km, vt, vs = ws["mx_attn_views"]
-                            N.qk_norm_rope_mx(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S,
-                                              write_bf16=self.trace is not None, out_q=qm, out_k=km)
-                            N.mx_quant_vt(QKV.view(B, S, 3 * D)[:, :, 2 * D:], self.heads, out=(vt, vs))
-                            oin = N.attention_mxfp8(qm, km, vt, vs, B, S, S, out=None if omx else O.view(B, S, D), out_mx=omx)
-                        else:
-                            N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
-                            if B == 1:
-                                oin = N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=None if omx else O.unsqueeze(0),
-                                                  heads=self.heads, out_mx=omx)
-                            else:
-                                Q3 = QKV.view(B, S, 3 * D)
-                                oin = N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:],
-                                                  out=None if omx else O.view(B, S, D), heads=self.heads, out_mx=omx)
-                        self._lin(oin if omx else O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate,
-                                  residual=X, rows_per_batch=rows)
-                    else:
-                        # sharded: the exchanges (and the projections that write / read their slabs) run clip by clip on this
-                        # rank's band of each clip; every clip of a batch has the same sigma, hence the same gate row
-                        if fused is None:
-                            W_ = D // world
-                            fused = (self.exchange == "a2a" and world > 1 and W_ >= 512 and N.gemm_blocked_ok(rows, 2 * D)
-                                     and N.gemm_blocked_ok(rows, D))
-                        for b in range(B):
-                            band = slice(b * rows, (b + 1) * rows)
-                            self._fa_sharded(sb, Hb[band], X[band], O[band], ws, plan, cos, sin, gate, fused)
-                else:
-                    uin = U
-                    if fusedmx and N.mx_gemm_plan(X.shape[0], U.shape[1], D, rows) <= 1:
-                        uin = N.gemm_mxfp8(hin, sb["w1"], epilogue=N.EPI_GELU, rows_per_batch=rows,
-                                           out_mx=self._mx_view(ws["uact"], ws["uact_q_bytes"], X.shape[0], U.shape[1]))
-                    else:
-                        self._lin(hin, sb["w1"], U, epilogue=N.EPI_GELU, rows_per_batch=rows)
-                    self._lin(uin, sb["w2"], X, epilogue=N.EPI_GATE_RES, gate=gateB[site - 1] if B > 1 else gate, residual=X,
-                              rows_per_batch=rows)
+        # mxfp8 with fused producers (the launches of drn_dit_forward with mx_fused, in its order): h, O and U leave their
+        # producers as MXFP8
+        fusedmx = self._mx_fused and self.trace is None and not sharded
+        for site, sb in enumerate(sb for subs in self.blocks for sb in subs):
+            m = mod[site]
+            shift, scale, gate = m[:D], m[D:2 * D], m[2 * D:]
+            if B > 1:
+                shift, scale, gate = modB[site, 0], modB[site, 1], gateB[site]
+            if self.trace is not None and site > 0:
+                self.trace[f"block{(site - 1) // nk}.{(site - 1) % nk}"] = self._traced(X, pending, B)
+            if sb["kind"] == "ca":
+                if pending is not None:
+                    N.bcast_add(X, pending, rows_per_batch=rows)
+                pending = addvec[sb["idx"]]
+                continue
+            if fusedmx:
+                hin = N.ln_modulate(X, shift, scale, add_vec=pending, rows_per_batch=rows,
+                                    out_mx=self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D))
+            else:
+                hin = N.ln_modulate(X, shift, scale, out=Hb, add_vec=pending, rows_per_batch=rows)
+            pending = None
+            if sb["kind"] == "mlp":
+                self._mlp(sb, hin, ws, gate, rows, fusedmx)
+            elif not sharded:
+                self._fa_local(sb, hin, ws, cos, sin, gate, S, B, fusedmx)
+            else:
+                # sharded: the exchanges (and the projections that write / read their slabs) run clip by clip on this
+                # rank's band of each clip; every clip of a batch has the same sigma, hence the same gate row
+                if fused is None:
+                    W_ = D // world
+                    fused = (self.exchange == "a2a" and world > 1 and W_ >= 512 and N.gemm_blocked_ok(rows, 2 * D)
+                             and N.gemm_blocked_ok(rows, D))
+                for b in range(B):
+                    band = slice(b * rows, (b + 1) * rows)
+                    self._fa_sharded(sb, Hb[band], X[band], O[band], ws, plan, cos, sin, m[2 * D:], fused)
 
         if self.trace is not None:
+            site = len(self.blocks) * nk
             self.trace[f"block{(site - 1) // nk}.{(site - 1) % nk}"] = self._traced(X, pending, B)
         if B == 1:
             N.ln_modulate(X, modf[:D], modf[D:], out=Hb, add_vec=pending)

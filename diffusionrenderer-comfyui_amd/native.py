@@ -88,6 +88,7 @@ SIGNATURES = {
     "drn_attention_mxfp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _F, _P],
     "drn_attention_splitkv_mxfp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _L, _L, _L, _L, _F, _I, _P, _P],
     "drn_dit_forward_mx_attn_bytes": [_L, _L, _L],
+    "drn_dit_forward_mx_attn_layout": [_L, _L, _L, POINTER(c_int64)],
     "drn_gemm_mxfp8": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _P],
     "drn_gemm_mxfp8_splitk_choice": [_L, _L, _L],
     "drn_gemm_mxfp8_splitk": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _I, _P, _P],
@@ -259,6 +260,29 @@ def set_timer(t):
 
 # ----------------------------------------------------------------------------------------------- wrappers
 
+_SPLIT_WS = {}
+
+
+def _split_workspace(key, nbytes, grow):
+    """The cached device scratch of the split launches (fp32 partials).  grow (the split-K GEMMs, key (device, "gemm")): one buffer
+    that only ever grows.  Else (split-KV attention, key (device, nbytes)): a buffer of exactly that size, replacing whatever the
+    cache held (one shape is kept resident)."""
+    ws = _SPLIT_WS.get(key)
+    if ws is None or (grow and ws.numel() < nbytes):
+        if not grow:
+            _SPLIT_WS.clear()
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=key[0])
+        _SPLIT_WS[key] = ws
+    return ws
+
+
+def _clip_rows(M, rows_per_batch):
+    """The rows of ONE clip: launch decisions that change the summation order come from them, so clips stacked along the rows
+    (rows_per_batch) get the plan of a clip alone (batch-invariant results)."""
+    rpb = rows_per_batch if rows_per_batch else max(M, 1)
+    return rpb if (0 < rpb < M and M % rpb == 0) else M
+
+
 def gemm(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None, splitk=None):
     """out[M,N] = epi(a[M,K] @ w[N,K]^T).  a/w/out may be row-strided 2-D views (last dim contiguous)."""
     _bf16(a, w, out, gate, residual)
@@ -274,17 +298,11 @@ def gemm(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_b
     t0 = _TIMER.begin("gemm") if _TIMER is not None else None
     lib = load_library()
     rpb = rows_per_batch if rows_per_batch else max(M, 1)
-    # launch decisions that change the summation order come from ONE clip's rows (batch-invariant results)
-    Mb = rpb if (0 < rpb < M and M % rpb == 0) else M
+    Mb = _clip_rows(M, rows_per_batch)
     splits = lib.drn_gemm_splitk_choice(Mb, N, K) if (Mb <= 1024 and splitk is None) else (splitk or 1)
     if splits > 1:
         # few tokens: the product streams the weights; K is split over several workgroups per tile to keep the CUs busy
-        nbytes = lib.drn_gemm_splitk_workspace_bytes(M, N, splits)
-        key = (a.device, "gemm")
-        ws = _SPLIT_WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-            _SPLIT_WS[key] = ws
+        ws = _split_workspace((a.device, "gemm"), lib.drn_gemm_splitk_workspace_bytes(M, N, splits), grow=True)
         _check(lib.drn_gemm_bf16_splitk(_ptr(a), _ptr(w), _ptr(out), M, N, K, a.stride(0), w.stride(0), out.stride(0), epilogue,
                                         _ptr(gate), _ptr(residual), ldr, rpb, splits, ws.data_ptr(), _stream()),
                "drn_gemm_bf16_splitk")
@@ -390,11 +408,8 @@ def attention_mx_available() -> bool:
 
 def mx_gemm_plan(M, N, K, rows_per_batch=None) -> int:
     """How gemm_mxfp8 runs an [M, N, K] product: 0 = drn_gemm_mxfp8 (256 x 256 tiles), s >= 1 = the few-token kernel with s K
-    slices (1 = unsplit, fused epilogue).  Decided by drn_gemm_mxfp8_splitk_choice from ONE clip's rows: clips stacked along the
-    rows (rows_per_batch) get the plan of a clip alone (batch-invariant summation order).  Host-only."""
-    rpb = rows_per_batch if rows_per_batch else max(M, 1)
-    Mb = rpb if (0 < rpb < M and M % rpb == 0) else M
-    return int(load_library().drn_gemm_mxfp8_splitk_choice(Mb, N, K))
+    slices (1 = unsplit, fused epilogue).  Decided by drn_gemm_mxfp8_splitk_choice from ONE clip's rows (_clip_rows).  Host-only."""
+    return int(load_library().drn_gemm_mxfp8_splitk_choice(_clip_rows(M, rows_per_batch), N, K))
 
 
 def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows_per_batch=None, splitk=None, out_mx=None):
@@ -437,12 +452,7 @@ def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows
     if splits >= 1:
         ws = None
         if splits > 1:
-            nbytes = lib.drn_gemm_splitk_workspace_bytes(M, N, splits)
-            key = (a.q.device, "gemm")
-            ws = _SPLIT_WS.get(key)
-            if ws is None or ws.numel() < nbytes:
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=a.q.device)
-                _SPLIT_WS[key] = ws
+            ws = _split_workspace((a.q.device, "gemm"), lib.drn_gemm_splitk_workspace_bytes(M, N, splits), grow=True)
         _check(lib.drn_gemm_mxfp8_splitk(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, out.stride(0),
                                          epilogue, _ptr(gate), _ptr(residual), ldr, rpb, splits, _ptr(ws), _stream()),
                "drn_gemm_mxfp8_splitk")
@@ -544,7 +554,6 @@ def qk_norm_rope(q, k, wq, wk, cos, sin, heads, tokens_per_batch=None, pos_offse
 
 
 _NUM_CUS = 256          # MI355X
-_SPLIT_WS = {}
 
 
 def attention_plan(batch, heads, Sq, Sk):
@@ -559,6 +568,41 @@ def attention_plan(batch, heads, Sq, Sk):
     return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
 
 
+def _attention_tail(launch, B, H, Sq, Sk, device, out, out_mx, scale, kv_splits, byte_factor):
+    """What attention() and attention_mxfp8() share once the operands are checked: the out / out_mx geometry, the walk of the
+    plan, the split-KV workspace and the timer.  launch(q0, n, o, oq, os, ldo, bso, scale, extra) enqueues the queries
+    [q0, q0 + n) of every clip: o / oq / os are the output pointers advanced to q0 (None = not written), extra = (nsplit, workspace)
+    for a launch with split keys, else ()."""
+    HD = H * 128
+    mx = None
+    if out_mx is not None:
+        mx = _mx_out(out_mx, B * Sq, HD, device)
+        assert out is None or (out.shape == (B, Sq, HD) and out.is_contiguous())
+        oq, osc = mx.q.view(B, Sq, HD), mx.scales.view(B, Sq, HD // 32)
+        ldo, bso = HD, Sq * HD                 # the MX rows are contiguous; o (optional) must share that geometry
+    else:
+        if out is None:
+            out = torch.empty((B, Sq, HD), dtype=torch.bfloat16, device=device)
+        ldo, bso = out.stride(1), out.stride(0)
+    if scale is None:
+        scale = 1.0 / (128 ** 0.5)
+    # the plan of ONE clip, applied to every clip of the batch: a split of the keys changes the summation order, so it must not
+    # depend on how many clips are stepped together
+    plan = attention_plan(1, H, Sq, Sk) if kv_splits is None else [(0, Sq, int(kv_splits))]
+    t0 = _TIMER.begin("attention") if _TIMER is not None else None
+    lib = load_library()
+    for q0, q1, ns in plan:
+        extra = ()
+        if ns > 1:
+            nbytes = lib.drn_attention_splitkv_workspace_bytes(B, H, q1 - q0, ns)
+            extra = (ns, _split_workspace((device, nbytes), nbytes, grow=False).data_ptr())
+        launch(q0, q1 - q0, _ptr(out[:, q0:q1]) if out is not None else None, _ptr(oq[:, q0:q1]) if mx is not None else None,
+               _ptr(osc[:, q0:q1]) if mx is not None else None, ldo, bso, scale, extra)
+    if t0 is not None:
+        _TIMER.end("attention", t0, 4.0 * B * H * Sq * Sk * 128, byte_factor * B * H * 128 * (2 * Sq + 2 * Sk))
+    return out if mx is None else mx
+
+
 def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None, out_mx=None):
     """q: [B, Sq, H*128], k/v: [B, Sk, H*128] (token-strided views allowed) -> out [B, Sq, H*128].
     kv_splits: None = automatic (attention_plan), 1 = single pass, n > 1 = split-KV + combine.
@@ -569,49 +613,18 @@ def attention(q, k, v, out=None, heads=None, scale=None, kv_splits=None, out_mx=
     Sk = k.shape[1]
     H = heads if heads else HD // 128
     assert HD == H * 128 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
-    mx = None
-    if out_mx is not None:
-        if not attention_mx_available():
-            raise RuntimeError("attention(out_mx=): the 32x32x16 body is selected and has no MX epilogue (drn.h)")
-        mx = _mx_out(out_mx, B * Sq, HD, q.device)
-        assert out is None or (out.shape == (B, Sq, HD) and out.is_contiguous())
-        oq, osc = mx.q.view(B, Sq, HD), mx.scales.view(B, Sq, HD // 32)
-        ldo, bso = HD, Sq * HD                 # the MX rows are contiguous; o (optional) must share that geometry
-    else:
-        if out is None:
-            out = torch.empty((B, Sq, HD), dtype=torch.bfloat16, device=q.device)
-        ldo, bso = out.stride(1), out.stride(0)
-    if scale is None:
-        scale = 1.0 / (128 ** 0.5)
-    # the plan of ONE clip, applied to every clip of the batch: a split of the keys changes the summation order, so it must not
-    # depend on how many clips are stepped together
-    plan = attention_plan(1, H, Sq, Sk) if kv_splits is None else [(0, Sq, int(kv_splits))]
-    t0 = _TIMER.begin("attention") if _TIMER is not None else None
+    if out_mx is not None and not attention_mx_available():
+        raise RuntimeError("attention(out_mx=): the 32x32x16 body is selected and has no MX epilogue (drn.h)")
     lib = load_library()
-    for q0, q1, ns in plan:
-        qs, n = q[:, q0:q1], q1 - q0
-        o_ = _ptr(out[:, q0:q1]) if out is not None else None
+
+    def launch(q0, n, o, oq, osc, ldo, bso, scale, extra):
         # (o [, oq, os]): the _mx entries take the two MX pointers behind o, everything else is the same call
-        outs = (o_,) if mx is None else (o_, _ptr(oq[:, q0:q1]), _ptr(osc[:, q0:q1]))
-        geom = (B, H, n, Sk, q.stride(1), k.stride(1), v.stride(1), ldo, q.stride(0), k.stride(0), v.stride(0), bso, scale)
-        if ns > 1:
-            nbytes = lib.drn_attention_splitkv_workspace_bytes(B, H, n, ns)
-            key = (q.device, nbytes)
-            ws = _SPLIT_WS.get(key)
-            if ws is None:
-                _SPLIT_WS.clear()
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-                _SPLIT_WS[key] = ws
-            fn, name = ((lib.drn_attention_splitkv_bf16, "drn_attention_splitkv_bf16") if mx is None else
-                        (lib.drn_attention_splitkv_bf16_mx, "drn_attention_splitkv_bf16_mx"))
-            _check(fn(_ptr(qs), _ptr(k), _ptr(v), *outs, *geom, ns, ws.data_ptr(), _stream()), name)
-        else:
-            fn, name = ((lib.drn_attention_bf16, "drn_attention_bf16") if mx is None else
-                        (lib.drn_attention_bf16_mx, "drn_attention_bf16_mx"))
-            _check(fn(_ptr(qs), _ptr(k), _ptr(v), *outs, *geom, _stream()), name)
-    if t0 is not None:
-        _TIMER.end("attention", t0, 4.0 * B * H * Sq * Sk * 128, 2.0 * B * H * 128 * (2 * Sq + 2 * Sk))
-    return out if mx is None else mx
+        name = "drn_attention" + ("_splitkv" if extra else "") + "_bf16" + ("_mx" if oq is not None else "")
+        outs = (o,) if oq is None else (o, oq, osc)
+        _check(getattr(lib, name)(_ptr(q[:, q0:q0 + n]), _ptr(k), _ptr(v), *outs, B, H, n, Sk, q.stride(1), k.stride(1), v.stride(1),
+                                  ldo, q.stride(0), k.stride(0), v.stride(0), bso, scale, *extra, _stream()), name)
+
+    return _attention_tail(launch, B, H, Sq, Sk, q.device, out, out_mx, scale, kv_splits, 2.0)
 
 
 # ----------------------------------------------------------------------------------------------- MXFP8 self-attention
@@ -687,42 +700,14 @@ def attention_mxfp8(qm, km, vt, vs, B, Sq, Sk, q_bs=None, k_bs=None, out=None, s
     assert HD == H * 128 and km.q.shape[1] == HD and qm.q.is_contiguous() and km.q.is_contiguous()
     assert qm.q.shape[0] >= (B - 1) * q_bs + Sq and km.q.shape[0] >= (B - 1) * k_bs + Sk
     assert vt.shape == (B, H, 128, Skp) and vt.is_contiguous() and vs.shape == (B, H, 128, Skp // 32) and vs.is_contiguous()
-    dev = qm.q.device
-    mx = None
-    if out_mx is not None:
-        mx = _mx_out(out_mx, B * Sq, HD, dev)
-        assert out is None or (out.shape == (B, Sq, HD) and out.is_contiguous())
-        oq, osc = mx.q.view(B, Sq, HD), mx.scales.view(B, Sq, HD // 32)
-        ldo, bso = HD, Sq * HD
-    else:
-        if out is None:
-            out = torch.empty((B, Sq, HD), dtype=torch.bfloat16, device=dev)
-        ldo, bso = out.stride(1), out.stride(0)
-    if scale is None:
-        scale = 1.0 / (128 ** 0.5)
-    plan = attention_plan(1, H, Sq, Sk) if kv_splits is None else [(0, Sq, int(kv_splits))]
-    t0 = _TIMER.begin("attention") if _TIMER is not None else None
     lib = load_library()
-    for q0, q1, ns in plan:
-        n = q1 - q0
-        ops = (_ptr(qm.q[q0:]), _ptr(qm.scales[q0:]), _ptr(km.q), _ptr(km.scales), _ptr(vt), _ptr(vs),
-               _ptr(out[:, q0:q1]) if out is not None else None,
-               _ptr(oq[:, q0:q1]) if mx is not None else None, _ptr(osc[:, q0:q1]) if mx is not None else None)
-        geom = (B, H, n, Sk, q_bs, k_bs, ldo, bso, scale)
-        if ns > 1:
-            nbytes = lib.drn_attention_splitkv_workspace_bytes(B, H, n, ns)
-            key = (dev, nbytes)
-            ws = _SPLIT_WS.get(key)
-            if ws is None:
-                _SPLIT_WS.clear()
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                _SPLIT_WS[key] = ws
-            _check(lib.drn_attention_splitkv_mxfp8(*ops, *geom, ns, ws.data_ptr(), _stream()), "drn_attention_splitkv_mxfp8")
-        else:
-            _check(lib.drn_attention_mxfp8(*ops, *geom, _stream()), "drn_attention_mxfp8")
-    if t0 is not None:
-        _TIMER.end("attention", t0, 4.0 * B * H * Sq * Sk * 128, 1.0 * B * H * 128 * (2 * Sq + 2 * Sk))
-    return out if mx is None else mx
+
+    def launch(q0, n, o, oq, osc, ldo, bso, scale, extra):
+        name = "drn_attention_splitkv_mxfp8" if extra else "drn_attention_mxfp8"
+        _check(getattr(lib, name)(_ptr(qm.q[q0:]), _ptr(qm.scales[q0:]), _ptr(km.q), _ptr(km.scales), _ptr(vt), _ptr(vs), o, oq, osc,
+                                  B, H, n, Sk, q_bs, k_bs, ldo, bso, scale, *extra, _stream()), name)
+
+    return _attention_tail(launch, B, H, Sq, Sk, qm.q.device, out, out_mx, scale, kv_splits, 1.0)
 
 
 def patchify_concat(x, cond, with_mask, pt, ps, ldo):

@@ -115,8 +115,8 @@ int drn_gemm_tall_force_shape(int shape);
 int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q, void* scales, void* stream);
 /* host-side count of the launches drn_mx_quant_bf16 has enqueued in this process (reset != 0 zeroes it after reading): lets a
  * test state "this forward issued no quantise launch" without a profiler.  A plain counter on the launch path (one host thread
- * per process, as everywhere in this library).  It counts ENQUEUES, not executions: launches replayed from a captured graph
- * (DRN_GRAPHS=1) are not counted, so the statement only holds for eager forwards. */
+ * per process, as everywhere in this library).  It counts ENQUEUES, not executions: launches a caller replays from a captured
+ * graph are not counted, so the statement only holds for eager forwards. */
 int64_t drn_mx_quant_calls(int reset);
 /* ---- producers that write their result as MXFP8 themselves (the `_mx` entry points below and next to their bf16 twins).
  * The one rule: a fused producer rounds its result to bf16 exactly where its twin rounds and applies the rule above to THAT bf16
@@ -379,6 +379,10 @@ typedef struct drn_dit_forward_args {
     int32_t reserved2;
     void* mx_attn; int64_t mx_attn_bytes; /* attn_precision 1: scratch for QQ | QS | KQ | KS | VT | VS (drn_dit_forward_mx_attn_bytes) */
 } drn_dit_forward_args;
+/* Every argument and workspace check is made up front, against the sizers below, before anything is enqueued: gemm_ws must hold
+ * drn_dit_forward_gemm_workspace_bytes (precision 1: the larger of its patch-embed / final-layer share and
+ * drn_dit_forward_mx_gemm_workspace_bytes), attn_ws drn_dit_forward_attn_workspace_bytes when a FA sub-block is present - whatever
+ * sub-blocks the forward holds.  DRN_EINVAL therefore always means that nothing was launched. */
 int drn_dit_forward(const drn_dit_forward_args* args, void* stream);
 int64_t drn_dit_forward_args_bytes(void);     /* sizeof the two structs as this library was compiled (binding self-check) */
 int64_t drn_dit_sub_bytes(void);
@@ -408,8 +412,12 @@ int64_t drn_dit_forward_mx_u_bytes(int64_t B, int64_t S, int64_t hidden);
  * (O is not written), else to O as bf16.  mx_attn holds, in this order and each 256-byte aligned from a 256-byte aligned base: QQ
  * [B S, D], KQ [B S, D], VT [B][heads][128][Sp], QS [B S, D / 32], KS [B S, D / 32], VS [B][heads][128][Sp / 32], Sp = S rounded up
  * to 128 (host-only sizer below).  DRN_EINVAL before any launch when attn_precision is neither 0 nor 1, or is 1 with mx_attn NULL,
- * misaligned or mx_attn_bytes short. */
+ * misaligned or mx_attn_bytes short.
+ * drn_dit_forward_mx_attn_layout (host-only) is the one statement of that layout: out[0 .. 5] = the byte offsets of QQ, KQ, VT, QS,
+ * KS, VS from the base of mx_attn, out[6] = the total (what drn_dit_forward_mx_attn_bytes returns), out[7] = Sp.  DRN_EINVAL where
+ * drn_dit_forward_mx_attn_bytes returns 0: B, S or D not positive, or D % 128 != 0. */
 int64_t drn_dit_forward_mx_attn_bytes(int64_t B, int64_t S, int64_t D);
+int drn_dit_forward_mx_attn_layout(int64_t B, int64_t S, int64_t D, int64_t out[8]);
 int64_t drn_dit_forward_mx_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden);
 
 /* ---- per-launch timing inside drn_dit_forward (the roofline leg of bench.py; no reference counterpart): a pool of HIP event

@@ -221,6 +221,51 @@ def test_forward_sequencer_equals_per_launch_path(pkg, gpu, D, L, heads, lat, B)
         assert torch.equal(y_seq, y_per), f"sigma {sigma}: max |diff| {(y_seq.float() - y_per.float()).abs().max().item()}"
 
 
+def test_two_launch_attention_plan_sequencer_equals_per_launch(pkg, gpu, monkeypatch):
+    """The smallest clip whose self-attention plan is TWO launches: latent (5, 104, 128) -> 5 x 52 x 64 = 16 640 tokens, 4 heads:
+    64 whole q-blocks x 4 heads fill one round of the 256 CUs unsplit, the one q-block left runs as a second launch from query
+    16 384 with its keys in 8 chunks + the combine pass.  Every other model-level fixture plans a single launch, so only here do
+    the sequencer's walk and the host wrapper's advance q / O / the MX rows by a non-zero first query.  For the four pairs of
+    (linear, attention) precision, and the MXFP8 linears also with DRN_MX_FUSED=0 (bf16 attention writing MX from the unsplit
+    launch and from the combine pass against bf16 O + quantise launches): sequencer == per-launch at B = 1 and B = 2, clip b of
+    the batch == that clip alone, a repeated call == itself.  16 640 >= 2048 tokens: drn_attention_mxfp8_choice is 1 unforced."""
+    Nn = pkg.native
+    heads, lat, S = 4, (5, 104, 128), 16640
+    plan = Nn.attention_plan(1, heads, S, S)
+    assert len(plan) == 2 and plan[1][2] > 1, plan
+    assert plan == [(0, 16384, 1), (16384, 16640, 8)] and Nn.attention_mxfp8_force(-1) == 0 and Nn.attention_mxfp8_choice(heads, S)
+    net = tiny_net(pkg, 512, 2, heads)
+    sw = pkg.synthetic_weights
+    sd = sw.synth_state_dict(net, torch.bfloat16, device=gpu)
+    x = sw.synth_tensor("two.x", (2, 16) + lat, torch.float32, device=gpu, scale=2.0).to(torch.bfloat16)
+    cond = sw.synth_tensor("two.c", (2, net["additional_concat_ch"]) + lat, torch.float32, device=gpu, scale=1.0).to(torch.bfloat16)
+    t = torch.tensor(1.5)
+    H = pkg.dit_engine.HipDiT
+    for lin, att, fused in [("bf16", "bf16", "1"), ("mxfp8", "bf16", "1"), ("mxfp8", "bf16", "0"), ("bf16", "mxfp8", "1"),
+                            ("mxfp8", "mxfp8", "1")]:
+        what = f"linears={lin} attention={att} DRN_MX_FUSED={fused}"
+        monkeypatch.setenv("DRN_MX_FUSED", fused)
+        monkeypatch.setenv("DRN_PER_LAUNCH", "0")
+        seq = H(net, sd, device=gpu, precision=lin, attention_precision=att)
+        monkeypatch.setenv("DRN_PER_LAUNCH", "1")
+        per = H(net, sd, device=gpu, precision=lin, attention_precision=att)
+        monkeypatch.delenv("DRN_PER_LAUNCH")
+        monkeypatch.delenv("DRN_MX_FUSED")
+        assert per._per_launch and not seq._per_launch and seq._mx_fused == (lin == "mxfp8" and fused == "1"), what
+        y1 = seq(x[:1], t, cond[:1], 2)
+        assert torch.isfinite(y1.float()).all(), what
+        assert torch.equal(y1, seq(x[:1], t, cond[:1], 2)), what + ": run to run"
+        assert torch.equal(y1, per(x[:1], t, cond[:1], 2)), what + ": sequencer vs per-launch, B = 1"
+        y2 = seq(x, t, cond, [2, 4])
+        assert torch.equal(y2, per(x, t, cond, [2, 4])), what + ": sequencer vs per-launch, B = 2"
+        assert torch.equal(y2[0:1], y1), what + ": clip 0 of the batch vs alone"
+        assert torch.equal(y2[1:2], seq(x[1:2], t, cond[1:2], 4)), what + ": clip 1 of the batch vs alone"
+        if (lin, att) == ("mxfp8", "bf16"):                  # fused producers write the bytes the quantise launches write
+            y_fused = y1 if fused == "1" else y_fused
+            assert torch.equal(y1, y_fused), what + ": fused vs quantise launches"
+        del seq, per
+
+
 def test_forward_sequencer_matches_reference_golden(pkg, gpu):
     """The golden of the two-block tiny model through the sequencer path (no trace): same bound as the per-launch path."""
     fixture, tag, D, L, heads, forward = CASES[1]

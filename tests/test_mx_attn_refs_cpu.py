@@ -182,6 +182,27 @@ def test_policy_query_and_sizers(pkg, lib):
     assert lib.drn_dit_forward_mx_attn_bytes(1, 256, 4096 + 64) == 0 and lib.drn_dit_forward_mx_attn_bytes(0, 256, 4096) == 0
 
 
+def test_mx_attn_layout_is_the_one_statement_of_the_scratch(pkg, lib):
+    """drn_dit_forward_mx_attn_layout: the offsets HipDiT._workspace builds its views from and the sequencer reads at.  Its total is
+    the sizer's, the six regions QQ | KQ | VT | QS | KS | VS follow each other 256-byte aligned without overlap (S = 300: no
+    multiple of 128, so Sp != S and the regions are no multiples of 256), and it refuses where the sizer returns 0."""
+    lay = (ctypes.c_int64 * 8)()
+    rounded = False
+    for B, S, Dm in ((1, 256, 4096), (2, 300, 512), (1, 18432, 4096)):
+        assert lib.drn_dit_forward_mx_attn_layout(B, S, Dm, lay) == 0
+        off, total, Sp = list(lay[:6]), lay[6], lay[7]
+        assert total == lib.drn_dit_forward_mx_attn_bytes(B, S, Dm) and Sp == (S + 127) // 128 * 128
+        sizes = [B * S * Dm, B * S * Dm, B * Dm * Sp, B * S * Dm // 32, B * S * Dm // 32, B * Dm * Sp // 32]
+        assert off[0] == 0 and all(o % 256 == 0 for o in off)
+        for i in range(6):
+            end = off[i + 1] if i < 5 else total
+            assert off[i] + sizes[i] <= end and end - (off[i] + sizes[i]) < 256, (B, S, Dm, i)
+            rounded = rounded or end != off[i] + sizes[i]
+    assert rounded                                                               # (S = 300: the scale regions are padded)
+    assert lib.drn_dit_forward_mx_attn_layout(1, 256, 4096 + 64, lay) == -1 and lib.drn_dit_forward_mx_attn_layout(0, 256, 4096, lay) == -1
+    assert lib.drn_dit_forward_mx_attn_layout(1, 256, 4096, None) == -1
+
+
 def test_site_choice_is_a_pure_function_of_one_clips_tokens(pkg, lib):
     assert lib.drn_attention_mxfp8_force(-1) == 0
     for heads in (2, 32):

@@ -301,4 +301,23 @@ def test_forward_refuses_before_any_launch(pkg, lib):
     a, subs = fused()
     a.AQ = None
     assert fwd(ctypes.byref(a), None) == -1
+    # and so are the per-sub-block ones, which an mx_fused forward used to reach only after its first launches (control first:
+    # the unchanged args are not refused; asked only where no GPU is visible, as a GPU would run kernels on the fake addresses)
+    import torch
+    for kw in ({}, dict(S=16640, D=512, hidden=2048)):
+        a, subs = fused(**kw)
+        a.attn_ws_bytes = lib.drn_dit_forward_attn_workspace_bytes(1, a.heads, a.S)
+        assert torch.cuda.is_available() or fwd(ctypes.byref(a), None) > 0
+    a, subs = fused()
+    subs[1].kind = 7
+    assert fwd(ctypes.byref(a), None) == -1
+    a, subs = fused()
+    subs[0].qn = None
+    assert fwd(ctypes.byref(a), None) == -1
+    a, subs = fused()
+    subs[1].kind, subs[1].ca_index = pkg.native.SUB_CA, 0                      # addvec is NULL in these args
+    assert fwd(ctypes.byref(a), None) == -1
+    a, subs = fused(S=16640, D=512, hidden=2048)
+    a.attn_ws_bytes = lib.drn_dit_forward_attn_workspace_bytes(1, 4, 16640) - 1
+    assert a.attn_ws_bytes > 0 and fwd(ctypes.byref(a), None) == -1
 

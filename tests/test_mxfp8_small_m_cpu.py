@@ -151,6 +151,53 @@ def test_forward_refuses_before_any_launch(pkg, lib):
     assert fwd(ctypes.byref(a), None) == -1
 
 
+def test_forward_refuses_per_sub_block_faults_before_any_launch(pkg, lib):
+    """What a sub-block or the attention plan needs is checked with everything else, before the patch-embed GEMM is enqueued (without
+    a GPU a launch would return a positive hipError_t, so -1 can only come from a check that ran first).  Both precisions."""
+    N = pkg.native
+    fwd = lib.drn_dit_forward
+
+    def args(precision, **kw):
+        a, subs = _mx_args(pkg, lib, **kw)
+        a.precision = precision
+        a.addvec, a.addvec_stride = 1 << 20, a.D
+        return a, subs
+
+    def not_refused(a):
+        """Valid args get past validate(): without a GPU the first launch then fails with a positive hipError_t.  Only asked
+        where no GPU is visible - with one, the call would enqueue kernels on the fake addresses."""
+        import torch
+        return torch.cuda.is_available() or fwd(ctypes.byref(a), None) > 0
+
+    for precision in (0, 1):
+        # controls: the unchanged args pass every check, so each -1 below comes from the one thing changed
+        a, subs = args(precision)
+        assert not_refused(a)
+        a, subs = args(precision)
+        subs[1].kind, subs[1].ca_index = N.SUB_CA, 0
+        assert not_refused(a)
+        a, subs = args(precision)
+        subs[1].kind = 7
+        assert fwd(ctypes.byref(a), None) == -1
+        a, subs = args(precision)
+        subs[0].qn = None
+        assert fwd(ctypes.byref(a), None) == -1
+        a, subs = args(precision)
+        subs[1].kind, subs[1].ca_index = N.SUB_CA, 0
+        a.addvec = None
+        assert fwd(ctypes.byref(a), None) == -1
+        # 4 heads, 16 640 tokens: the plan's second launch splits its keys and needs the split-KV workspace
+        a, subs = args(precision, S=16640, D=512, hidden=2048)
+        need = lib.drn_dit_forward_attn_workspace_bytes(1, 4, 16640)
+        assert need > 0 and N.attention_plan(1, 4, 16640, 16640) == [(0, 16384, 1), (16384, 16640, 8)]
+        a.attn_ws_bytes = need
+        assert not_refused(a)                                                    # control: exactly enough
+        a.attn_ws_bytes = need - 1
+        assert fwd(ctypes.byref(a), None) == -1
+        a.attn_ws_bytes, a.attn_ws = need, None
+        assert fwd(ctypes.byref(a), None) == -1
+
+
 def test_split_entry_points_refuse_on_the_host(pkg, lib):
     """The contract of drn_gemm_mxfp8_splitk / _partials is checked before the launch: these calls need no GPU."""
     p = 1 << 20
