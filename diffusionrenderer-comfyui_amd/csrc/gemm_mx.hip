@@ -73,12 +73,24 @@ __device__ __forceinline__ void mx_tile_of(int bid, int nwg, int tiles_m, int ti
     n0 = (int64_t)((pid % width) / gsz) * MX_T;
 }
 
-template <int EPI>
+// blocked operand layouts (drn_gemm_mxfp8_blocked, drn.h): A | SA in planes of a_cols columns (a plain A is ONE plane of K
+// columns), C in planes of 1 << c_shift columns (shift 62 = plain).  The plain-layout kernel takes the empty form.
+template <bool BLK> struct mx_blk_t {};
+template <> struct mx_blk_t<true> {
+    int64_t a_cols, a_stride, c_stride;
+    int c_shift;
+};
+// where the next K step of A starts inside a row (BLK only): byte offset, and the bytes of the current plane's row still ahead
+template <bool BLK> struct mx_astep_t {};
+template <> struct mx_astep_t<true> { int64_t koff = 0, left = 0; };
+
+// BLK = false is the plain-layout kernel: nothing of the blocked addressing reaches its code
+template <int EPI, bool BLK = false>
 __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ SA,
                                                          const uint8_t* __restrict__ W, const uint8_t* __restrict__ SW,
                                                          bf16_t* C, int64_t M, int64_t N, int64_t K, int64_t ldc,
                                                          const bf16_t* __restrict__ gate, const bf16_t* R, int64_t ldr, int64_t rpb,
-                                                         uint8_t* __restrict__ CS) {
+                                                         uint8_t* __restrict__ CS, const mx_blk_t<BLK> blk) {
     // the two stages as two LDS objects: the reads of one and the DMA into the other then provably do not alias, and the
     // compiler puts no vmcnt wait of its own in front of the fragment reads (one shared array: a vmcnt(0) before every step)
     __shared__ __attribute__((aligned(1024))) char lds0[MX_STAGE];
@@ -101,7 +113,8 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
         const int c = (lane & 7) ^ ((r >> 1) & 7);
         int64_t ra = m0 + r;
         if (ra > M - 1) ra = M - 1;
-        srcA[p] = A + ra * K + c * 16;
+        if constexpr (BLK) srcA[p] = A + ra * blk.a_cols + c * 16;      // a plane's rows are a_cols bytes apart
+        else srcA[p] = A + ra * K + c * 16;
         srcW[p] = W + (n0 + r) * K + c * 16;
     }
     const uint8_t* srcS;
@@ -110,20 +123,38 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
         if (wave < 4) {
             int64_t ra = m0 + r;
             if (ra > M - 1) ra = M - 1;
-            srcS = SA + ra * sk;
+            if constexpr (BLK) srcS = SA + ra * (blk.a_cols / 32);
+            else srcS = SA + ra * sk;
         } else {
             srcS = SW + (n0 + r) * sk;
         }
     }
     const int s_dst = (wave < 4 ? MX_SA : MX_SW) + (wave & 3) * 256;
 
+    // BLK: the K steps are requested in order (0, 1, 2, ...), so the byte offset of step kt inside an A row - plane * a_stride +
+    // (k % a_cols) - is carried from call to call: a_cols % 128 == 0, so a step and its 4-byte scale piece (offset / 32 in SA,
+    // whose planes are a_stride / 32 apart) never straddle a plane
+    mx_astep_t<BLK> as;
+    if constexpr (BLK) as.left = blk.a_cols;
     auto dma = [&](int kt, char* base) {
+        int64_t ka;
+        if constexpr (BLK) ka = as.koff; else ka = (int64_t)kt * MX_K;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            __builtin_amdgcn_global_load_lds((mx_gptr_t)(srcA[p] + (int64_t)kt * MX_K), (mx_lptr_t)(base + MX_A + (wave * 4 + p) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((mx_gptr_t)(srcA[p] + ka), (mx_lptr_t)(base + MX_A + (wave * 4 + p) * 1024), 16, 0, 0);
             __builtin_amdgcn_global_load_lds((mx_gptr_t)(srcW[p] + (int64_t)kt * MX_K), (mx_lptr_t)(base + MX_W + (wave * 4 + p) * 1024), 16, 0, 0);
         }
-        __builtin_amdgcn_global_load_lds((mx_gptr_t)(srcS + kt * 4), (mx_lptr_t)(base + s_dst), 4, 0, 0);
+        if constexpr (BLK) {
+            __builtin_amdgcn_global_load_lds((mx_gptr_t)(srcS + (wave < 4 ? (ka >> 5) : (int64_t)kt * 4)), (mx_lptr_t)(base + s_dst), 4, 0, 0);
+            as.koff += MX_K;
+            as.left -= MX_K;
+            if (as.left == 0) {
+                as.koff += blk.a_stride - blk.a_cols;
+                as.left = blk.a_cols;
+            }
+        } else {
+            __builtin_amdgcn_global_load_lds((mx_gptr_t)(srcS + kt * 4), (mx_lptr_t)(base + s_dst), 4, 0, 0);
+        }
     };
 
     // fragment read offsets: row fr of a 16-row tile, chunks fq and fq + 4 (K 16 fq .. +15 and 64 + 16 fq .. +15)
@@ -214,6 +245,7 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
         }
         return;
     }
+    if constexpr (BLK) C += (n0 >> blk.c_shift) * (blk.c_stride - ((int64_t)1 << blk.c_shift));   // the tile's plane (256 | plane width)
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
         const int64_t m = m0 + wm * 128 + mt * 16 + fr;
@@ -242,12 +274,22 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
 }
 
 template <int EPI>
+int launch_mx_blocked(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K,
+                      int64_t ldc, const void* gate, const void* R, int64_t ldr, int64_t rpb, const mx_blk_t<true>& blk, hipStream_t st) {
+    const int64_t tiles = (M + MX_T - 1) / MX_T * (N / MX_T);
+    gemm_mx_kernel<EPI, true><<<dim3((unsigned)tiles), dim3(512), 0, st>>>(
+        (const uint8_t*)A, (const uint8_t*)SA, (const uint8_t*)W, (const uint8_t*)SW, (bf16_t*)C, M, N, K, ldc,
+        (const bf16_t*)gate, (const bf16_t*)R, ldr, rpb, nullptr, blk);
+    return drn_launch_status();
+}
+
+template <int EPI>
 int launch_mx(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K, int64_t ldc,
               const void* gate, const void* R, int64_t ldr, int64_t rpb, hipStream_t st, void* CS = nullptr) {
     const int64_t tiles = (M + MX_T - 1) / MX_T * (N / MX_T);
     gemm_mx_kernel<EPI><<<dim3((unsigned)tiles), dim3(512), 0, st>>>(
         (const uint8_t*)A, (const uint8_t*)SA, (const uint8_t*)W, (const uint8_t*)SW, (bf16_t*)C, M, N, K, ldc,
-        (const bf16_t*)gate, (const bf16_t*)R, ldr, rpb, (uint8_t*)CS);
+        (const bf16_t*)gate, (const bf16_t*)R, ldr, rpb, (uint8_t*)CS, mx_blk_t<false>());
     return drn_launch_status();
 }
 
@@ -293,6 +335,45 @@ extern "C" int drn_gemm_mxfp8(const void* A, const void* SA, const void* W, cons
             const int64_t rpb = rows_per_batch > 0 ? rows_per_batch : M;
             DRN_CHECK_ARG(gate && residual && ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual & 7) == 0 && ((uintptr_t)gate & 7) == 0);
             return launch_mx<DRN_EPI_GATE_RES>(A, SA, W, SW, C, M, N, K, ldc, gate, residual, ldr, rpb, st);
+        }
+        default: return DRN_EINVAL;
+    }
+}
+
+// drn_gemm_mxfp8 with A | SA and / or C stored in column planes (drn.h): always the 256 x 256 kernel above
+extern "C" int drn_gemm_mxfp8_blocked(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N,
+                                      int64_t K, int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr,
+                                      int64_t rows_per_batch, int64_t a_block_cols, int64_t a_block_stride, int64_t c_block_cols,
+                                      int64_t c_block_stride, void* stream) {
+    DRN_CHECK_ARG(A && SA && W && SW && C && M >= 1 && N >= MX_T && N % MX_T == 0 && K >= MX_K && K % MX_K == 0);
+    DRN_CHECK_ARG(ldc % 4 == 0 && ((uintptr_t)C & 7) == 0);
+    DRN_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)SA & 3) == 0 && ((uintptr_t)SW & 3) == 0);
+    DRN_CHECK_ARG((M + MX_T - 1) / MX_T * (N / MX_T) < (1ll << 31));
+    mx_blk_t<true> blk = {K, 0, 0, 62};
+    if (a_block_cols) {
+        DRN_CHECK_ARG(a_block_cols >= MX_K && a_block_cols % MX_K == 0 && K % a_block_cols == 0);
+        DRN_CHECK_ARG(a_block_stride % 128 == 0 && a_block_stride / a_block_cols >= M);     // scale planes: a_block_stride / 32 apart
+        blk.a_cols = a_block_cols;
+        blk.a_stride = a_block_stride;
+    }
+    if (c_block_cols) {
+        int sh = 0;
+        while (sh < 40 && ((int64_t)1 << sh) < c_block_cols) ++sh;
+        DRN_CHECK_ARG(((int64_t)1 << sh) == c_block_cols && sh >= 8 && N % c_block_cols == 0 && ldc >= c_block_cols);
+        DRN_CHECK_ARG(c_block_stride % 4 == 0 && c_block_stride >= c_block_cols && (c_block_stride - c_block_cols) / ldc >= M - 1);
+        blk.c_shift = sh;
+        blk.c_stride = c_block_stride;
+    } else {
+        DRN_CHECK_ARG(ldc >= N);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    switch (epilogue) {
+        case DRN_EPI_NONE: return launch_mx_blocked<DRN_EPI_NONE>(A, SA, W, SW, C, M, N, K, ldc, nullptr, nullptr, 0, 1, blk, st);
+        case DRN_EPI_GELU: return launch_mx_blocked<DRN_EPI_GELU>(A, SA, W, SW, C, M, N, K, ldc, nullptr, nullptr, 0, 1, blk, st);
+        case DRN_EPI_GATE_RES: {
+            const int64_t rpb = rows_per_batch > 0 ? rows_per_batch : M;
+            DRN_CHECK_ARG(gate && residual && ldr >= N && ldr % 4 == 0 && ((uintptr_t)residual & 7) == 0 && ((uintptr_t)gate & 7) == 0);
+            return launch_mx_blocked<DRN_EPI_GATE_RES>(A, SA, W, SW, C, M, N, K, ldc, gate, residual, ldr, rpb, blk, st);
         }
         default: return DRN_EINVAL;
     }

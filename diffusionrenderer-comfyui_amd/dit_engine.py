@@ -19,7 +19,9 @@ fused into the next sub-block's LayerNorm pass.
 Sequence parallelism (one process per GPU): rank r owns a contiguous band of latent frames; every op is
 token-local except self-attention.  There the ranks trade token bands for heads with one all-to-all (each rank
 attends over ALL tokens of heads/world heads) and trade back afterwards; when the world size does not divide the
-head count, K/V rows (after RMSNorm + RoPE) are all-gathered instead (parallel.py).
+head count, K/V rows (after RMSNorm + RoPE) are all-gathered instead (parallel.py).  Both MXFP8 switches work under it: the
+projections write / read the exchange slabs through the blocked MXFP8 GEMM, the attention output goes home as e4m3 + scales
+($DRN_SP_MX_RETURN=0: as bf16), the MXFP8 attention runs on the heads a rank holds.
 """
 import ctypes
 import math
@@ -29,7 +31,7 @@ import torch
 
 from . import native as N
 from .host_tables import rope_cos_sin, timestep_sinusoid
-from .parallel import ShardPlan, allgather_rows_, alltoall_bands_, alltoall_rows_, group_info, wait_exchange
+from .parallel import ShardPlan, allgather_rows_, alltoall_bands_, alltoall_rows_, group_info, is_process_group, wait_exchange
 
 
 PRECISIONS = ("bf16", "mxfp8")
@@ -69,18 +71,20 @@ class HipDiT:
             attention_precision = os.environ.get("DRN_ATT_PRECISION", "") or "bf16"
         if attention_precision not in ATTENTION_PRECISIONS:
             raise ValueError(f"unknown attention precision {attention_precision!r}: expected one of {ATTENTION_PRECISIONS}")
-        if attention_precision == "mxfp8" and process_group is not None:
-            raise ValueError("attention_precision='mxfp8' with a process_group (sequence parallelism) is not built yet")
         self.attention_precision = attention_precision
         self._amx = attention_precision == "mxfp8"
         if precision is None:
             precision = os.environ.get("DRN_DIT_PRECISION", "") or "bf16"
         if precision not in PRECISIONS:
             raise ValueError(f"unknown DiT precision {precision!r}: expected one of {PRECISIONS}")
-        if precision == "mxfp8" and process_group is not None:
-            raise ValueError("precision='mxfp8' with a process_group (sequence parallelism) is not built yet")
         self.precision = precision
         self._mx = precision == "mxfp8"
+        # the MXFP8 exchanges carry uint8 / e4m3 payloads through torch.distributed collectives (parallel.py); a group object of
+        # any other transport gets the refusal that every process group got before the sharded MXFP8 paths existed
+        if (self._mx or self._amx) and process_group is not None and not is_process_group(process_group):
+            which = "precision" if self._mx else "attention_precision"
+            raise ValueError(f"{which}='mxfp8' with a process_group that is no torch.distributed.ProcessGroup (sequence parallelism "
+                             f"over another transport) is not built yet; got {type(process_group).__name__}")
         self.net = dict(net)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self.D = net["model_channels"]
@@ -125,8 +129,13 @@ class HipDiT:
         self._per_launch = os.environ.get("DRN_PER_LAUNCH", "0") == "1"
         # mxfp8: the producers (LayerNorm + modulate, attention, the GELU epilogue of MLP-up) write the quantised operand of the
         # next block linear themselves - no quantise launch, the same bits (drn.h).  DRN_MX_FUSED=0: a quantise launch in front of
-        # every block linear (the A/B switch).  Sharded engines cannot be mxfp8; trace mode keeps the bf16 intermediates.
+        # every block linear (the A/B switch).  Trace mode keeps the bf16 intermediates.
         self._mx_fused = self._mx and os.environ.get("DRN_MX_FUSED", "1") != "0"
+        # mxfp8 with the head <-> token exchange: the attention output goes home as e4m3 elements + scales (what its epilogue
+        # writes, 0.516 x the bytes of bf16) and the out-projection reads them as they arrive.  DRN_SP_MX_RETURN=0: the bf16 return
+        # exchange and a quantise launch (the A/B switch; the same bits)
+        self._mx_return = self._mx and os.environ.get("DRN_SP_MX_RETURN", "1") != "0"
+        self.sp_path = None        # sharded forwards: which layout / return exchange the last one took (tests, tools)
         # DRN_SP_SPLIT_RETURN=0: the return all-to-all as ONE collective after the whole attention (A/B runs)
         self._split_return = os.environ.get("DRN_SP_SPLIT_RETURN", "1") != "0"
 
@@ -296,9 +305,31 @@ class HipDiT:
                   "o": torch.empty((n, D), dtype=bf, device=dev),
                   "u": torch.empty((n, int(D * self.net["mlp_ratio"])), dtype=bf, device=dev),
                   "y": torch.empty((B * S, self.w_final.shape[0]), dtype=bf, device=dev)}
+            lib = N.load_library()
+            u8, f8 = torch.uint8, torch.float8_e4m3fn
+            if self.exchange != "none" and self._mx:
+                # sharded mxfp8: AQ | AS and UQ | US for this rank's band rows of every clip, laid out as on one GPU
+                hid = ws["u"].shape[1]
+                ws["act"] = torch.empty(lib.drn_dit_forward_mx_act_bytes(B, rows, D, hid), dtype=u8, device=dev)
+                ws["act_q_bytes"] = n * max(D, hid)
+                if self._mx_fused:
+                    ws["uact"] = torch.empty(lib.drn_dit_forward_mx_u_bytes(B, rows, hid), dtype=u8, device=dev)
+                    ws["uact_q_bytes"] = n * hid
+            if self.exchange != "none" and self._amx:
+                # MXFP8 attention over all S keys of the heads this rank attends (a2a: heads / world, Q of all tokens; gather: every
+                # head, Q of the band only): QQ | KQ | VT | QS | KS | VS by the layout rule of drn_dit_forward, one clip at a time
+                Da = D // self.world if self.exchange == "a2a" else D
+                lay = (ctypes.c_int64 * 8)()
+                N._check(lib.drn_dit_forward_mx_attn_layout(1, S, Da, lay), "drn_dit_forward_mx_attn_layout")
+                buf = torch.empty(lay[6], dtype=u8, device=dev)
+                Sp = lay[7]
+                shapes = ((S, Da), (S, Da), (1, Da // 128, 128, Sp), (S, Da // 32), (S, Da // 32), (1, Da // 128, 128, Sp // 32))
+                views = [buf[off:off + math.prod(shape)].view(shape) for off, shape in zip(lay, shapes)]
+                ws["mx_attn"] = buf
+                ws["mx_attn_views"] = (N.MxTensor(views[0].view(f8), views[3]), N.MxTensor(views[1].view(f8), views[4]),
+                                       views[2].view(f8), views[5])
             if self.exchange == "none":
                 ws["qkv"] = torch.empty((B * S, 3 * D), dtype=bf, device=dev)      # q | k | v, fused projection
-                lib = N.load_library()
                 nb = lib.drn_dit_forward_gemm_workspace_bytes(B, S, D, ws["u"].shape[1], self.w_final.shape[0], self.kpad)
                 if self._mx:
                     # the slices of the MXFP8 block linears share gemm_ws; AQ | AS: the quantised A operand of the next one
@@ -334,9 +365,18 @@ class HipDiT:
                 ws["rkv"] = torch.empty((S, 2 * W), dtype=bf, device=dev)
                 ws["oh"] = torch.empty((S, W), dtype=bf, device=dev)               # attention output, own heads
                 ws["oback"] = torch.empty((self.world, rows, W), dtype=bf, device=dev)
+                if self._mx:
+                    # the same two as MXFP8 (e4m3 return exchange), and the token-major regroup of the unfused layout
+                    ws["ohm"] = N.mx_empty(S, W, dev)
+                    ws["obm"] = N.MxTensor(torch.empty((self.world, rows, W), dtype=f8, device=dev),
+                                           torch.empty((self.world, rows, W // 32), dtype=u8, device=dev))
+                    ws["otm"] = N.mx_empty(rows, D, dev)
             else:
                 ws["q"] = torch.empty((rows, D), dtype=bf, device=dev)             # local queries
                 ws["kv"] = torch.empty((S, 2 * D), dtype=bf, device=dev)           # k | v of ALL tokens (all-gathered)
+                if self._amx:
+                    ws["kb"] = torch.empty((rows, D), dtype=bf, device=dev)        # K of the band (gathered as MXFP8, not as bf16)
+                    ws["vfull"] = torch.empty((S, D), dtype=bf, device=dev)        # V of ALL tokens (all-gathered)
             self._ws = {key: ws}
         return ws
 
@@ -414,14 +454,29 @@ class HipDiT:
         K slices from one clip's rows, as drn_dit_forward does)."""
         if not self._mx:
             return N.gemm(a, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch)
-        if isinstance(a, N.MxTensor):                            # a fused producer wrote the operand as MX already
-            return N.gemm_mxfp8(a, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch,
-                                splitk=None)
+        return N.gemm_mxfp8(self._mxq(a), w, out=out, epilogue=epilogue, gate=gate, residual=residual,
+                            rows_per_batch=rows_per_batch, splitk=None)
+
+    def _mxq(self, a):
+        """The MXFP8 operand of a block linear: `a` as it is when a fused producer wrote it as MX already, else the quantise launch
+        (into a buffer kept per shape)."""
+        if isinstance(a, N.MxTensor):
+            return a
         key = tuple(a.shape)
         aq = N.mx_quant(a, out=self._mx_act.get(key))
         self._mx_act[key] = aq
-        return N.gemm_mxfp8(aq, w, out=out, epilogue=epilogue, gate=gate, residual=residual, rows_per_batch=rows_per_batch,
-                            splitk=None)
+        return aq
+
+    @staticmethod
+    def _rows(t, lo, hi):
+        """Rows lo .. hi of a bf16 matrix or of an MxTensor (elements and scales): weight row blocks, token bands."""
+        return N.MxTensor(t.q[lo:hi], t.scales[lo:hi]) if isinstance(t, N.MxTensor) else t[lo:hi]
+
+    def _lin_planes(self, a, w, out, rows, a_planes=False, c_planes=False, **epi):
+        """A block linear that writes (c_planes) or reads (a_planes) the rank-major slabs of the head <-> token all-to-all."""
+        if self._mx:
+            return N.gemm_mxfp8_blocked(a, w, out, rows, a_planes=a_planes, c_planes=c_planes, **epi)
+        return N.gemm_blocked(a, w, out, rows, a_planes=a_planes, c_planes=c_planes, **epi)
 
     @staticmethod
     def _traced(X, pending, B):
@@ -429,75 +484,170 @@ class HipDiT:
             return X.clone()
         return (X.view(B, -1, X.shape[1]) + pending.view(B, 1, -1)).view_as(X)
 
-    def _fa_sharded(self, sb, Hb, X, O, ws, plan, cos, sin, gate, fused):
-        """Self-attention sub-block of ONE clip's token band with an exchange (Hb: modulated input rows, X: residual stream rows,
-        updated in place; O: scratch rows)."""
+    @staticmethod
+    def _regroup_bytes(src, dst):
+        """[world, rows, C] bytes -> [rows, world, C] bytes with the bf16 regroup kernel over byte pairs."""
+        world, rows, C = src.shape
+        N.permute_021(src.view(torch.uint8).view(torch.bfloat16),
+                      out=dst.view(torch.uint8).view(rows, world * C).view(torch.bfloat16))
+
+    def _attend(self, q, k, v, heads, S, amx, launches, out, out_mx):
+        """The attention launches of `heads` heads over all S keys for the sharded paths, after norm + RoPE.  bf16: q [Sq, heads*128],
+        k / v [S, heads*128] views; amx: q / k MxTensors, v = (vt, vs) of mx_quant_vt.  launches: [(q0, q1, kv_splits)], or None
+        for the one call under the automatic plan.  The output goes to `out` (bf16 [Sq, heads*128]) or `out_mx` (an MxTensor).
+        A generator: it yields after every launch, so the caller can start the exchange of the rows that are finished."""
+        Sq = q.shape[0]
+        for q0, q1, ns in (launches if launches is not None else [(0, Sq, None)]):
+            o = out[q0:q1].unsqueeze(0) if out is not None else None
+            om = self._rows(out_mx, q0, q1) if out_mx is not None else None
+            if amx:
+                N.attention_mxfp8(self._rows(q, q0, q1), k, v[0], v[1], 1, q1 - q0, S, out=o, out_mx=om, kv_splits=ns)
+            else:
+                N.attention(q[q0:q1].unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=o, heads=heads, kv_splits=ns, out_mx=om)
+            yield q1
+
+    def _fa_sharded(self, sb, hin, X, O, ws, plan, cos, sin, gate, fused, omx):
+        """Self-attention sub-block of ONE clip's token band with an exchange (hin: modulated input rows - bf16, or the MxTensor a
+        fused LayerNorm wrote; X: residual stream rows, updated in place; O: scratch rows; omx: their MXFP8 twin or None)."""
         D = self.D
         S, rows, world = plan.S, plan.rows, plan.world
+        mx = self._mx
+        if mx:
+            hin = self._mxq(hin)                                 # one operand for the K|V and the Q projection
+        wq, wkv, wo = self._rows(sb["wqkv"], 0, D), self._rows(sb["wqkv"], D, 3 * D), sb["wo"]
+        res = dict(epilogue=N.EPI_GATE_RES, gate=gate, residual=X)
         if self.exchange == "a2a":
             # tokens -> heads: project the band, regroup rank-major, all-to-all; norm + RoPE + attention over all S
             # tokens of this rank's heads; heads -> tokens: all-to-all back, regroup, output projection.
             # K|V go first so their exchange (RCCL's stream, 2/3 of the bytes) overlaps the Q projection.
             W, hpr = D // world, self.heads // world
             Oh, oback, rq, rkv = ws["oh"], ws["oback"], ws["rq"], ws["rkv"]
+            amx = self._amx and N.attention_mxfp8_choice(hpr, S)               # per site, from ONE clip's tokens
             # (the projections write the rank-major send slabs themselves where the tile kernel can; else a regroup pass)
             if fused:
-                N.gemm_blocked(Hb, sb["wqkv"][D:], ws["skv"], rows, c_planes=True)
+                self._lin_planes(hin, wkv, ws["skv"], rows, c_planes=True)
             else:
-                N.gemm(Hb, sb["wqkv"][D:], out=ws["kvb"])
+                self._lin(hin, wkv, ws["kvb"])
                 N.permute_021(ws["kvb"].view(rows, world, 2 * W), out=ws["skv"])
             work_kv = alltoall_rows_(ws["skv"], rkv.view(world, rows, 2 * W), self.pg, async_op=True)
             if fused:
-                N.gemm_blocked(Hb, sb["wqkv"][:D], ws["sq"], rows, c_planes=True)
+                self._lin_planes(hin, wq, ws["sq"], rows, c_planes=True)
             else:
-                N.gemm(Hb, sb["wqkv"][:D], out=ws["qb"])
+                self._lin(hin, wq, ws["qb"])
                 N.permute_021(ws["qb"].view(rows, world, W), out=ws["sq"])
             work_q = alltoall_rows_(ws["sq"], rq.view(world, rows, W), self.pg, async_op=True)
             wait_exchange(work_kv, "a2a k|v")
             k, v = rkv[:, :W], rkv[:, W:]
-            N.qk_norm_rope(None, k, None, sb["kn"], cos, sin, hpr, tokens_per_batch=S)
-            wait_exchange(work_q, "a2a q")
-            N.qk_norm_rope(rq, None, sb["qn"], None, cos, sin, hpr, tokens_per_batch=S)
+            if amx:
+                # q and k leave norm + RoPE as MXFP8, contiguous [S, W]; v is transposed and quantised along the keys
+                qm, km, vt, vs = ws["mx_attn_views"]
+                N.qk_norm_rope_mx(None, k, None, sb["kn"], cos, sin, hpr, tokens_per_batch=S, out_k=km)
+                N.mx_quant_vt(v.unsqueeze(0), hpr, out=(vt, vs))
+                wait_exchange(work_q, "a2a q")
+                N.qk_norm_rope_mx(rq, None, sb["qn"], None, cos, sin, hpr, tokens_per_batch=S, out_q=qm)
+                aq, ak, av = qm, km, (vt, vs)
+            else:
+                N.qk_norm_rope(None, k, None, sb["kn"], cos, sin, hpr, tokens_per_batch=S)
+                wait_exchange(work_q, "a2a q")
+                N.qk_norm_rope(rq, None, sb["qn"], None, cos, sin, hpr, tokens_per_batch=S)
+                aq, ak, av = rq, k, v
+            # mxfp8: the output leaves the attention as e4m3 + scales and travels like that, where an MX epilogue exists and the
+            # receive side can consume the bytes as they are: as A planes (fused), as they lie (one rank), or through the regroup
+            # kernel over byte pairs (scale rows of a multiple of 16 bytes); else bf16 goes home and is quantised there
+            mxret = (self._mx_return and (amx or N.attention_mx_available())
+                     and (fused or world == 1 or (W // 32) % 16 == 0))
+            self.sp_path = {"layout": "slabs" if fused else "regroup", "return": "e4m3" if mxret else "bf16",
+                            "attention": "mxfp8" if amx else "bf16"}
+            if mxret:
+                ohm, obm = ws["ohm"], ws["obm"]
+                send = (ohm.q.view(world, rows, W), ohm.scales.view(world, rows, W // 32))
+                recv = (obm.q, obm.scales)
+            else:
+                send, recv = Oh.view(world, rows, W), oback
             # heads -> tokens.  The attention of a rank's heads is usually two launches (native.attention_plan: the
             # q-blocks that fill whole rounds of the CUs, then the rest with its keys split): the token bands whose
             # queries the first launch has finished go home while the second one runs, only the last bands' slabs
             # (1 of 8 at world 8) travel exposed.  Same launches as the single call: same bits.
             aplan = N.attention_plan(1, hpr, S, S)
             nb = aplan[0][1] // rows if len(aplan) == 2 else 0             # complete bands of the first launch
-            if nb >= 1 and self._split_return:
-                (_, q_cut, ns0), (_, _, ns1) = aplan
-                N.attention(rq[:q_cut].unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=Oh[:q_cut].unsqueeze(0),
-                            heads=hpr, kv_splits=ns0)
-                work0 = alltoall_bands_(Oh.view(world, rows, W), oback, 0, nb, self.pg, async_op=True)
-                N.attention(rq[q_cut:].unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=Oh[q_cut:].unsqueeze(0),
-                            heads=hpr, kv_splits=ns1)
-                work1 = alltoall_bands_(Oh.view(world, rows, W), oback, nb, world, self.pg, async_op=True)
+            split = nb >= 1 and self._split_return
+            att = self._attend(aq, ak, av, hpr, S, amx, aplan if split else None, None if mxret else Oh,
+                               ws["ohm"] if mxret else None)
+            if split:
+                next(att)
+                work0 = alltoall_bands_(send, recv, 0, nb, self.pg, async_op=True)
+                next(att)
+                work1 = alltoall_bands_(send, recv, nb, world, self.pg, async_op=True)
                 wait_exchange(work0, "a2a o (return, under the attention tail)")
                 wait_exchange(work1, "a2a o (return)")
             else:
-                N.attention(rq.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=Oh.unsqueeze(0), heads=hpr)
-                work = alltoall_rows_(Oh.view(world, rows, W), oback, self.pg, async_op=True)
+                next(att)
+                work = alltoall_rows_(send, recv, self.pg, async_op=True)
                 wait_exchange(work, "a2a o (return)")
+            att.close()
             if fused:
-                N.gemm_blocked(oback, sb["wo"], X, rows, epilogue=N.EPI_GATE_RES, gate=gate, residual=X, a_planes=True)
+                if mxret:
+                    a = ws["obm"]
+                elif mx:                                         # bf16 came home: quantise the slabs where they lie
+                    aq = self._mxq(oback.view(world * rows, W))
+                    a = N.MxTensor(aq.q.view(world, rows, W), aq.scales.view(world, rows, W // 32))
+                else:
+                    a = oback
+                self._lin_planes(a, wo, X, rows, a_planes=True, **res)
+                return
+            if mxret:
+                otm = ws["otm"]
+                if world == 1:
+                    otm = N.MxTensor(ws["obm"].q.view(rows, D), ws["obm"].scales.view(rows, D // 32))
+                else:
+                    self._regroup_bytes(ws["obm"].q, otm.q)
+                    self._regroup_bytes(ws["obm"].scales, otm.scales)
+                self._lin(otm, wo, X, **res)
                 return
             N.permute_021(oback, out=O.view(rows, world, W))
         else:
             # local projections; K|V land directly in this rank's band of the gather buffer.  K|V first, so the
             # exchange (RCCL's own stream) overlaps the Q projection + q-norm; wait() orders attention after it.
             q, KV = ws["q"], ws["kv"]
-            kv_loc = plan.band(KV)
-            N.gemm(Hb, sb["wqkv"][D:], out=kv_loc)
-            N.qk_norm_rope(None, kv_loc[:, :D], None, sb["kn"], cos, sin, self.heads,
-                           tokens_per_batch=rows, pos_offset=plan.start)
-            work = allgather_rows_(KV, plan, self.pg, async_op=True)     # the one exchange of the block (xGMI)
-            N.gemm(Hb, sb["wqkv"][:D], out=q)
-            N.qk_norm_rope(q, None, sb["qn"], None, cos, sin, self.heads,
-                           tokens_per_batch=rows, pos_offset=plan.start)
-            wait_exchange(work, "gather k|v")
-            k, v = KV[:, :D], KV[:, D:]
-            N.attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=O.unsqueeze(0), heads=self.heads)
-        N.gemm(O, sb["wo"], out=X, epilogue=N.EPI_GATE_RES, gate=gate, residual=X)
+            amx = self._amx and N.attention_mxfp8_choice(self.heads, S)
+            self.sp_path = {"layout": "gather", "return": "none", "attention": "mxfp8" if amx else "bf16"}
+            if amx:
+                # K of the band leaves norm + RoPE as MXFP8 and is gathered like that (half the bytes of the bf16 K gather); V is
+                # gathered in bf16 and transposed + quantised along ALL keys afterwards
+                qm, km, vt, vs = ws["mx_attn_views"]
+                qm = self._rows(qm, 0, rows)
+                kb, vfull = ws["kb"], ws["vfull"]
+                self._lin(hin, self._rows(sb["wqkv"], D, 2 * D), kb)
+                self._lin(hin, self._rows(sb["wqkv"], 2 * D, 3 * D), plan.band(vfull))
+                N.qk_norm_rope_mx(None, kb, None, sb["kn"], cos, sin, self.heads, tokens_per_batch=rows, pos_offset=plan.start,
+                                  out_k=self._rows(km, plan.start, plan.stop))
+                work = [allgather_rows_(t, plan, self.pg, async_op=True) for t in (km.q, km.scales, vfull)]
+                work = [w_ for w_ in work if w_ is not None] or None
+            else:
+                kv_loc = plan.band(KV)
+                self._lin(hin, wkv, kv_loc)
+                N.qk_norm_rope(None, kv_loc[:, :D], None, sb["kn"], cos, sin, self.heads,
+                               tokens_per_batch=rows, pos_offset=plan.start)
+                work = allgather_rows_(KV, plan, self.pg, async_op=True)     # the one exchange of the block (xGMI)
+            self._lin(hin, wq, q)
+            if amx:
+                N.qk_norm_rope_mx(q, None, sb["qn"], None, cos, sin, self.heads, tokens_per_batch=rows, pos_offset=plan.start,
+                                  out_q=qm)
+                wait_exchange(work, "gather k|v")
+                N.mx_quant_vt(vfull.unsqueeze(0), self.heads, out=(vt, vs))
+                aq, ak, av = qm, km, (vt, vs)
+            else:
+                N.qk_norm_rope(q, None, sb["qn"], None, cos, sin, self.heads, tokens_per_batch=rows, pos_offset=plan.start)
+                wait_exchange(work, "gather k|v")
+                aq, ak, av = q, KV[:, :D], KV[:, D:]
+            # fused producers: O leaves the attention as MXFP8 (the 32x32x16 body has no MX epilogue: bf16 + the quantise launch)
+            if omx is not None and not (amx or N.attention_mx_available()):
+                omx = None
+            for _ in self._attend(aq, ak, av, self.heads, S, amx, None, None if omx is not None else O, omx):
+                pass
+            if omx is not None:
+                O = omx
+        self._lin(O, wo, X, **res)
 
     def _sequencer_args(self, ws, P, S, B, *, mod, modf, batched, addvec, rope):
         """The argument block of drn_dit_forward for this workspace (raw pointers: the caller keeps every tensor alive).
@@ -615,7 +765,7 @@ class HipDiT:
         fused = None                                             # a2a exchange: blocked-layout GEMMs instead of regroup passes
         # mxfp8 with fused producers (the launches of drn_dit_forward with mx_fused, in its order): h, O and U leave their
         # producers as MXFP8
-        fusedmx = self._mx_fused and self.trace is None and not sharded
+        fusedmx = self._mx_fused and self.trace is None
         for site, sb in enumerate(sb for subs in self.blocks for sb in subs):
             m = mod[site]
             shift, scale, gate = m[:D], m[D:2 * D], m[2 * D:]
@@ -643,11 +793,19 @@ class HipDiT:
                 # rank's band of each clip; every clip of a batch has the same sigma, hence the same gate row
                 if fused is None:
                     W_ = D // world
-                    fused = (self.exchange == "a2a" and world > 1 and W_ >= 512 and N.gemm_blocked_ok(rows, 2 * D)
-                             and N.gemm_blocked_ok(rows, D))
+                    if self._mx:
+                        # the MXFP8 slab GEMM always runs on the 256 x 256 kernel: taken where the plan of one clip's band rows picks
+                        # that kernel anyway (the slab layout then changes no bit) and the planes meet its contract (drn.h)
+                        fused = (self.exchange == "a2a" and world > 1 and W_ >= 256 and W_ & (W_ - 1) == 0
+                                 and N.mx_gemm_plan(rows, 2 * D, D) == 0 and N.mx_gemm_plan(rows, D, D) == 0)
+                    else:
+                        fused = (self.exchange == "a2a" and world > 1 and W_ >= 512 and N.gemm_blocked_ok(rows, 2 * D)
+                                 and N.gemm_blocked_ok(rows, D))
+                omx = self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D) if fusedmx and self.exchange == "gather" else None
                 for b in range(B):
-                    band = slice(b * rows, (b + 1) * rows)
-                    self._fa_sharded(sb, Hb[band], X[band], O[band], ws, plan, cos, sin, m[2 * D:], fused)
+                    self._fa_sharded(sb, self._rows(hin, b * rows, (b + 1) * rows), X[b * rows:(b + 1) * rows],
+                                     O[b * rows:(b + 1) * rows], ws, plan, cos, sin, m[2 * D:], fused,
+                                     self._rows(omx, b * rows, (b + 1) * rows) if omx is not None else None)
 
         if self.trace is not None:
             site = len(self.blocks) * nk

@@ -90,6 +90,7 @@ SIGNATURES = {
     "drn_dit_forward_mx_attn_bytes": [_L, _L, _L],
     "drn_dit_forward_mx_attn_layout": [_L, _L, _L, POINTER(c_int64)],
     "drn_gemm_mxfp8": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _P],
+    "drn_gemm_mxfp8_blocked": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _L, _L, _L, _L, _P],
     "drn_gemm_mxfp8_splitk_choice": [_L, _L, _L],
     "drn_gemm_mxfp8_splitk": [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _L, _L, _I, _P, _P],
     "drn_gemm_mxfp8_splitk_partials": [_P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P],
@@ -459,6 +460,49 @@ def gemm_mxfp8(a, w, out=None, epilogue=EPI_NONE, gate=None, residual=None, rows
     else:
         _check(lib.drn_gemm_mxfp8(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, out.stride(0),
                                   epilogue, _ptr(gate), _ptr(residual), ldr, rpb, _stream()), "drn_gemm_mxfp8")
+    if t0 is not None:
+        _TIMER.end("gemm", t0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (2 if residual is not None else 1))
+    return out
+
+
+def mx_plane_args(planes):
+    """(block_cols, row stride, block_stride) of a tensor of column planes [P, M, cols] as drn_gemm_mxfp8_blocked takes them: plane p
+    holds the logical columns p * cols .. of every row; the planes may be views of wider allocations (rows past M behind each
+    plane), the columns of a row are contiguous.  Strides in elements of the tensor.  Host-only (any device, meta included)."""
+    P, M, cols = planes.shape
+    assert planes.stride(2) == 1 and planes.stride(1) >= cols
+    return cols, planes.stride(1), planes.stride(0) if P > 1 else max(planes.stride(0), M * planes.stride(1))
+
+
+def gemm_mxfp8_blocked(a, w, out, M, epilogue=EPI_NONE, gate=None, residual=None, a_planes=False, c_planes=False):
+    """gemm_mxfp8 with A and / or C stored as planes of columns (drn_gemm_mxfp8_blocked; always the 256 x 256 kernel).
+    a_planes: `a` is an MxTensor with q [P, M, Kb] = logical A[M, P*Kb] (plane p holds columns p*Kb ..; rows contiguous) and scales
+    [P, M, Kb/32], planes q.stride(0) bytes resp. q.stride(0) / 32 scale bytes apart; c_planes: `out` is bf16 [P, M, Nb] = logical
+    C[M, P*Nb].  Otherwise a plain MxTensor [M, K] / a row-strided [M, N] view.  The residual stays plain."""
+    _bf16(out, gate, residual)
+    N, K = w.shape
+    if a_planes:
+        P, Ma, Kb = a.q.shape
+        abc, lda, abs_ = mx_plane_args(a.q)
+        sbc, lds, sbs = mx_plane_args(a.scales)
+        assert Ma == M and P * Kb == K and lda == Kb and a.scales.shape == (P, M, Kb // 32) and lds == Kb // 32 and sbs * 32 == abs_
+    else:
+        assert a.q.shape == (M, K) and a.q.is_contiguous() and a.scales.shape == (M, K // 32) and a.scales.is_contiguous()
+        abc, abs_ = 0, 0
+    if c_planes:
+        P, Mc, Nb = out.shape
+        cbc, ldc, cbs = mx_plane_args(out)
+        assert Mc == M and P * Nb == N
+    else:
+        assert out.shape == (M, N) and out.stride(1) == 1
+        ldc, cbc, cbs = out.stride(0), 0, 0
+    ldr = residual.stride(0) if residual is not None else 0
+    if residual is not None:
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+    t0 = _TIMER.begin("gemm") if _TIMER is not None else None
+    _check(load_library().drn_gemm_mxfp8_blocked(_ptr(a.q), _ptr(a.scales), _ptr(w.q), _ptr(w.scales), _ptr(out), M, N, K, ldc,
+                                                 epilogue, _ptr(gate), _ptr(residual), ldr, max(M, 1), abc, abs_, cbc, cbs,
+                                                 _stream()), "drn_gemm_mxfp8_blocked")
     if t0 is not None:
         _TIMER.end("gemm", t0, 2.0 * M * N * K, 1.03 * (M * K + N * K) + 2.0 * M * N * (2 if residual is not None else 1))
     return out

@@ -45,6 +45,11 @@ def group_info(group=None) -> Tuple[int, int]:
     return dist.get_rank(group), dist.get_world_size(group)
 
 
+def is_process_group(group) -> bool:
+    """True for a group whose collectives torch.distributed runs (what the uint8 / e4m3 exchanges of the MXFP8 paths need)."""
+    return dist.is_available() and isinstance(group, dist.ProcessGroup)
+
+
 # tests set this to run the collectives of a 1-rank group too (RCCL call path on a single GPU)
 SINGLE_RANK_COLLECTIVES = False
 
@@ -89,17 +94,38 @@ def set_exchange_timer(t):
 
 
 def wait_exchange(work, tag: str):
-    """work.wait() (None = nothing was issued), timed when an ExchangeTimer is installed."""
+    """work.wait() (None = nothing was issued; a list = the collectives of one exchange that carries several tensors), timed when an
+    ExchangeTimer is installed."""
     if work is None:
         return
+    works = work if isinstance(work, (list, tuple)) else [work]
     if _XTIMER is None or not torch.cuda.is_available() or not _XTIMER.take(tag):
-        work.wait()
+        for w in works:
+            w.wait()
         return
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
-    work.wait()
+    for w in works:
+        w.wait()
     b.record()
     _XTIMER.records.append((tag, a, b))
+
+
+_FP8 = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
+def _wire(t: torch.Tensor) -> torch.Tensor:
+    """The tensor as a collective carries it: fp8 payloads (the e4m3 elements of an MXFP8 exchange) travel as the uint8 view of the
+    same memory - bytes are bytes, and not every backend (gloo; RCCL of older builds) takes the fp8 dtypes."""
+    return t.view(torch.uint8) if t.dtype in _FP8 else t
+
+
+def _several(fn, send, recv, *args):
+    """An exchange that carries several tensors (MXFP8: elements and scales): one collective each, their works as a list."""
+    assert len(send) == len(recv)
+    works = [fn(s_, r_, *args) for s_, r_ in zip(send, recv)]
+    works = [w for w in works if w is not None]
+    return works or None
 
 
 def allgather_rows_(full: torch.Tensor, plan: ShardPlan, group=None, async_op: bool = False):
@@ -107,6 +133,7 @@ def allgather_rows_(full: torch.Tensor, plan: ShardPlan, group=None, async_op: b
     if plan.world == 1 and not (SINGLE_RANK_COLLECTIVES and group is not None):
         return None
     assert full.is_contiguous() and full.shape[0] == plan.S
+    full = _wire(full)
     if dist.get_backend(group) == "gloo" and full.is_cuda:
         # test-only path (two ranks sharing one GPU cannot use RCCL): gloo gathers device tensors through host staging
         parts = [torch.empty_like(plan.band(full)) for _ in range(plan.world)]
@@ -127,7 +154,11 @@ def allgather_rows(local: torch.Tensor, plan: ShardPlan, group=None) -> torch.Te
 
 
 def alltoall_rows_(send: torch.Tensor, recv: torch.Tensor, group=None, async_op: bool = False):
-    """Equal-split all-to-all: send [world, n, C] (slab r goes to rank r) -> recv [world, n, C] (slab r came from rank r)."""
+    """Equal-split all-to-all: send [world, n, C] (slab r goes to rank r) -> recv [world, n, C] (slab r came from rank r).
+    Any payload dtype, uint8 and fp8 included; send / recv may be equally long tuples of tensors (one collective each)."""
+    if isinstance(send, (tuple, list)):
+        return _several(alltoall_rows_, send, recv, group, async_op)
+    send, recv = _wire(send), _wire(recv)
     assert send.is_contiguous() and recv.is_contiguous() and send.shape == recv.shape
     if dist.get_backend(group) == "gloo" and send.is_cuda:
         # test-only path (two ranks sharing one GPU cannot use RCCL): host staging
@@ -142,7 +173,11 @@ def alltoall_bands_(send: torch.Tensor, recv: torch.Tensor, lo: int, hi: int, gr
     """The part of alltoall_rows_(send, recv) whose DESTINATION ranks are lo <= r < hi: every rank sends slab r to rank r for those
     r only; a rank inside [lo, hi) receives its slab from every peer (all of `recv`), the others receive nothing.  The parts
     over a partition of the ranks add up to the whole exchange - used to return the attention output of the token bands whose
-    queries are finished while the attention of the remaining bands still runs (dit_engine, head <-> token exchange)."""
+    queries are finished while the attention of the remaining bands still runs (dit_engine, head <-> token exchange).
+    Payloads and tuples as alltoall_rows_."""
+    if isinstance(send, (tuple, list)):
+        return _several(alltoall_bands_, send, recv, lo, hi, group, async_op)
+    send, recv = _wire(send), _wire(recv)
     assert send.is_contiguous() and recv.is_contiguous() and send.shape == recv.shape
     world, n = send.shape[0], send.shape[1]
     rank = dist.get_rank(group)

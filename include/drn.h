@@ -18,7 +18,9 @@
  *     NOT built: the library has no communication state at all.  The sequence-parallel exchanges (head <-> token all-to-all,
  *     K|V all-gather; parallel.py) are issued by the host through torch.distributed (backend "nccl" = RCCL over xGMI) on the
  *     tensors the kernels below read and write - drn_gemm_bf16_blocked / drn_permute_021 produce and consume the rank-major
- *     slabs of those exchanges directly.
+ *     slabs of those exchanges directly.  The MXFP8 switches work under that sharding too: drn_gemm_mxfp8_blocked is the slab
+ *     GEMM, and the attention output travels home as the e4m3 elements + scales drn_attention_*_mx writes.  Not built: Q / K|V
+ *     sent as e4m3, MXFP8 in the sharded tokenizer, the sharded path on drn_dit_forward.
  *   - drn_attention_bf16: the output base and its row / batch strides must allow 16-byte stores (o % 16 == 0, ldo % 8 == 0);
  *     the K / V tile DMA addresses a row as a 32-bit byte offset from its tile's first row: 64 * ldk * 2 and 64 * ldv * 2 < 2^32.
  */
@@ -137,6 +139,25 @@ int drn_gemm_mxfp8_gelu_mx(const void* A, const void* SA, const void* W, const v
 int drn_gemm_mxfp8(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K,
                    int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
                    void* stream);
+/* ---- drn_gemm_mxfp8 with operands stored in column blocks ("planes"), as drn_gemm_bf16_blocked defines them: the MXFP8 forms of
+ * the sequence-parallel projections write the rank-major send slabs of the head <-> token all-to-all and the output projection
+ * reads the rank-major receive slabs - there the e4m3 elements and scales the attention epilogue wrote, as they travelled.
+ *   A: logical A[m][k] at A + (k / a_block_cols) * a_block_stride + m * a_block_cols + k % a_block_cols (bytes; a plane's rows are
+ *      contiguous), its scale for block k / 32 at the same decomposition of SA divided by 32: SA + (k / a_block_cols) *
+ *      (a_block_stride / 32) + m * (a_block_cols / 32) + (k % a_block_cols) / 32.  a_block_cols % 128 == 0 (a K step of 128
+ *      bytes and its 4-byte scale piece never straddle a plane), K % a_block_cols == 0, a_block_stride % 128 == 0 and
+ *      >= M * a_block_cols.  a_block_cols 0 = plain (then a_block_stride is ignored).
+ *   C: logical C[m][n] at C + (n / c_block_cols) * c_block_stride + m * ldc + n % c_block_cols (elements).  c_block_cols a power
+ *      of two >= 256 dividing N, ldc >= c_block_cols, c_block_stride % 4 == 0 and >= (M - 1) * ldc + c_block_cols (planes do not
+ *      overlap; rows past M are not stored, so nothing lands in the next plane).  c_block_cols 0 = plain (ldc >= N).
+ *   W / SW, gate and the residual stay plain.  Product, rounding points, epilogues and every other requirement are those of
+ *   drn_gemm_mxfp8: the same kernel (256 x 256 tile, rings, lane maps, swizzle) with the plane addressing as a template flag, so a
+ *   blocked product equals the plain one on the same data bit for bit.  It always runs on that kernel - the few-token kernel has
+ *   no blocked layouts.  Anything outside the contract: DRN_EINVAL, nothing launched. */
+int drn_gemm_mxfp8_blocked(const void* A, const void* SA, const void* W, const void* SW, void* C, int64_t M, int64_t N, int64_t K,
+                           int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
+                           int64_t a_block_cols, int64_t a_block_stride, int64_t c_block_cols, int64_t c_block_stride,
+                           void* stream);
 /* ---- the same product for few tokens (one clip of 256 .. 1024 rows; csrc/gemm_mx_tall.hip): a workgroup owns a tile of one
  * clip's rows x a narrow column band (128 x 128 or 256 x 64) over the whole K or over one of `splits` K slices, so that enough
  * CUs stream the weights.  Operands, format and lane maps are those of drn_gemm_mxfp8.
