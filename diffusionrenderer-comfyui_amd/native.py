@@ -113,6 +113,7 @@ SIGNATURES = {
     "drn_edm_step": [_P, _P, _P, _L, _F, _F, _F, _F, _P],
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
@@ -809,6 +810,24 @@ def postprocess_u8(video, normalize_normal: bool):
     out = torch.empty((B, T, H, W, 3), dtype=torch.uint8, device=video.device)
     _check(load_library().drn_postprocess_u8(_ptr(video), _ptr(out), B, T, H, W, 1 if normalize_normal else 0, _stream()),
            "drn_postprocess_u8")
+    return out
+
+
+def env_project(cube, vec, rot, log_scale=10000.0, out=None):
+    """The forward renderer's environment light under a per-frame y-rotation (drn_env_project).  cube [6, R, R, 3], vec [H, W, 3]
+    (latlong_vec), rot [T, 2] = (cos, sin) of every frame's angle, all fp32 and contiguous -> (env_ldr, env_log), each
+    [3, T, H, W] fp32 in [-1, 1].  out: a pair of such tensors to write into."""
+    for t in (cube, vec, rot):
+        assert t.dtype == torch.float32 and t.is_contiguous(), "contiguous fp32 tensor required"
+    R, (H, W), T = cube.shape[1], vec.shape[:2], rot.shape[0]
+    assert cube.shape == (6, R, R, 3) and vec.shape == (H, W, 3) and rot.shape == (T, 2)
+    if out is None:
+        out = (torch.empty((3, T, H, W), dtype=torch.float32, device=cube.device),
+               torch.empty((3, T, H, W), dtype=torch.float32, device=cube.device))
+    for t in out:
+        assert t.dtype == torch.float32 and t.shape == (3, T, H, W) and t.is_contiguous()
+    _check(load_library().drn_env_project(_ptr(cube), R, _ptr(vec), _ptr(rot), _ptr(out[0]), _ptr(out[1]), T, H, W, log_scale,
+                                          _stream()), "drn_env_project")
     return out
 
 

@@ -158,7 +158,8 @@ class Cosmos1ForwardRenderer:
                          "env_format": (["proj", "ball"], {"default": "proj"}),
                          "env_brightness": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 2.0, "step": 0.1}),
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
-                         "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0})},
+                         "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
+                         "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0})},
         }
 
     RETURN_TYPES = ("IMAGE",)
@@ -166,7 +167,8 @@ class Cosmos1ForwardRenderer:
     CATEGORY = "Cosmos1"
 
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
-                         env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0):
+                         env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
+                         env_spin=0.0):
         pipeline.set_model_type("forward")
         pipeline.guidance = guidance
         pipeline.seed = seed
@@ -179,10 +181,11 @@ class Cosmos1ForwardRenderer:
             data_batch[key_mapping[name]] = t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
         B, _, T, H, W = data_batch["depth"].shape
         data_batch["video"] = data_batch["depth"]
-        # env-map conditions (env_ldr / env_log / env_nrm): one-shot preprocessing outside the denoise loop (reference :283-304)
+        # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
+        # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static
         from . import preprocess_envmap as pe
         env = pe.envmap_conditions(env_map, (H, W), T, env_format, env_brightness, env_flip_horizontal, env_rotation,
-                                   device=getattr(pipeline, "device", "cuda"))
+                                   device=getattr(pipeline, "device", "cuda"), env_spin=env_spin)
         data_batch["env_ldr"] = env["env_ldr"].expand(B, -1, -1, -1, -1)
         data_batch["env_log"] = env["env_log"].expand(B, -1, -1, -1, -1)
         data_batch["env_nrm"] = env["env_nrm"].expand(B, -1, T, -1, -1)

@@ -1,10 +1,15 @@
 """Environment-map conditions of the forward (relighting) renderer: env_ldr / env_log / env_nrm.
 
-One-shot preprocessing per clip, outside the denoising loop, so this is plain torch on
-the device - no HIP kernels.  Mirrors the public functions the reference's forward node imports (nodes.py:25-31):
+Preprocessing per clip, outside the denoising loop.  With static lighting it runs once and is
+plain torch on the device.  Mirrors the public functions the reference's forward node imports (nodes.py:25-31):
 render_projection_from_panorama (:408-467), tonemap_image_direct (:469-526), latlong_vec (:320-338),
 clear_environment_cache, get_cache_stats, with the same tone-mapping arithmetic (rgb2srgb :109-113, reinhard :115-117,
-hdr_mapping :119-140), HDR clean-up (:263-286) and lat-long -> cube-map resampling (:161-206).
+hdr_mapping :119-140), HDR clean-up (:263-286) and lat-long -> cube-map resampling (:161-206); all of these are pinned to the
+reference's own functions by tests/golden/envmap.safetensors (tests/test_envmap_spin_cpu.py).
+
+env_spin (degrees over the clip) fills in the reference's unused per-frame hook `y_rot = rotate_y(0.0)` (:340-348, :442): frame
+t of T is projected under the y-rotation radians(env_spin) * t / T.  The per-frame torch loop (project_frame) specifies it and
+is what CPU devices run; on a GPU one launch of drn_env_project (csrc/envmap.hip) projects every frame.
 
 One deliberate difference: the reference projects the cube map with nvdiffrast (`dr.texture(..., boundary_mode='cube')`,
 :448-449), a CUDA-only third-party library that is neither installed here nor portable to ROCm.  `cube_lookup` below is
@@ -202,25 +207,90 @@ def _frames(t: torch.Tensor, n: int) -> torch.Tensor:
     return t.unsqueeze(0).expand(n, -1, -1, -1) if n > 1 else t.unsqueeze(0)
 
 
-def render_projection_from_panorama(env_input, resolution: Tuple[int, int], env_brightness: float = 1.0, env_flip: bool = True,
-                                    env_rot: float = 180.0, device="cuda", num_frames: int = 1, use_cache: bool = True,
-                                    **kwargs) -> Dict[str, torch.Tensor]:
-    """Panorama -> 512^2 cube map -> lat-long projection -> tone maps: {'env_ldr','env_log'} as (T, H, W, 3)."""
+# ---------------------------------------------------------------------------------------------- rotating light (env_spin)
+def rotate_y(angle: float, device="cpu") -> torch.Tensor:
+    """4x4 rotation about +Y, fp32 from fp64 np.cos / np.sin (reference :340-348)."""
+    c, s = np.cos(angle), np.sin(angle)
+    return torch.tensor([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1]], dtype=torch.float32, device=device)
+
+
+def spin_angles(env_spin: float, num_frames: int):
+    """theta_t = radians(env_spin) * t / T of every frame: env_spin = 360 is one full turn over the clip."""
+    return [float(np.radians(env_spin)) * t / num_frames for t in range(num_frames)]
+
+
+def spin_table(env_spin: float, num_frames: int) -> torch.Tensor:
+    """[T, 2] fp32 (cos theta_t, sin theta_t): the entries of rotate_y(theta_t), as drn_env_project takes them (host tensor)."""
+    return torch.stack([rotate_y(a)[0, [0, 2]] for a in spin_angles(env_spin, num_frames)])
+
+
+def project_frame(cubemap: torch.Tensor, vec: torch.Tensor, y_rot: torch.Tensor, log_scale: float = 10000.0) -> Dict[str, torch.Tensor]:
+    """One frame of the projection at the reference's rotation hook (:441-450): vec (H, W, 3) turned by the 4x4 y_rot, looked up,
+    flipped and tone-mapped.  This loop body is the specification of drn_env_project (csrc/envmap.hip)."""
+    H, W = vec.shape[:2]
+    vq = (vec.view(-1, 3) @ y_rot[:3, :3].T).view(H, W, 3)
+    return hdr_mapping_official(torch.flip(cube_lookup(cubemap, -vq), dims=[0, 1]), log_scale=log_scale)
+
+
+def _projection(env_input, resolution, env_brightness, env_flip, env_rot, device, num_frames, use_cache, env_spin, backend):
+    """The cached worker behind render_projection_from_panorama / envmap_conditions.  Returns a dict: the torch path holds
+    'env_ldr' / 'env_log' as (T, H, W, 3) in [0, 1]; the kernel path holds 'cond_ldr' / 'cond_log' as [3, T, H, W] in [-1, 1]."""
+    if backend not in ("auto", "torch", "hip"):
+        raise ValueError(f"unknown backend {backend!r}")
+    on_gpu = torch.device(device).type == "cuda"
+    if backend == "hip" and not on_gpu:
+        raise ValueError(f"backend='hip' needs a GPU device, got {device!r} (the torch path is what CPU devices run)")
+    use_hip = backend == "hip" or (backend == "auto" and env_spin != 0 and on_gpu)
+    # the cache key tells (env_spin, num_frames) apart through the format string; static lighting keeps the key it had
+    fmt = ("proj" if env_spin == 0 else f"proj_spin{float(env_spin)}_T{num_frames}") + ("_hip" if use_hip else "")
     if use_cache:
         h = compute_tensor_hash(env_input) if isinstance(env_input, torch.Tensor) else hashlib.md5(str(env_input).encode()).hexdigest()
-        hit = _env_cache.get(h, resolution, "proj", env_brightness, env_flip, env_rot)
+        hit = _env_cache.get(h, resolution, fmt, env_brightness, env_flip, env_rot)
         if hit is not None:
-            return hit
+            return _expand_static(hit, num_frames)
     H, W = resolution
     latlong = apply_hdr_preprocessing(_load(env_input), env_brightness, env_flip, env_rot, device)
     cubemap = latlong_to_cubemap_official(latlong, [512, 512])
-    vec = latlong_vec((H, W), device=device)                 # camera = identity, y-rotation 0 (reference :441-446)
-    env_proj = torch.flip(cube_lookup(cubemap, -vec), dims=[0, 1])
-    m = hdr_mapping_official(env_proj, log_scale=10000.0)
-    result = {"env_ldr": _frames(m["env_ev0"], num_frames), "env_log": _frames(m["env_log"], num_frames)}
+    vec = latlong_vec((H, W), device=device)
+    if use_hip:
+        from . import native                      # all frames in one launch, written in the conditions' final layout and range
+        rot = spin_table(env_spin, num_frames if env_spin != 0 else 1).to(cubemap.device)
+        ldr, log = native.env_project(cubemap.contiguous(), vec.contiguous(), rot, 10000.0)
+        result = {"cond_ldr": ldr, "cond_log": log}        # static light: ONE frame, cached as such (its key carries no T)
+    elif env_spin == 0:
+        # camera = identity, y-rotation 0 (reference :441-446)
+        env_proj = torch.flip(cube_lookup(cubemap, -vec), dims=[0, 1])
+        m = hdr_mapping_official(env_proj, log_scale=10000.0)
+        result = {"env_ldr": _frames(m["env_ev0"], num_frames), "env_log": _frames(m["env_log"], num_frames)}
+    else:
+        ms = [project_frame(cubemap, vec, rotate_y(a, device=device)) for a in spin_angles(env_spin, num_frames)]
+        result = {"env_ldr": torch.stack([m["env_ev0"] for m in ms]), "env_log": torch.stack([m["env_log"] for m in ms])}
     if use_cache:
-        _env_cache.put(h, resolution, "proj", env_brightness, env_flip, env_rot, result)
-    return result
+        _env_cache.put(h, resolution, fmt, env_brightness, env_flip, env_rot, result)
+    return _expand_static(result, num_frames)
+
+
+def _expand_static(d, num_frames):
+    """The kernel path's one static frame [3, 1, H, W] expanded over the clip, after the cache (everything else: as stored)."""
+    if "cond_ldr" in d and d["cond_ldr"].shape[1] == 1 and num_frames > 1:
+        return {k: v.expand(-1, num_frames, -1, -1) for k, v in d.items()}
+    return d
+
+
+def render_projection_from_panorama(env_input, resolution: Tuple[int, int], env_brightness: float = 1.0, env_flip: bool = True,
+                                    env_rot: float = 180.0, device="cuda", num_frames: int = 1, use_cache: bool = True,
+                                    env_spin: float = 0.0, backend: str = "auto", **kwargs) -> Dict[str, torch.Tensor]:
+    """Panorama -> 512^2 cube map -> lat-long projection -> tone maps: {'env_ldr','env_log'} as (T, H, W, 3) in [0, 1].
+
+    env_spin (degrees): frame t of T is projected under the y-rotation radians(env_spin) * t / T, at the reference's own
+    rotate_y hook; 0 = today's static light, one image expanded over T.  backend: 'auto' = the HIP kernel (drn_env_project) when
+    the light turns and the device is a GPU, else torch (static lighting keeps its bits); 'torch' / 'hip' force a path.  The
+    kernel writes the conditions' [-1, 1] tensors; what this function returns from them is (c + 1) / 2, permuted - a view
+    in this function's layout, within one rounding of the tone maps themselves (envmap_conditions hands on the kernel's own)."""
+    d = _projection(env_input, resolution, env_brightness, env_flip, env_rot, device, num_frames, use_cache, env_spin, backend)
+    if "env_ldr" in d:
+        return d
+    return {"env_ldr": (d["cond_ldr"].permute(1, 2, 3, 0) + 1.0) * 0.5, "env_log": (d["cond_log"].permute(1, 2, 3, 0) + 1.0) * 0.5}
 
 
 def tonemap_image_direct(env_input, resolution: Tuple[int, int], device="cuda", num_frames: int = 1, use_cache: bool = True,
@@ -243,15 +313,21 @@ def tonemap_image_direct(env_input, resolution: Tuple[int, int], device="cuda", 
 
 
 def envmap_conditions(env_map, resolution, num_frames, env_format="proj", env_brightness=1.0, env_flip=False, env_rot=0.0,
-                      device="cuda") -> Dict[str, torch.Tensor]:
-    """The three forward-renderer conditions as (1, 3, T|1, H, W) tensors in [-1, 1] / unit vectors (reference nodes.py:283-304)."""
+                      device="cuda", env_spin=0.0, backend="auto") -> Dict[str, torch.Tensor]:
+    """The three forward-renderer conditions as (1, 3, T|1, H, W) tensors in [-1, 1] / unit vectors (reference nodes.py:283-304).
+    env_spin / backend: see render_projection_from_panorama.  env_nrm holds camera-space directions and does not turn."""
     if env_format == "proj":
-        d = render_projection_from_panorama(env_map, resolution, env_brightness, env_flip, env_rot, device, num_frames)
+        d = _projection(env_map, resolution, env_brightness, env_flip, env_rot, device, num_frames, True, env_spin, backend)
     elif env_format == "ball":
+        if env_spin != 0:
+            raise ValueError("env_spin needs env_format='proj': a pre-rendered ball cannot be rotated")
         d = tonemap_image_direct(env_map, resolution, device, num_frames)
     else:
         raise ValueError(f"unknown env_format {env_format!r}")
-    env_ldr = d["env_ldr"].permute(3, 0, 1, 2).unsqueeze(0) * 2.0 - 1.0
-    env_log = d["env_log"].permute(3, 0, 1, 2).unsqueeze(0) * 2.0 - 1.0
+    if "cond_ldr" in d:            # the kernel wrote the final layout and range
+        env_ldr, env_log = d["cond_ldr"].unsqueeze(0), d["cond_log"].unsqueeze(0)
+    else:
+        env_ldr = d["env_ldr"].permute(3, 0, 1, 2).unsqueeze(0) * 2.0 - 1.0
+        env_log = d["env_log"].permute(3, 0, 1, 2).unsqueeze(0) * 2.0 - 1.0
     env_nrm = latlong_vec(resolution, device=device).permute(2, 0, 1).unsqueeze(0).unsqueeze(2)
     return {"env_ldr": env_ldr, "env_log": env_log, "env_nrm": env_nrm}

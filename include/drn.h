@@ -1,5 +1,6 @@
 /* drn.h - C ABI of libdrn.so: the MI355X (gfx950) kernels behind the DiffusionRenderer
- * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer).
+ * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer),
+ * and the forward renderer's per-frame environment-light projection (drn_env_project).
  *
  * The reference (eggsbenedicto/DiffusionRenderer-ComfyUI) is pure Python/torch and has no FFI;
  * each entry point below names the reference code (file:line under /root/reference) whose
@@ -469,6 +470,19 @@ int drn_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, 
 /* ---- pipeline post-process (diffusion_renderer_pipeline.py:299-318): optional normal re-normalisation blend,
  * (1+v).clamp(0,2)/2, permute to (B,T,H,W,C), *255, truncating uint8 cast.  video: [B,3,T,H,W] bf16. Bit-exact. */
 int drn_postprocess_u8(const void* video, void* out_u8, int B, int T, int H, int W, int normalize_normal, void* stream);
+
+/* ---- environment light of the forward renderer, turning about +Y over the clip (preprocess_envmap.py:440-450 with the unused
+ * per-frame hook `y_rot = rotate_y(0.0)` (:340-348, :442) filled in, then hdr_mapping_official :119-140 and the `* 2 - 1` /
+ * permute of nodes.py:283-304).  One launch over T*H*W pixels, one thread per output pixel of one frame: the direction
+ * vec[h][w] is rotated by frame t's (cos, sin) = rot[t] (q = vec @ rotate_y(theta_t)[:3,:3].T), negated, looked up in the cube
+ * map (major-axis face chosen by `ax >= ay && ax >= az`, then `ay >= az`; per-face bilinear fetch with grid_sample's
+ * align_corners=False arithmetic and border clamp - the project's own replacement of nvdiffrast's dr.texture, :446), tone
+ * mapped (reinhard + clamp + sRGB -> env_ldr; log1p / log1p(log_scale) + sRGB + clamp -> env_log) and stored at the flipped
+ * position (H-1-h, W-1-w), scaled to [-1, 1].  All tensors fp32 and contiguous: cube [6,R,R,3], vec [H,W,3] (latlong_vec),
+ * rot [T,2], outputs [3,T,H,W].  Accurate powf / log1pf / division, torch's rounding order.  DRN_EINVAL: a null pointer, R, T, H
+ * or W < 1, T*H*W >= 2^31, a pointer not 4-byte aligned. */
+int drn_env_project(const float* cube, int R, const float* vec, const float* rot, float* env_ldr, float* env_log,
+                    int T, int H, int W, float log_scale, void* stream);
 
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).

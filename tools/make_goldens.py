@@ -6,7 +6,7 @@
 The reference (/root/reference) never travels to the GPU box, so its outputs are
 committed as small fixtures.  Weights and inputs are NOT stored: they come from
 the build-owned hash generator (synthetic_weights.py), which produces identical
-bits on any machine.  Each file's metadata records how it was produced,
+bits on any machine (envmap.safetensors alone carries its small panorama, as 'in.pano').  Each file's metadata records how it was produced,
 including the F1 head-flatten patch applied in memory.
 
 While generating, the script asserts that oracle/dit_oracle.py reproduces the
@@ -15,6 +15,7 @@ reference bit-for-bit (that is what pins the oracle).
 import argparse
 import gc
 import json
+import math
 import os
 import sys
 import time
@@ -477,6 +478,83 @@ def live_case(ref):
     return {"out.bf16": y.contiguous()}, meta
 
 
+ENVMAP_STANDINS = ("cv2", "imageio", "imageio.v3", "nvdiffrast", "nvdiffrast.torch")
+ENVMAP_ANGLES = {"0": 0.0, "37": 37.0, "90": 90.0, "m45": -45.0}          # degrees
+
+
+def load_reference_envmap():
+    """The reference's preprocess_envmap.py, imported under oracle/ref_import.py's synthetic parent package.  Its imports of
+    cv2 / imageio / nvdiffrast (file loading and the CUDA-only cube fetch, none of which is run here) resolve to empty stand-in
+    modules for the duration of the import, wherever the real module is missing."""
+    import importlib
+    import types
+    from oracle import ref_import
+    added = []
+    for n in ENVMAP_STANDINS:
+        if n not in sys.modules:
+            try:
+                importlib.import_module(n)
+            except ImportError:
+                sys.modules[n] = types.ModuleType(n)
+                added.append(n)
+    dont_write, sys.dont_write_bytecode = sys.dont_write_bytecode, True
+    try:
+        return importlib.import_module(ref_import._PKG + ".preprocess_envmap")
+    finally:
+        sys.dont_write_bytecode = dont_write
+        for n in added:
+            del sys.modules[n]
+
+
+def envmap_inputs():
+    """The synthetic HDR panorama (1, 16, 32, 3): |u|^4 * 50 with one NaN, +inf, -inf, 0 and 65504 texel each."""
+    pano = sw.synth_tensor("envmap.pano", (1, 16, 32, 3), torch.float32).abs().pow(4) * 50.0
+    pano[0, 2, 5, 0] = float("nan")
+    pano[0, 3, 9, 1] = float("inf")
+    pano[0, 4, 1, 2] = float("-inf")
+    pano[0, 8, 20] = 0.0
+    pano[0, 11, 27] = 65504.0
+    return pano
+
+
+def envmap_case(ref):
+    """Environment-map preprocessing through the REFERENCE's own functions on CPU: everything of
+    preprocess_envmap.py but the nvdiffrast texel fetch (:446).  The inputs are stored next to the outputs ('in.*')."""
+    rpe = load_reference_envmap()
+    out = {}
+    pano = envmap_inputs()
+    out["in.pano"] = pano
+    variants = {"bhwc": pano, "bchw": pano.permute(0, 3, 1, 2).contiguous(), "rgba": torch.cat([pano, torch.ones_like(pano[..., :1])], -1),
+                "gray": pano[..., :1].contiguous(), "hwc": pano[0]}
+    for k, v in variants.items():
+        out["process_comfyui_tensor." + k] = rpe.process_comfyui_tensor(v.clone())
+    latlong = out["process_comfyui_tensor.bhwc"]
+    for flip in (False, True):
+        for rot in (0, 90, 180):
+            out[f"apply_hdr_preprocessing.b0.7.flip{int(flip)}.rot{rot}"] = rpe.apply_hdr_preprocessing(latlong.clone(), 0.7, flip, float(rot), "cpu")
+    clean = out["apply_hdr_preprocessing.b0.7.flip0.rot0"]
+    assert torch.isfinite(clean).all() and clean.max() == 65504.0 and clean.min() == 0.0
+    cube = rpe.latlong_to_cubemap_official(clean, [16, 16])
+    out["latlong_to_cubemap_official.16x16"] = cube
+    for H, W in ((9, 14), (6, 20)):
+        out[f"latlong_vec.{H}x{W}"] = rpe.latlong_vec((H, W), device="cpu")
+    m = rpe.hdr_mapping_official(cube, log_scale=10000.0)
+    out["hdr_mapping_official.env_ev0"], out["hdr_mapping_official.env_log"] = m["env_ev0"], m["env_log"]
+    vec = out["latlong_vec.9x14"]
+    for tag, deg in ENVMAP_ANGLES.items():
+        ry = rpe.rotate_y(math.radians(deg), device="cpu")
+        out[f"rotate_y.{tag}"] = ry
+        out[f"vec_rotated.{tag}"] = vec.view(-1, 3) @ ry[:3, :3].T           # the expression of the reference's hook (:444-445)
+    for tag, res in (("native", (16, 32)), ("resized", (10, 14))):
+        d = rpe.tonemap_image_direct(clean.clone(), res, device="cpu", num_frames=2, use_cache=False)
+        out[f"tonemap_image_direct.{tag}.env_ldr"], out[f"tonemap_image_direct.{tag}.env_log"] = d["env_ldr"], d["env_log"]
+    meta = dict(META_COMMON, case="envmap preprocessing", weights="none",
+                standins="empty modules for " + ", ".join(ENVMAP_STANDINS) + " during the import (none of their code runs)",
+                angles_deg=json.dumps(ENVMAP_ANGLES), rotate_y_angle="math.radians(deg)",
+                inputs="in.pano = |synth_tensor('envmap.pano',(1,16,32,3),fp32)|^4*50 with NaN/+inf/-inf/0/65504 texels (stored)")
+    return out, meta
+
+
 def save(name, tensors, meta):
     os.makedirs(GOLD, exist_ok=True)
     path = os.path.join(GOLD, name)
@@ -523,6 +601,8 @@ def main():
         save("conditions.safetensors", *conditions_case(ref))
     if want("configs"):
         configs_case(ref)
+    if want("envmap"):
+        save("envmap.safetensors", *envmap_case(ref))
     if want("live"):
         save("dit_live_tiny.safetensors", *live_case(ref))
     if args.full and want("fullwidth"):
