@@ -25,7 +25,7 @@ projections write / read the exchange slabs through the blocked MXFP8 GEMM, the 
 """
 import ctypes
 import math
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -56,6 +56,49 @@ def _pad_rows(w: torch.Tensor, mult: int) -> torch.Tensor:
     out = torch.zeros((npad, k), dtype=w.dtype, device=w.device)
     out[:n] = w
     return out
+
+
+class SpRoute(NamedTuple):
+    """What the self-attention blocks of one sharded forward do (sp_route)."""
+    layout: str                # "gather"; a2a: "slabs" (the projections write / read the rank-major slabs) or "regroup" (GEMM + pass)
+    amx: bool                  # the attention runs on the MXFP8 kernels
+    mx_return: bool = False    # a2a: the attention output goes home as e4m3 + scales
+    launches: tuple = ()       # a2a: native.attention_plan of the heads a rank holds
+    first_bands: int = 0       # a2a: token bands launch 0 completes, sent home under launch 1 (0 = the return as one collective)
+    o_mx: bool = False         # gather: O leaves the attention as MXFP8
+
+    def path(self) -> dict:
+        """HipDiT.sp_path: the route as tests and tools read it."""
+        ret = "none" if self.layout == "gather" else ("e4m3" if self.mx_return else "bf16")
+        return {"layout": self.layout, "return": ret, "attention": "mxfp8" if self.amx else "bf16"}
+
+
+def sp_route(D, heads, S, world, exchange, mx, amx_on, fused_mx, mx_return, split_return) -> SpRoute:
+    """The route of a sharded forward, from numbers and switches alone (host-only queries of native: no engine, no device).
+    mx / amx_on: MXFP8 linears / attention switched on; fused_mx: the producers write MXFP8; mx_return / split_return: the
+    engine's _mx_return / _split_return.  Asked once per forward, so a force switch of the library flipped in between is seen."""
+    if exchange == "gather":
+        amx = bool(amx_on and N.attention_mxfp8_choice(heads, S))              # per site, from ONE clip's tokens
+        # fused producers: O leaves the attention as MXFP8 (the 32x32x16 body has no MX epilogue: bf16 + the quantise launch)
+        return SpRoute("gather", amx, o_mx=bool(fused_mx and (amx or N.attention_mx_available())))
+    W, rows, hpr = D // world, S // world, heads // world
+    if mx:
+        # the MXFP8 slab GEMM always runs on the 256 x 256 kernel: taken where the plan of one clip's band rows picks that
+        # kernel anyway (the slab layout then changes no bit) and the planes meet its contract (drn.h)
+        slabs = (world > 1 and W >= 256 and W & (W - 1) == 0
+                 and N.mx_gemm_plan(rows, 2 * D, D) == 0 and N.mx_gemm_plan(rows, D, D) == 0)
+    else:
+        slabs = world > 1 and W >= 512 and N.gemm_blocked_ok(rows, 2 * D) and N.gemm_blocked_ok(rows, D)
+    amx = bool(amx_on and N.attention_mxfp8_choice(hpr, S))
+    # mxfp8: the output leaves the attention as e4m3 + scales and travels like that, where an MX epilogue exists and the receive
+    # side can consume the bytes as they are: as A planes (slabs), as they lie (one rank), or through the regroup kernel over
+    # byte pairs (scale rows of a multiple of 16 bytes); else bf16 goes home and is quantised there
+    mxret = bool(mx and mx_return and (amx or N.attention_mx_available()) and (slabs or world == 1 or (W // 32) % 16 == 0))
+    # the attention of a rank's heads is usually two launches (the q-blocks that fill whole rounds of the CUs, then the rest with
+    # its keys split): the token bands whose queries the first has finished go home while the second runs
+    launches = tuple(N.attention_plan(1, hpr, S, S))
+    nb = launches[0][1] // rows if len(launches) == 2 and split_return else 0
+    return SpRoute("slabs" if slabs else "regroup", amx, mxret, launches, nb)
 
 
 class HipDiT:
@@ -295,90 +338,91 @@ class HipDiT:
         return hit
 
     def _workspace(self, S, rows, B=1):
-        """Activation buffers for `rows` local tokens of S total, B clips stacked along the rows (one shape kept resident)."""
+        """Activation buffers for `rows` local tokens of S total, B clips stacked along the rows (one shape kept resident): the
+        residual stream and the token-local scratch that every exchange needs, then what the configured one adds."""
         key = (S, rows, B)
         ws = self._ws.get(key)
-        if ws is None:
-            D, dev, bf = self.D, self.device, torch.bfloat16
-            n = B * rows
-            ws = {"x": torch.empty((n, D), dtype=bf, device=dev), "h": torch.empty((n, D), dtype=bf, device=dev),
-                  "o": torch.empty((n, D), dtype=bf, device=dev),
-                  "u": torch.empty((n, int(D * self.net["mlp_ratio"])), dtype=bf, device=dev),
-                  "y": torch.empty((B * S, self.w_final.shape[0]), dtype=bf, device=dev)}
-            lib = N.load_library()
-            u8, f8 = torch.uint8, torch.float8_e4m3fn
-            if self.exchange != "none" and self._mx:
-                # sharded mxfp8: AQ | AS and UQ | US for this rank's band rows of every clip, laid out as on one GPU
-                hid = ws["u"].shape[1]
-                ws["act"] = torch.empty(lib.drn_dit_forward_mx_act_bytes(B, rows, D, hid), dtype=u8, device=dev)
-                ws["act_q_bytes"] = n * max(D, hid)
-                if self._mx_fused:
-                    ws["uact"] = torch.empty(lib.drn_dit_forward_mx_u_bytes(B, rows, hid), dtype=u8, device=dev)
-                    ws["uact_q_bytes"] = n * hid
-            if self.exchange != "none" and self._amx:
-                # MXFP8 attention over all S keys of the heads this rank attends (a2a: heads / world, Q of all tokens; gather: every
-                # head, Q of the band only): QQ | KQ | VT | QS | KS | VS by the layout rule of drn_dit_forward, one clip at a time
-                Da = D // self.world if self.exchange == "a2a" else D
-                lay = (ctypes.c_int64 * 8)()
-                N._check(lib.drn_dit_forward_mx_attn_layout(1, S, Da, lay), "drn_dit_forward_mx_attn_layout")
-                buf = torch.empty(lay[6], dtype=u8, device=dev)
-                Sp = lay[7]
-                shapes = ((S, Da), (S, Da), (1, Da // 128, 128, Sp), (S, Da // 32), (S, Da // 32), (1, Da // 128, 128, Sp // 32))
-                views = [buf[off:off + math.prod(shape)].view(shape) for off, shape in zip(lay, shapes)]
-                ws["mx_attn"] = buf
-                ws["mx_attn_views"] = (N.MxTensor(views[0].view(f8), views[3]), N.MxTensor(views[1].view(f8), views[4]),
-                                       views[2].view(f8), views[5])
-            if self.exchange == "none":
-                ws["qkv"] = torch.empty((B * S, 3 * D), dtype=bf, device=dev)      # q | k | v, fused projection
-                nb = lib.drn_dit_forward_gemm_workspace_bytes(B, S, D, ws["u"].shape[1], self.w_final.shape[0], self.kpad)
-                if self._mx:
-                    # the slices of the MXFP8 block linears share gemm_ws; AQ | AS: the quantised A operand of the next one
-                    nb = max(nb, lib.drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, ws["u"].shape[1]))
-                    kmax = max(D, ws["u"].shape[1])
-                    ws["act"] = torch.empty(lib.drn_dit_forward_mx_act_bytes(B, S, D, ws["u"].shape[1]), dtype=torch.uint8, device=dev)
-                    ws["act_q_bytes"] = n * kmax
-                    if self._mx_fused:
-                        # UQ | US: U as MXFP8 (MLP-up writes it while it reads AQ | AS)
-                        ws["uact"] = torch.empty(lib.drn_dit_forward_mx_u_bytes(B, S, ws["u"].shape[1]), dtype=torch.uint8, device=dev)
-                        ws["uact_q_bytes"] = n * ws["u"].shape[1]
-                ws["gemm_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-K partials (few tokens)
-                if self._amx:
-                    # MXFP8 attention: QQ | KQ | VT | QS | KS | VS in one buffer, at the offsets drn_dit_forward reads them (drn.h)
-                    lay = (ctypes.c_int64 * 8)()
-                    N._check(lib.drn_dit_forward_mx_attn_layout(B, S, D, lay), "drn_dit_forward_mx_attn_layout")
-                    buf = torch.empty(lay[6], dtype=torch.uint8, device=dev)
-                    Sp = lay[7]
-                    shapes = ((n, D), (n, D), (B, self.heads, 128, Sp), (n, D // 32), (n, D // 32), (B, self.heads, 128, Sp // 32))
-                    views = [buf[off:off + math.prod(shape)].view(shape) for off, shape in zip(lay, shapes)]
-                    qq, kq, vt = (v.view(torch.float8_e4m3fn) for v in views[:3])
-                    ws["mx_attn"] = buf
-                    ws["mx_attn_views"] = (N.MxTensor(qq, views[3]), N.MxTensor(kq, views[4]), vt, views[5])
-                nb = lib.drn_dit_forward_attn_workspace_bytes(B, self.heads, S)
-                ws["attn_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-KV partials
-            elif self.exchange == "a2a":
-                W = D // self.world                                                # columns of this rank's heads
-                ws["qb"] = torch.empty((rows, D), dtype=bf, device=dev)            # band projections: [rows][rank][W]
-                ws["kvb"] = torch.empty((rows, 2 * D), dtype=bf, device=dev)       #                   [rows][rank][k | v][W]
-                ws["sq"] = torch.empty((self.world, rows, W), dtype=bf, device=dev)        # send slabs, rank-major
-                ws["skv"] = torch.empty((self.world, rows, 2 * W), dtype=bf, device=dev)
-                ws["rq"] = torch.empty((S, W), dtype=bf, device=dev)               # all tokens, own heads
-                ws["rkv"] = torch.empty((S, 2 * W), dtype=bf, device=dev)
-                ws["oh"] = torch.empty((S, W), dtype=bf, device=dev)               # attention output, own heads
-                ws["oback"] = torch.empty((self.world, rows, W), dtype=bf, device=dev)
-                if self._mx:
-                    # the same two as MXFP8 (e4m3 return exchange), and the token-major regroup of the unfused layout
-                    ws["ohm"] = N.mx_empty(S, W, dev)
-                    ws["obm"] = N.MxTensor(torch.empty((self.world, rows, W), dtype=f8, device=dev),
-                                           torch.empty((self.world, rows, W // 32), dtype=u8, device=dev))
-                    ws["otm"] = N.mx_empty(rows, D, dev)
-            else:
-                ws["q"] = torch.empty((rows, D), dtype=bf, device=dev)             # local queries
-                ws["kv"] = torch.empty((S, 2 * D), dtype=bf, device=dev)           # k | v of ALL tokens (all-gathered)
-                if self._amx:
-                    ws["kb"] = torch.empty((rows, D), dtype=bf, device=dev)        # K of the band (gathered as MXFP8, not as bf16)
-                    ws["vfull"] = torch.empty((S, D), dtype=bf, device=dev)        # V of ALL tokens (all-gathered)
-            self._ws = {key: ws}
+        if ws is not None:
+            return ws
+        D, dev, bf, u8 = self.D, self.device, torch.bfloat16, torch.uint8
+        n, hid = B * rows, int(D * self.net["mlp_ratio"])
+        ws = {"x": torch.empty((n, D), dtype=bf, device=dev), "h": torch.empty((n, D), dtype=bf, device=dev),
+              "o": torch.empty((n, D), dtype=bf, device=dev), "u": torch.empty((n, hid), dtype=bf, device=dev),
+              "y": torch.empty((B * S, self.w_final.shape[0]), dtype=bf, device=dev)}
+        lib = N.load_library()
+
+        def mx_view(buf, K, q_bytes):
+            """[n, K] MXFP8 over a byte buffer laid out as drn_dit_forward takes it: elements from the start, scales from q_bytes."""
+            return N.MxTensor(buf[:n * K].view(torch.float8_e4m3fn).view(n, K), buf[q_bytes:q_bytes + n * (K // 32)].view(n, K // 32))
+        if self._mx:
+            # AQ | AS: the quantised A operand of the next block linear (H or O as MXFP8; sized for the K = hidden operand too)
+            ws["act"] = torch.empty(lib.drn_dit_forward_mx_act_bytes(B, rows, D, hid), dtype=u8, device=dev)
+            ws["act_mx"] = mx_view(ws["act"], D, n * max(D, hid))
+            if self._mx_fused:
+                # UQ | US: U as MXFP8 (MLP-up writes it while it reads AQ | AS)
+                ws["uact"] = torch.empty(lib.drn_dit_forward_mx_u_bytes(B, rows, hid), dtype=u8, device=dev)
+                ws["uact_mx"] = mx_view(ws["uact"], hid, n * hid)
+        {"none": self._ws_local, "a2a": self._ws_a2a, "gather": self._ws_gather}[self.exchange](ws, S, rows, B)
+        self._ws = {key: ws}
         return ws
+
+    def _mx_attn_views(self, ws, B, S, Da):
+        """MXFP8 attention operands of Da / 128 heads over S tokens of B clips: QQ | KQ | VT | QS | KS | VS in one buffer, at the
+        offsets drn_dit_forward reads them (drn.h); as (q, k: MxTensor [B * S, Da]; vt, vs of mx_quant_vt)."""
+        lay = (ctypes.c_int64 * 8)()
+        N._check(N.load_library().drn_dit_forward_mx_attn_layout(B, S, Da, lay), "drn_dit_forward_mx_attn_layout")
+        buf = torch.empty(lay[6], dtype=torch.uint8, device=self.device)
+        n, heads, Sp = B * S, Da // 128, lay[7]
+        shapes = ((n, Da), (n, Da), (B, heads, 128, Sp), (n, Da // 32), (n, Da // 32), (B, heads, 128, Sp // 32))
+        views = [buf[off:off + math.prod(shape)].view(shape) for off, shape in zip(lay, shapes)]
+        qq, kq, vt = (v.view(torch.float8_e4m3fn) for v in views[:3])
+        ws["mx_attn"] = buf
+        ws["mx_attn_views"] = (N.MxTensor(qq, views[3]), N.MxTensor(kq, views[4]), vt, views[5])
+
+    def _ws_local(self, ws, S, rows, B):
+        """No exchange: the buffers of drn_dit_forward (the per-launch path uses the same ones)."""
+        D, dev, hid = self.D, self.device, ws["u"].shape[1]
+        lib = N.load_library()
+        ws["qkv"] = torch.empty((B * S, 3 * D), dtype=torch.bfloat16, device=dev)      # q | k | v, fused projection
+        nb = lib.drn_dit_forward_gemm_workspace_bytes(B, S, D, hid, self.w_final.shape[0], self.kpad)
+        if self._mx:
+            nb = max(nb, lib.drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, hid))    # the slices of the MXFP8 linears share it
+        ws["gemm_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-K partials (few tokens)
+        if self._amx:
+            self._mx_attn_views(ws, B, S, D)
+        nb = lib.drn_dit_forward_attn_workspace_bytes(B, self.heads, S)
+        ws["attn_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None      # split-KV partials
+
+    def _ws_a2a(self, ws, S, rows, B):
+        """Head <-> token all-to-all, one clip at a time: band projections, send / receive slabs, the attention of own heads."""
+        D, dev, bf, world = self.D, self.device, torch.bfloat16, self.world
+        W = D // world                                                     # columns of this rank's heads
+        ws["qb"] = torch.empty((rows, D), dtype=bf, device=dev)            # band projections: [rows][rank][W]
+        ws["kvb"] = torch.empty((rows, 2 * D), dtype=bf, device=dev)       #                   [rows][rank][k | v][W]
+        ws["sq"] = torch.empty((world, rows, W), dtype=bf, device=dev)     # send slabs, rank-major
+        ws["skv"] = torch.empty((world, rows, 2 * W), dtype=bf, device=dev)
+        ws["rq"] = torch.empty((S, W), dtype=bf, device=dev)               # all tokens, own heads
+        ws["rkv"] = torch.empty((S, 2 * W), dtype=bf, device=dev)
+        ws["oh"] = torch.empty((S, W), dtype=bf, device=dev)               # attention output, own heads
+        ws["oback"] = torch.empty((world, rows, W), dtype=bf, device=dev)
+        if self._mx:
+            # the same two as MXFP8 (e4m3 return exchange), and the token-major regroup of the unfused layout
+            ws["ohm"] = N.mx_empty(S, W, dev)
+            ws["obm"] = N.MxTensor(torch.empty((world, rows, W), dtype=torch.float8_e4m3fn, device=dev),
+                                   torch.empty((world, rows, W // 32), dtype=torch.uint8, device=dev))
+            ws["otm"] = N.mx_empty(rows, D, dev)
+        if self._amx:
+            self._mx_attn_views(ws, 1, S, W)                               # Q of all tokens, heads / world heads
+
+    def _ws_gather(self, ws, S, rows, B):
+        """K|V all-gather, one clip at a time: local queries against the keys and values of ALL tokens, every head."""
+        D, dev, bf = self.D, self.device, torch.bfloat16
+        ws["q"] = torch.empty((rows, D), dtype=bf, device=dev)             # local queries
+        ws["kv"] = torch.empty((S, 2 * D), dtype=bf, device=dev)           # k | v of ALL tokens (all-gathered)
+        if self._amx:
+            ws["kb"] = torch.empty((rows, D), dtype=bf, device=dev)        # K of the band (gathered as MXFP8, not as bf16)
+            ws["vfull"] = torch.empty((S, D), dtype=bf, device=dev)        # V of ALL tokens (all-gathered)
+            self._mx_attn_views(ws, 1, S, D)                               # Q of the band only
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -439,14 +483,7 @@ class HipDiT:
             else:
                 cv = torch.stack([self.context_vectors(c) for c in cis], 1)       # [n_ca, B, D]
                 addvec = (gates.unsqueeze(1) * cv).contiguous()
-        return self._run(x, cond, mod, modf, addvec, Tp, Hp, Wp, plan)
-
-    @staticmethod
-    def _mx_view(buf, q_bytes, rows, K):
-        """An MxTensor [rows, K] over a byte buffer laid out as drn_dit_forward is given AQ | AS / UQ | US: elements from the
-        start, scales from byte `q_bytes` (the offset the sequencer path passes as AS / US)."""
-        return N.MxTensor(buf[:rows * K].view(torch.float8_e4m3fn).view(rows, K),
-                          buf[q_bytes:q_bytes + rows * (K // 32)].view(rows, K // 32))
+        return self._run(x, cond, mod, modf, addvec, (Tp, Hp, Wp), plan)
 
     def _lin(self, a, w, out, epilogue=N.EPI_NONE, gate=None, residual=None, rows_per_batch=None):
         """A block linear (q|k|v, out-proj, MLP-up, MLP-down): the bf16 GEMM, or with precision 'mxfp8' the quantisation of
@@ -491,163 +528,139 @@ class HipDiT:
         N.permute_021(src.view(torch.uint8).view(torch.bfloat16),
                       out=dst.view(torch.uint8).view(rows, world * C).view(torch.bfloat16))
 
-    def _attend(self, q, k, v, heads, S, amx, launches, out, out_mx):
-        """The attention launches of `heads` heads over all S keys for the sharded paths, after norm + RoPE.  bf16: q [Sq, heads*128],
-        k / v [S, heads*128] views; amx: q / k MxTensors, v = (vt, vs) of mx_quant_vt.  launches: [(q0, q1, kv_splits)], or None
-        for the one call under the automatic plan.  The output goes to `out` (bf16 [Sq, heads*128]) or `out_mx` (an MxTensor).
-        A generator: it yields after every launch, so the caller can start the exchange of the rows that are finished."""
-        Sq = q.shape[0]
-        for q0, q1, ns in (launches if launches is not None else [(0, Sq, None)]):
-            o = out[q0:q1].unsqueeze(0) if out is not None else None
-            om = self._rows(out_mx, q0, q1) if out_mx is not None else None
-            if amx:
-                N.attention_mxfp8(self._rows(q, q0, q1), k, v[0], v[1], 1, q1 - q0, S, out=o, out_mx=om, kv_splits=ns)
-            else:
-                N.attention(q[q0:q1].unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=o, heads=heads, kv_splits=ns, out_mx=om)
-            yield q1
-
-    def _fa_sharded(self, sb, hin, X, O, ws, plan, cos, sin, gate, fused, omx):
-        """Self-attention sub-block of ONE clip's token band with an exchange (hin: modulated input rows - bf16, or the MxTensor a
-        fused LayerNorm wrote; X: residual stream rows, updated in place; O: scratch rows; omx: their MXFP8 twin or None)."""
-        D = self.D
-        S, rows, world = plan.S, plan.rows, plan.world
-        mx = self._mx
-        if mx:
-            hin = self._mxq(hin)                                 # one operand for the K|V and the Q projection
-        wq, wkv, wo = self._rows(sb["wqkv"], 0, D), self._rows(sb["wqkv"], D, 3 * D), sb["wo"]
-        res = dict(epilogue=N.EPI_GATE_RES, gate=gate, residual=X)
-        if self.exchange == "a2a":
-            # tokens -> heads: project the band, regroup rank-major, all-to-all; norm + RoPE + attention over all S
-            # tokens of this rank's heads; heads -> tokens: all-to-all back, regroup, output projection.
-            # K|V go first so their exchange (RCCL's stream, 2/3 of the bytes) overlaps the Q projection.
-            W, hpr = D // world, self.heads // world
-            Oh, oback, rq, rkv = ws["oh"], ws["oback"], ws["rq"], ws["rkv"]
-            amx = self._amx and N.attention_mxfp8_choice(hpr, S)               # per site, from ONE clip's tokens
-            # (the projections write the rank-major send slabs themselves where the tile kernel can; else a regroup pass)
-            if fused:
-                self._lin_planes(hin, wkv, ws["skv"], rows, c_planes=True)
-            else:
-                self._lin(hin, wkv, ws["kvb"])
-                N.permute_021(ws["kvb"].view(rows, world, 2 * W), out=ws["skv"])
-            work_kv = alltoall_rows_(ws["skv"], rkv.view(world, rows, 2 * W), self.pg, async_op=True)
-            if fused:
-                self._lin_planes(hin, wq, ws["sq"], rows, c_planes=True)
-            else:
-                self._lin(hin, wq, ws["qb"])
-                N.permute_021(ws["qb"].view(rows, world, W), out=ws["sq"])
-            work_q = alltoall_rows_(ws["sq"], rq.view(world, rows, W), self.pg, async_op=True)
-            wait_exchange(work_kv, "a2a k|v")
-            k, v = rkv[:, :W], rkv[:, W:]
-            if amx:
-                # q and k leave norm + RoPE as MXFP8, contiguous [S, W]; v is transposed and quantised along the keys
-                qm, km, vt, vs = ws["mx_attn_views"]
-                N.qk_norm_rope_mx(None, k, None, sb["kn"], cos, sin, hpr, tokens_per_batch=S, out_k=km)
-                N.mx_quant_vt(v.unsqueeze(0), hpr, out=(vt, vs))
-                wait_exchange(work_q, "a2a q")
-                N.qk_norm_rope_mx(rq, None, sb["qn"], None, cos, sin, hpr, tokens_per_batch=S, out_q=qm)
-                aq, ak, av = qm, km, (vt, vs)
-            else:
-                N.qk_norm_rope(None, k, None, sb["kn"], cos, sin, hpr, tokens_per_batch=S)
-                wait_exchange(work_q, "a2a q")
-                N.qk_norm_rope(rq, None, sb["qn"], None, cos, sin, hpr, tokens_per_batch=S)
-                aq, ak, av = rq, k, v
-            # mxfp8: the output leaves the attention as e4m3 + scales and travels like that, where an MX epilogue exists and the
-            # receive side can consume the bytes as they are: as A planes (fused), as they lie (one rank), or through the regroup
-            # kernel over byte pairs (scale rows of a multiple of 16 bytes); else bf16 goes home and is quantised there
-            mxret = (self._mx_return and (amx or N.attention_mx_available())
-                     and (fused or world == 1 or (W // 32) % 16 == 0))
-            self.sp_path = {"layout": "slabs" if fused else "regroup", "return": "e4m3" if mxret else "bf16",
-                            "attention": "mxfp8" if amx else "bf16"}
-            if mxret:
-                ohm, obm = ws["ohm"], ws["obm"]
-                send = (ohm.q.view(world, rows, W), ohm.scales.view(world, rows, W // 32))
-                recv = (obm.q, obm.scales)
-            else:
-                send, recv = Oh.view(world, rows, W), oback
-            # heads -> tokens.  The attention of a rank's heads is usually two launches (native.attention_plan: the
-            # q-blocks that fill whole rounds of the CUs, then the rest with its keys split): the token bands whose
-            # queries the first launch has finished go home while the second one runs, only the last bands' slabs
-            # (1 of 8 at world 8) travel exposed.  Same launches as the single call: same bits.
-            aplan = N.attention_plan(1, hpr, S, S)
-            nb = aplan[0][1] // rows if len(aplan) == 2 else 0             # complete bands of the first launch
-            split = nb >= 1 and self._split_return
-            att = self._attend(aq, ak, av, hpr, S, amx, aplan if split else None, None if mxret else Oh,
-                               ws["ohm"] if mxret else None)
-            if split:
-                next(att)
-                work0 = alltoall_bands_(send, recv, 0, nb, self.pg, async_op=True)
-                next(att)
-                work1 = alltoall_bands_(send, recv, nb, world, self.pg, async_op=True)
-                wait_exchange(work0, "a2a o (return, under the attention tail)")
-                wait_exchange(work1, "a2a o (return)")
-            else:
-                next(att)
-                work = alltoall_rows_(send, recv, self.pg, async_op=True)
-                wait_exchange(work, "a2a o (return)")
-            att.close()
-            if fused:
-                if mxret:
-                    a = ws["obm"]
-                elif mx:                                         # bf16 came home: quantise the slabs where they lie
-                    aq = self._mxq(oback.view(world * rows, W))
-                    a = N.MxTensor(aq.q.view(world, rows, W), aq.scales.view(world, rows, W // 32))
-                else:
-                    a = oback
-                self._lin_planes(a, wo, X, rows, a_planes=True, **res)
-                return
-            if mxret:
-                otm = ws["otm"]
-                if world == 1:
-                    otm = N.MxTensor(ws["obm"].q.view(rows, D), ws["obm"].scales.view(rows, D // 32))
-                else:
-                    self._regroup_bytes(ws["obm"].q, otm.q)
-                    self._regroup_bytes(ws["obm"].scales, otm.scales)
-                self._lin(otm, wo, X, **res)
-                return
-            N.permute_021(oback, out=O.view(rows, world, W))
+    def _attend(self, q, k, v, heads, amx, out, part=None):
+        """Enqueue the attention of `heads` heads over all keys for the sharded paths, after norm + RoPE.  bf16: q [Sq, heads*128],
+        k / v [S, heads*128] views; amx: q / k MxTensors, v = (vt, vs) of mx_quant_vt.  part: one (q0, q1, kv_splits) of
+        native.attention_plan, or None for all Sq queries under the automatic plan.  `out` ([Sq, heads*128], bf16 or an MxTensor
+        written by the MX epilogue) receives the rows of the queries."""
+        q0, q1, ns = part if part is not None else (0, q.shape[0], None)
+        o, om = (None, self._rows(out, q0, q1)) if isinstance(out, N.MxTensor) else (out[q0:q1].unsqueeze(0), None)
+        if amx:
+            N.attention_mxfp8(self._rows(q, q0, q1), k, v[0], v[1], 1, q1 - q0, k.shape[0], out=o, out_mx=om, kv_splits=ns)
         else:
-            # local projections; K|V land directly in this rank's band of the gather buffer.  K|V first, so the
-            # exchange (RCCL's own stream) overlaps the Q projection + q-norm; wait() orders attention after it.
-            q, KV = ws["q"], ws["kv"]
-            amx = self._amx and N.attention_mxfp8_choice(self.heads, S)
-            self.sp_path = {"layout": "gather", "return": "none", "attention": "mxfp8" if amx else "bf16"}
-            if amx:
-                # K of the band leaves norm + RoPE as MXFP8 and is gathered like that (half the bytes of the bf16 K gather); V is
-                # gathered in bf16 and transposed + quantised along ALL keys afterwards
-                qm, km, vt, vs = ws["mx_attn_views"]
-                qm = self._rows(qm, 0, rows)
-                kb, vfull = ws["kb"], ws["vfull"]
-                self._lin(hin, self._rows(sb["wqkv"], D, 2 * D), kb)
-                self._lin(hin, self._rows(sb["wqkv"], 2 * D, 3 * D), plan.band(vfull))
-                N.qk_norm_rope_mx(None, kb, None, sb["kn"], cos, sin, self.heads, tokens_per_batch=rows, pos_offset=plan.start,
-                                  out_k=self._rows(km, plan.start, plan.stop))
-                work = [allgather_rows_(t, plan, self.pg, async_op=True) for t in (km.q, km.scales, vfull)]
-                work = [w_ for w_ in work if w_ is not None] or None
+            N.attention(q[q0:q1].unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), out=o, heads=heads, kv_splits=ns, out_mx=om)
+
+    @staticmethod
+    def _norm_rope(which, x, w, rope, heads, out_mx=None, **where):
+        """RMSNorm + RoPE of the q or the k rows `x` (which: "q" / "k"): in place, or with `out_mx` written there as MXFP8
+        (x keeps its input).  where: tokens_per_batch, pos_offset of the rows."""
+        xs, ws_ = ((x, None), (w, None)) if which == "q" else ((None, x), (None, w))
+        if out_mx is None:
+            N.qk_norm_rope(*xs, *ws_, *rope, heads, **where)
+        else:
+            N.qk_norm_rope_mx(*xs, *ws_, *rope, heads, **where, **{"out_" + which: out_mx})
+
+    def _to_slabs(self, hin, w, band, slabs, route):
+        """A projection of the token band into the rank-major send slabs [world, rows, C] of the head <-> token exchange: written
+        there by the blocked GEMM, or as the plain GEMM into `band` [rows, world * C] + a regroup pass."""
+        world, rows, C = slabs.shape
+        if route.layout == "slabs":
+            self._lin_planes(hin, w, slabs, rows, c_planes=True)
+        else:
+            self._lin(hin, w, band)
+            N.permute_021(band.view(rows, world, C), out=slabs)
+
+    def _fa_a2a(self, sb, hin, ws, plan, rope, gate, route, b):
+        """Self-attention sub-block of clip b's token band with the head <-> token all-to-all, in launch order (hin: modulated input
+        of all clips - bf16, or the MxTensor a fused LayerNorm wrote; the residual stream ws["x"] is updated in place).
+        tokens -> heads: project the band into rank-major slabs, all-to-all; norm + RoPE + attention over all S tokens of this
+        rank's heads; heads -> tokens: all-to-all back, output projection."""
+        D, S, rows, world = self.D, plan.S, plan.rows, plan.world
+        W, hpr = D // world, self.heads // world
+        hin = self._rows(hin, b * rows, (b + 1) * rows)
+        if self._mx:
+            hin = self._mxq(hin)                                 # one operand for the K|V and the Q projection
+        rq, rkv = ws["rq"], ws["rkv"]
+        # K|V go first so their exchange (RCCL's stream, 2/3 of the bytes) overlaps the Q projection
+        self._to_slabs(hin, self._rows(sb["wqkv"], D, 3 * D), ws["kvb"], ws["skv"], route)
+        work_kv = alltoall_rows_(ws["skv"], rkv.view(world, rows, 2 * W), self.pg, async_op=True)
+        self._to_slabs(hin, self._rows(sb["wqkv"], 0, D), ws["qb"], ws["sq"], route)
+        work_q = alltoall_rows_(ws["sq"], rq.view(world, rows, W), self.pg, async_op=True)
+        # amx: q and k leave norm + RoPE as MXFP8, contiguous [S, W]; v is transposed and quantised along the keys
+        qm, km, vt, vs = ws["mx_attn_views"] if route.amx else (None,) * 4
+        wait_exchange(work_kv, "a2a k|v")
+        k, v = rkv[:, :W], rkv[:, W:]
+        self._norm_rope("k", k, sb["kn"], rope, hpr, km, tokens_per_batch=S)
+        if route.amx:
+            N.mx_quant_vt(v.unsqueeze(0), hpr, out=(vt, vs))
+        wait_exchange(work_q, "a2a q")
+        self._norm_rope("q", rq, sb["qn"], rope, hpr, qm, tokens_per_batch=S)
+        qkv = (qm, km, (vt, vs)) if route.amx else (rq, k, v)
+        if route.mx_return:
+            out, obm = ws["ohm"], ws["obm"]
+            send, recv = (out.q.view(world, rows, W), out.scales.view(world, rows, W // 32)), (obm.q, obm.scales)
+        else:
+            out = ws["oh"]
+            send, recv = out.view(world, rows, W), ws["oback"]
+        if route.first_bands:
+            # the bands whose queries launch 0 has finished go home while launch 1 runs: only the last bands' slabs (1 of 8 at
+            # world 8) travel exposed.  Same launches as the single call: same bits
+            self._attend(*qkv, hpr, route.amx, out, route.launches[0])
+            work0 = alltoall_bands_(send, recv, 0, route.first_bands, self.pg, async_op=True)
+            self._attend(*qkv, hpr, route.amx, out, route.launches[1])
+            work1 = alltoall_bands_(send, recv, route.first_bands, world, self.pg, async_op=True)
+            wait_exchange(work0, "a2a o (return, under the attention tail)")
+            wait_exchange(work1, "a2a o (return)")
+        else:
+            self._attend(*qkv, hpr, route.amx, out)
+            wait_exchange(alltoall_rows_(send, recv, self.pg, async_op=True), "a2a o (return)")
+        # out-projection from what came home: slabs as A planes, the bytes as they lie (one rank), byte-pair or bf16 regroup
+        X = ws["x"][b * rows:(b + 1) * rows]
+        res = dict(epilogue=N.EPI_GATE_RES, gate=gate, residual=X)
+        if route.layout == "slabs":
+            a = obm if route.mx_return else recv
+            if self._mx and not route.mx_return:                 # bf16 came home: quantise the slabs where they lie
+                aq = self._mxq(a.view(world * rows, W))
+                a = N.MxTensor(aq.q.view(world, rows, W), aq.scales.view(world, rows, W // 32))
+            self._lin_planes(a, sb["wo"], X, rows, a_planes=True, **res)
+        elif route.mx_return:
+            otm = ws["otm"]
+            if world == 1:
+                otm = N.MxTensor(obm.q.view(rows, D), obm.scales.view(rows, D // 32))
             else:
-                kv_loc = plan.band(KV)
-                self._lin(hin, wkv, kv_loc)
-                N.qk_norm_rope(None, kv_loc[:, :D], None, sb["kn"], cos, sin, self.heads,
-                               tokens_per_batch=rows, pos_offset=plan.start)
-                work = allgather_rows_(KV, plan, self.pg, async_op=True)     # the one exchange of the block (xGMI)
-            self._lin(hin, wq, q)
-            if amx:
-                N.qk_norm_rope_mx(q, None, sb["qn"], None, cos, sin, self.heads, tokens_per_batch=rows, pos_offset=plan.start,
-                                  out_q=qm)
-                wait_exchange(work, "gather k|v")
-                N.mx_quant_vt(vfull.unsqueeze(0), self.heads, out=(vt, vs))
-                aq, ak, av = qm, km, (vt, vs)
-            else:
-                N.qk_norm_rope(q, None, sb["qn"], None, cos, sin, self.heads, tokens_per_batch=rows, pos_offset=plan.start)
-                wait_exchange(work, "gather k|v")
-                aq, ak, av = q, KV[:, :D], KV[:, D:]
-            # fused producers: O leaves the attention as MXFP8 (the 32x32x16 body has no MX epilogue: bf16 + the quantise launch)
-            if omx is not None and not (amx or N.attention_mx_available()):
-                omx = None
-            for _ in self._attend(aq, ak, av, self.heads, S, amx, None, None if omx is not None else O, omx):
-                pass
-            if omx is not None:
-                O = omx
-        self._lin(O, wo, X, **res)
+                self._regroup_bytes(obm.q, otm.q)
+                self._regroup_bytes(obm.scales, otm.scales)
+            self._lin(otm, sb["wo"], X, **res)
+        else:
+            O = ws["o"][b * rows:(b + 1) * rows]
+            N.permute_021(recv, out=O.view(rows, world, W))
+            self._lin(O, sb["wo"], X, **res)
+
+    def _fa_gather(self, sb, hin, ws, plan, rope, gate, route, b):
+        """Self-attention sub-block of clip b's token band with the K|V all-gather, in launch order (hin, ws["x"] as _fa_a2a).
+        Local projections; K|V go first, so their exchange (RCCL's own stream) overlaps the Q projection + q-norm; the wait
+        orders the attention of the band's queries over ALL keys after it."""
+        D, heads, rows = self.D, self.heads, plan.rows
+        X, hin = ws["x"][b * rows:(b + 1) * rows], self._rows(hin, b * rows, (b + 1) * rows)
+        if self._mx:
+            hin = self._mxq(hin)                                 # one operand for the K|V and the Q projection
+        wqkv, q, KV = sb["wqkv"], ws["q"], ws["kv"]
+        where = dict(tokens_per_batch=rows, pos_offset=plan.start)
+        qm, km, vt, vs = ws["mx_attn_views"] if route.amx else (None,) * 4
+        if route.amx:
+            # K of the band leaves norm + RoPE as MXFP8 and is gathered like that (half the bytes of the bf16 K gather); V is
+            # gathered in bf16 and transposed + quantised along ALL keys afterwards
+            qm = self._rows(qm, 0, rows)
+            kb, vfull = ws["kb"], ws["vfull"]
+            self._lin(hin, self._rows(wqkv, D, 2 * D), kb)
+            self._lin(hin, self._rows(wqkv, 2 * D, 3 * D), plan.band(vfull))
+            self._norm_rope("k", kb, sb["kn"], rope, heads, self._rows(km, plan.start, plan.stop), **where)
+            work = [allgather_rows_(t, plan, self.pg, async_op=True) for t in (km.q, km.scales, vfull)]
+            work = [w_ for w_ in work if w_ is not None] or None
+        else:
+            kv_loc = plan.band(KV)
+            self._lin(hin, self._rows(wqkv, D, 3 * D), kv_loc)
+            self._norm_rope("k", kv_loc[:, :D], sb["kn"], rope, heads, **where)
+            work = allgather_rows_(KV, plan, self.pg, async_op=True)     # the one exchange of the block (xGMI)
+        self._lin(hin, self._rows(wqkv, 0, D), q)
+        self._norm_rope("q", q, sb["qn"], rope, heads, qm, **where)
+        wait_exchange(work, "gather k|v")
+        if route.amx:
+            N.mx_quant_vt(vfull.unsqueeze(0), heads, out=(vt, vs))
+        qkv = (qm, km, (vt, vs)) if route.amx else (q, KV[:, :D], KV[:, D:])
+        O = self._rows(ws["act_mx"] if route.o_mx else ws["o"], b * rows, (b + 1) * rows)
+        self._attend(*qkv, heads, route.amx, O)
+        self._lin(O, sb["wo"], X, epilogue=N.EPI_GATE_RES, gate=gate, residual=X)
 
     def _sequencer_args(self, ws, P, S, B, *, mod, modf, batched, addvec, rope):
         """The argument block of drn_dit_forward for this workspace (raw pointers: the caller keeps every tensor alive).
@@ -681,18 +694,18 @@ class HipDiT:
         a.eps = 1e-6
         if self._mx:
             a.precision = 1
-            a.AQ, a.AS = ws["act"].data_ptr(), ws["act"].data_ptr() + ws["act_q_bytes"]
+            a.AQ, a.AS = ws["act_mx"].q.data_ptr(), ws["act_mx"].scales.data_ptr()
             a.act_bytes = ws["act"].numel()
             if self._mx_fused:
                 a.mx_fused = 1
-                a.UQ, a.US = ws["uact"].data_ptr(), ws["uact"].data_ptr() + ws["uact_q_bytes"]
+                a.UQ, a.US = ws["uact_mx"].q.data_ptr(), ws["uact_mx"].scales.data_ptr()
                 a.u_act_bytes = ws["uact"].numel()
         if self._amx:
             a.attn_precision = 1
             a.mx_attn, a.mx_attn_bytes = ws["mx_attn"].data_ptr(), ws["mx_attn"].numel()
         return a
 
-    def _fa_local(self, sb, hin, ws, cos, sin, gate, S, B, fusedmx):
+    def _fa_local(self, sb, hin, ws, rope, gate, S, B, fusedmx):
         """Self-attention sub-block without an exchange, launch by launch (the launches of drn_dit_forward, in its order).
         hin: the modulated input (bf16 H, or the MxTensor a fused LayerNorm wrote)."""
         D = self.D
@@ -701,18 +714,17 @@ class HipDiT:
         q, k, v = QKV[:, :D], QKV[:, D:2 * D], QKV[:, 2 * D:]
         amx = self._amx and N.attention_mxfp8_choice(self.heads, S)      # per site, from ONE clip's tokens
         # fused producers: O leaves the attention as MXFP8; the 32x32x16 body has no MX epilogue and keeps bf16 + the quantise launch
-        omx = (self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D)
-               if fusedmx and (amx or N.attention_mx_available()) else None)
+        omx = ws["act_mx"] if fusedmx and (amx or N.attention_mx_available()) else None
         if amx:
             # MXFP8 attention (the launches of drn_dit_forward with attn_precision 1): q and k leave norm + RoPE
             # as MX (trace mode keeps the bf16 q and k as well), v is transposed and quantised along the keys
             qm, km, vt, vs = ws["mx_attn_views"]
-            N.qk_norm_rope_mx(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S,
+            N.qk_norm_rope_mx(q, k, sb["qn"], sb["kn"], *rope, self.heads, tokens_per_batch=S,
                               write_bf16=self.trace is not None, out_q=qm, out_k=km)
             N.mx_quant_vt(QKV.view(B, S, 3 * D)[:, :, 2 * D:], self.heads, out=(vt, vs))
             oin = N.attention_mxfp8(qm, km, vt, vs, B, S, S, out=None if omx else O.view(B, S, D), out_mx=omx)
         else:
-            N.qk_norm_rope(q, k, sb["qn"], sb["kn"], cos, sin, self.heads, tokens_per_batch=S)
+            N.qk_norm_rope(q, k, sb["qn"], sb["kn"], *rope, self.heads, tokens_per_batch=S)
             Q3 = QKV.view(B, S, 3 * D)
             oin = N.attention(Q3[:, :, :D], Q3[:, :, D:2 * D], Q3[:, :, 2 * D:], out=None if omx else O.view(B, S, D),
                               heads=self.heads, out_mx=omx)
@@ -724,53 +736,55 @@ class HipDiT:
         X, U = ws["x"], ws["u"]
         uin = U
         if fusedmx and N.mx_gemm_plan(X.shape[0], U.shape[1], self.D, rows) <= 1:
-            uin = N.gemm_mxfp8(hin, sb["w1"], epilogue=N.EPI_GELU, rows_per_batch=rows,
-                               out_mx=self._mx_view(ws["uact"], ws["uact_q_bytes"], X.shape[0], U.shape[1]))
+            uin = N.gemm_mxfp8(hin, sb["w1"], epilogue=N.EPI_GELU, rows_per_batch=rows, out_mx=ws["uact_mx"])
         else:
             self._lin(hin, sb["w1"], U, epilogue=N.EPI_GELU, rows_per_batch=rows)
         self._lin(uin, sb["w2"], X, epilogue=N.EPI_GATE_RES, gate=gate, residual=X, rows_per_batch=rows)
 
-    def _run(self, x, cond, mod, modf, addvec, Tp, Hp, Wp, plan):
-        """The kernel sequence of one forward (all shapes / pointers fixed for a given input shape)."""
-        D = self.D
-        S, rows, world = plan.S, plan.rows, plan.world
-        B = x.shape[0]                                           # B > 1 only without an exchange (rows == S)
-        cos, sin = self.rope(Tp, Hp, Wp)
+    def _run(self, x, cond, mod, modf, addvec, grid, plan):
+        """The kernel sequence of one forward (all shapes / pointers fixed for a given input shape).  grid: (Tp, Hp, Wp) patches."""
+        D, S, rows, B = self.D, plan.S, plan.rows, x.shape[0]    # (a sharded batch: row = b * band + r)
+        rope = self.rope(*grid)
         ws = self._workspace(S, rows, B)
-        X, Hb, O, Y = ws["x"], ws["h"], ws["o"], ws["y"]
-        modB = modfB = gateB = None
+        X, Hb, Y = ws["x"], ws["h"], ws["y"]
+        batched = None
         if B > 1:
-            # shift | scale rows per clip for the batched LayerNorm pass: [sites, 2, B, D] (one sigma -> B equal rows)
-            modB = mod[:, :2 * D].reshape(-1, 2, 1, D).expand(-1, 2, B, D).contiguous()
-            modfB = modf.view(2, 1, D).expand(2, B, D).contiguous()
-            gateB = mod[:, 2 * D:].reshape(-1, 1, D).expand(-1, B, D).contiguous()     # one gate row per clip: [sites, B, D]
+            # shift | scale rows per clip for the batched LayerNorm pass: [sites, 2, B, D] (one sigma -> B equal rows), the
+            # final layer's [2, B, D], and one gate row per clip: [sites, B, D]
+            batched = (mod[:, :2 * D].reshape(-1, 2, 1, D).expand(-1, 2, B, D).contiguous(),
+                       modf.view(2, 1, D).expand(2, B, D).contiguous(),
+                       mod[:, 2 * D:].reshape(-1, 1, D).expand(-1, B, D).contiguous())
+        # mxfp8 with fused producers (the launches of drn_dit_forward with mx_fused): h, O and U leave their producers as MXFP8
+        fusedmx = self._mx_fused and self.trace is None
+        sharded = self.exchange != "none"
+        if sharded:
+            # what every self-attention block of this forward does, decided here once; the exchanges (and the projections that
+            # write / read their slabs) then run clip by clip on this rank's band of each clip
+            route = sp_route(D, self.heads, S, plan.world, self.exchange, self._mx, self._amx, fusedmx, self._mx_return,
+                             self._split_return)
+            self.sp_path = route.path()
+            fa_sharded = self._fa_a2a if self.exchange == "a2a" else self._fa_gather
 
         # the latent is tiny: every rank patchifies it all and keeps its own token band
         P = N.patchify_concat(x, cond, self.with_mask, self.pt, self.ps, self.kpad)
-        sharded = self.exchange != "none"
         if not sharded and self.trace is None and not self._per_launch:
             # one GPU: the whole launch sequence below is enqueued by ONE C call (csrc/dit_forward.hip: same kernels, same
             # arguments, same order -> same bits; ~570 ctypes round trips less per forward)
-            N.dit_forward(self._sequencer_args(ws, P, S, B, mod=mod, modf=modf, batched=(modB, modfB, gateB) if B > 1 else None,
-                                               addvec=addvec, rope=(cos, sin)))
-            return N.unpatchify(Y, B, self.out_ch, Tp, Hp, Wp, self.pt, self.ps)
-        if sharded and B > 1:
+            N.dit_forward(self._sequencer_args(ws, P, S, B, mod=mod, modf=modf, batched=batched, addvec=addvec, rope=rope))
+            return N.unpatchify(Y, B, self.out_ch, *grid, self.pt, self.ps)
+        if sharded:
             for b in range(B):                                   # this rank's band of every clip (P holds whole clips)
                 N.gemm(plan.band(P[b * S:(b + 1) * S]), self.w_patch, out=X[b * rows:(b + 1) * rows])
         else:
-            N.gemm(plan.band(P) if B == 1 else P, self.w_patch, out=X, rows_per_batch=rows)
+            N.gemm(P, self.w_patch, out=X, rows_per_batch=rows)
 
         pending = None
         nk = len(self.kinds)
-        fused = None                                             # a2a exchange: blocked-layout GEMMs instead of regroup passes
-        # mxfp8 with fused producers (the launches of drn_dit_forward with mx_fused, in its order): h, O and U leave their
-        # producers as MXFP8
-        fusedmx = self._mx_fused and self.trace is None
         for site, sb in enumerate(sb for subs in self.blocks for sb in subs):
             m = mod[site]
             shift, scale, gate = m[:D], m[D:2 * D], m[2 * D:]
             if B > 1:
-                shift, scale, gate = modB[site, 0], modB[site, 1], gateB[site]
+                shift, scale, gate = batched[0][site, 0], batched[0][site, 1], batched[2][site]
             if self.trace is not None and site > 0:
                 self.trace[f"block{(site - 1) // nk}.{(site - 1) % nk}"] = self._traced(X, pending, B)
             if sb["kind"] == "ca":
@@ -779,48 +793,34 @@ class HipDiT:
                 pending = addvec[sb["idx"]]
                 continue
             if fusedmx:
-                hin = N.ln_modulate(X, shift, scale, add_vec=pending, rows_per_batch=rows,
-                                    out_mx=self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D))
+                hin = N.ln_modulate(X, shift, scale, add_vec=pending, rows_per_batch=rows, out_mx=ws["act_mx"])
             else:
                 hin = N.ln_modulate(X, shift, scale, out=Hb, add_vec=pending, rows_per_batch=rows)
             pending = None
             if sb["kind"] == "mlp":
                 self._mlp(sb, hin, ws, gate, rows, fusedmx)
             elif not sharded:
-                self._fa_local(sb, hin, ws, cos, sin, gate, S, B, fusedmx)
+                self._fa_local(sb, hin, ws, rope, gate, S, B, fusedmx)
             else:
-                # sharded: the exchanges (and the projections that write / read their slabs) run clip by clip on this
-                # rank's band of each clip; every clip of a batch has the same sigma, hence the same gate row
-                if fused is None:
-                    W_ = D // world
-                    if self._mx:
-                        # the MXFP8 slab GEMM always runs on the 256 x 256 kernel: taken where the plan of one clip's band rows picks
-                        # that kernel anyway (the slab layout then changes no bit) and the planes meet its contract (drn.h)
-                        fused = (self.exchange == "a2a" and world > 1 and W_ >= 256 and W_ & (W_ - 1) == 0
-                                 and N.mx_gemm_plan(rows, 2 * D, D) == 0 and N.mx_gemm_plan(rows, D, D) == 0)
-                    else:
-                        fused = (self.exchange == "a2a" and world > 1 and W_ >= 512 and N.gemm_blocked_ok(rows, 2 * D)
-                                 and N.gemm_blocked_ok(rows, D))
-                omx = self._mx_view(ws["act"], ws["act_q_bytes"], X.shape[0], D) if fusedmx and self.exchange == "gather" else None
-                for b in range(B):
-                    self._fa_sharded(sb, self._rows(hin, b * rows, (b + 1) * rows), X[b * rows:(b + 1) * rows],
-                                     O[b * rows:(b + 1) * rows], ws, plan, cos, sin, m[2 * D:], fused,
-                                     self._rows(omx, b * rows, (b + 1) * rows) if omx is not None else None)
+                for b in range(B):                               # every clip of a batch has the same sigma: the same gate row
+                    fa_sharded(sb, hin, ws, plan, rope, m[2 * D:], route, b)
 
         if self.trace is not None:
             site = len(self.blocks) * nk
             self.trace[f"block{(site - 1) // nk}.{(site - 1) % nk}"] = self._traced(X, pending, B)
-        if B == 1:
-            N.ln_modulate(X, modf[:D], modf[D:], out=Hb, add_vec=pending)
-            N.gemm(Hb, self.w_final, out=plan.band(Y))
-            allgather_rows_(Y, plan, self.pg)                       # 2.4 MB at cfg 3: every rank gets the full latent
-        elif sharded:
-            N.ln_modulate(X, modfB[0], modfB[1], out=Hb, add_vec=pending, rows_per_batch=rows)
+        self._final_layer(ws, plan, (modf[:D], modf[D:]) if B == 1 else batched[1], pending, B)
+        return N.unpatchify(Y, B, self.out_ch, *grid, self.pt, self.ps)
+
+    def _final_layer(self, ws, plan, mod, pending, B):
+        """Final LayerNorm (mod: shift, scale - one row, or one per clip) + projection into ws["y"]."""
+        S, rows, Hb, Y = plan.S, plan.rows, ws["h"], ws["y"]
+        N.ln_modulate(ws["x"], mod[0], mod[1], out=Hb, add_vec=pending, rows_per_batch=rows)
+        if self.exchange != "none" or B == 1:
+            # this rank's band of every clip, then every rank gets the full latent (2.4 MB at cfg 3).  One clip without an
+            # exchange: the same GEMM; its gather is issued by a 1-rank group under parallel.SINGLE_RANK_COLLECTIVES alone
             for b in range(B):
                 Yb = Y[b * S:(b + 1) * S]
                 N.gemm(Hb[b * rows:(b + 1) * rows], self.w_final, out=plan.band(Yb))
                 allgather_rows_(Yb, plan, self.pg)
         else:
-            N.ln_modulate(X, modfB[0], modfB[1], out=Hb, add_vec=pending, rows_per_batch=rows)
             N.gemm(Hb, self.w_final, out=Y, rows_per_batch=rows)
-        return N.unpatchify(Y, B, self.out_ch, Tp, Hp, Wp, self.pt, self.ps)

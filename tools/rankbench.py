@@ -60,6 +60,7 @@ def main():
     ap.add_argument("--attention-precision", choices=("bf16", "mxfp8"), default="bf16", help="self-attention (HipDiT attention_precision)")
     ap.add_argument("--compare", type=int, default=0, metavar="ROUNDS",
                     help="also build the bf16 / bf16 engine and time the two alternately for this many rounds")
+    ap.add_argument("--checksum", action="store_true", help="print the int16 sum of the last forward's output (A/B runs of two trees)")
     args = ap.parse_args()
     os.environ["DRN_SP_EXCHANGE"] = args.exchange
     pkg = load_package()
@@ -144,9 +145,11 @@ def main():
     print(f"host cost of one forward on an empty queue: {one_ms:.2f} ms")
     timer = N.KernelTimer(sample_every=3)
     N.set_timer(timer)
-    dit(x, sig[1], cond, 3)
+    y = dit(x, sig[1], cond, 3)
     torch.cuda.synchronize()
     N.set_timer(None)
+    if args.checksum:
+        print(f"checksum {int(y.view(torch.int16).sum(dtype=torch.int64))}")
     print(f"world={world} exchange={dit.exchange} clips={args.clips} {tag} path={dit.sp_path}: {ms:.2f} ms per forward on this rank's "
           f"shapes (no communication); host enqueue {host_ms:.2f} ms per forward")
     for name, d in timer.summary().items():
