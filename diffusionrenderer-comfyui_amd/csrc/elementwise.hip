@@ -781,6 +781,30 @@ extern "C" int drn_cfg_combine(const void* cond, const void* uncond, void* out, 
 
 // ------------------------------------------------------------------------------------------------
 // pipeline post-process -> uint8 (B,T,H,W,3); diffusion_renderer_pipeline.py:299-318 with every bf16 rounding kept.
+// One pixel's chain, shared by both post-process kernels: c[] = the pixel's three bf16 channel values (widened), o[] = its bytes.
+__device__ __forceinline__ void postprocess_pixel(float (&c)[3], int normalize, uint8_t (&o)[3]) {
+    if (normalize) {
+        const float norm = rbf(sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
+        const float den = rbf(fmaxf(norm, 1e-12f));
+        // torch CPU rounds the Python scalar of a bf16 add/sub to bf16 first (0.2 -> 0.2001953125); div keeps fp32
+        float blend = rbf(rbf(norm - 0.2001953125f) / 0.2f);
+        blend = fminf(fmaxf(blend, 0.f), 1.f);
+        const float om = rbf(1.0f - blend);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float vn = rbf(c[ch] / den);
+            c[ch] = rbf(rbf(vn * blend) + rbf(c[ch] * om));
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float a = rbf(1.0f + c[ch]);
+        a = fminf(fmaxf(a, 0.f), 2.f);
+        const float u = rbf((a / 2.0f) * 255.0f);
+        o[ch] = (uint8_t)u;
+    }
+}
+
 __global__ __launch_bounds__(256) void postprocess_kernel(const bf16_t* __restrict__ v, uint8_t* __restrict__ o, int B,
                                                           int64_t thw, int normalize) {
     const int64_t total = (int64_t)B * thw;
@@ -789,26 +813,10 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const bf16_t* __restri
         float c[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) c[ch] = bf2f(v[(b * 3 + ch) * thw + p]);
-        if (normalize) {
-            const float norm = rbf(sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
-            const float den = rbf(fmaxf(norm, 1e-12f));
-            // torch CPU rounds the Python scalar of a bf16 add/sub to bf16 first (0.2 -> 0.2001953125); div keeps fp32
-            float blend = rbf(rbf(norm - 0.2001953125f) / 0.2f);
-            blend = fminf(fmaxf(blend, 0.f), 1.f);
-            const float om = rbf(1.0f - blend);
+        uint8_t u[3];
+        postprocess_pixel(c, normalize, u);
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float vn = rbf(c[ch] / den);
-                c[ch] = rbf(rbf(vn * blend) + rbf(c[ch] * om));
-            }
-        }
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            float a = rbf(1.0f + c[ch]);
-            a = fminf(fmaxf(a, 0.f), 2.f);
-            const float u = rbf((a / 2.0f) * 255.0f);
-            o[i * 3 + ch] = (uint8_t)u;
-        }
+        for (int ch = 0; ch < 3; ++ch) o[i * 3 + ch] = u[ch];
     }
 }
 
@@ -818,6 +826,111 @@ extern "C" int drn_postprocess_u8(const void* video, void* out_u8, int B, int T,
     const int64_t thw = (int64_t)T * H * W;
     postprocess_kernel<<<ew_grid((int64_t)B * thw), dim3(256), 0, (hipStream_t)stream>>>(
         (const bf16_t*)video, (uint8_t*)out_u8, B, thw, normalize_normal);
+    return drn_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// post-process of one WINDOW of a long clip (drn.h): frames [write_lo, write_hi) of the decoded window -> uint8, the O ramp frames
+// cross-faded in fp32 with the previous window's last O decoded frames before the chain above.  A block works inside ONE output
+// frame (blockIdx.y strides the B * (write_hi - write_lo) frames), so "is this a ramp frame" and its weight are uniform.
+// VEC: a lane owns 8 consecutive pixels of the frame - one 16-byte load per channel plane (two on a ramp frame) and 24 contiguous
+// output bytes as three 8-byte stores, a wave writes 1536 contiguous bytes.  Needs H * W % 8 == 0 (every plane of every frame then
+// starts 16-byte aligned, and a frame is whole groups: no partial group exists); any other shape takes the one-pixel-per-lane form.
+__device__ __forceinline__ float window_blend(float a, float b, float w) {
+    // three separately rounded fp32 operations (torch's a + w * (b - a)), never an FMA; then the bf16 rounding of .to(bfloat16).
+    // Plain operators under this file's `fp contract(off)`: hipcc lowers __fmul_rn / __fadd_rn through library code that the
+    // pragma does not reach and fuses the pair into v_pk_fma_f32 all the same (seen in the ISA).
+    const float d = b - a;
+    const float m = w * d;
+    return rbf(a + m);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void postprocess_window_kernel(const bf16_t* __restrict__ v, const bf16_t* __restrict__ prev,
+                                                                 const float* __restrict__ rw, uint8_t* __restrict__ o,
+                                                                 int nframes, int nF, int Tw, int64_t hw, int O, int ramp_at,
+                                                                 int write_lo, int normalize) {
+    for (int fi = blockIdx.y; fi < nframes; fi += gridDim.y) {
+        const int b = fi / nF, f = write_lo + (fi - b * nF);
+        const int j = f - ramp_at;
+        const bool ramp = prev != nullptr && j >= 0 && j < O;
+        const float w = ramp ? rw[j] : 0.f;
+        const int64_t vcs = (int64_t)Tw * hw, pcs = (int64_t)O * hw;           // channel strides of the window / the carry
+        const bf16_t* vb = v + ((int64_t)b * 3 * Tw + f) * hw;
+        const bf16_t* pb = ramp ? prev + ((int64_t)b * 3 * O + j) * hw : nullptr;
+        uint8_t* ob = o + (int64_t)fi * hw * 3;
+        if (VEC) {
+            const int64_t G = hw >> 3;
+            for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < G; g += (int64_t)gridDim.x * 256) {
+                float c[3][8];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) unpack8(ld16_nt(vb + ch * vcs + g * 8), c[ch]);
+                if (ramp) {
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        float a[8];
+                        unpack8(ld16_nt(pb + ch * pcs + g * 8), a);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) c[ch][k] = window_blend(a[k], c[ch][k], w);
+                    }
+                }
+                uint32_t word[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float px[3] = {c[0][k], c[1][k], c[2][k]};
+                    uint8_t u[3];
+                    postprocess_pixel(px, normalize, u);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) word[(3 * k + ch) >> 2] |= (uint32_t)u[ch] << (8 * ((3 * k + ch) & 3));
+                }
+                uint2* dst = reinterpret_cast<uint2*>(ob + g * 24);
+                dst[0] = make_uint2(word[0], word[1]);
+                dst[1] = make_uint2(word[2], word[3]);
+                dst[2] = make_uint2(word[4], word[5]);
+            }
+        } else {
+            for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < hw; p += (int64_t)gridDim.x * 256) {
+                float c[3];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    c[ch] = bf2f(vb[ch * vcs + p]);
+                    if (ramp) c[ch] = window_blend(bf2f(pb[ch * pcs + p]), c[ch], w);
+                }
+                uint8_t u[3];
+                postprocess_pixel(c, normalize, u);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) ob[p * 3 + ch] = u[ch];
+            }
+        }
+    }
+}
+
+extern "C" int drn_postprocess_window_u8(const void* video, const void* prev_tail, const void* ramp_w, void* out_u8, int B, int Tw,
+                                         int H, int W, int O, int ramp_at, int write_lo, int write_hi, int normalize_normal,
+                                         void* stream) {
+    DRN_CHECK_ARG(video && out_u8 && B > 0 && Tw > 0 && H > 0 && W > 0);
+    DRN_CHECK_ARG((prev_tail == nullptr) == (ramp_w == nullptr));
+    DRN_CHECK_ARG(O >= 0 && ramp_at >= 0 && (int64_t)ramp_at + O <= Tw);
+    DRN_CHECK_ARG(0 <= write_lo && write_lo < write_hi && write_hi <= Tw);
+    // a ramp is written whole or not at all: the frames in front of write_lo have no other writer
+    if (prev_tail && O > 0) DRN_CHECK_ARG(write_lo <= ramp_at || write_lo >= ramp_at + O);
+    DRN_CHECK_ARG(((uintptr_t)video & 1) == 0 && ((uintptr_t)prev_tail & 1) == 0 && ((uintptr_t)ramp_w & 3) == 0);
+    const int nF = write_hi - write_lo;
+    const int64_t hw = (int64_t)H * W, nframes = (int64_t)B * nF;
+    DRN_CHECK_ARG(nframes < (1ll << 31));
+    const bool vec = hw % 8 == 0 && ((uintptr_t)video & 15) == 0 && ((uintptr_t)prev_tail & 15) == 0 && ((uintptr_t)out_u8 & 7) == 0;
+    const int64_t per_frame = vec ? hw / 8 : hw;
+    int64_t gx = (per_frame + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    const dim3 grid((unsigned)gx, (unsigned)(nframes < 65535 ? nframes : 65535));
+    if (vec)
+        postprocess_window_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(
+            (const bf16_t*)video, (const bf16_t*)prev_tail, (const float*)ramp_w, (uint8_t*)out_u8, (int)nframes, nF, Tw, hw, O,
+            ramp_at, write_lo, normalize_normal);
+    else
+        postprocess_window_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(
+            (const bf16_t*)video, (const bf16_t*)prev_tail, (const float*)ramp_w, (uint8_t*)out_u8, (int)nframes, nF, Tw, hw, O,
+            ramp_at, write_lo, normalize_normal);
     return drn_launch_status();
 }
 

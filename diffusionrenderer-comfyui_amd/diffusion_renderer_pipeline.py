@@ -18,6 +18,9 @@ import torch
 from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
 from .model_diffusion_renderer import CleanDiffusionRendererModel
+from .windows import plan_windows, ramp_weights
+
+_SHAPE_KEYS = ("rgb", "image", "basecolor", "normal", "depth", "roughness", "metallic")
 
 
 class CleanDiffusionRendererPipeline:
@@ -35,6 +38,11 @@ class CleanDiffusionRendererPipeline:
         self.default_width = width
         self.default_num_video_frames = num_video_frames
         self.seed = seed
+        # long clips (windows.py): a clip of more than `window_frames` frames (8k + 1; 0 = off, 57 = the training length) is
+        # rendered as windows of that length overlapping by `window_overlap` frames, cross-faded where the decoded frames
+        # become uint8
+        self.window_frames = 0
+        self.window_overlap = 8
         self.device = torch.device("cuda")     # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
@@ -145,6 +153,9 @@ class CleanDiffusionRendererPipeline:
 
     def generate_video(self, data_batch: Dict[str, torch.Tensor], normalize_normal: bool = False, seed: int = None,
                        init_noise: torch.Tensor = None) -> np.ndarray:
+        plan = self._window_plan(data_batch)
+        if plan is not None:
+            return self._generate_windowed([data_batch], [[bool(normalize_normal)]], seed, init_noise, plan)[0][0]
         sample = self._sample(data_batch, seed, init_noise)
         video = self.model.decode(sample)
         u8 = N.postprocess_u8(video.to(self.dtype).contiguous(), normalize_normal)   # fused :299-318
@@ -157,6 +168,9 @@ class CleanDiffusionRendererPipeline:
         would return for the passes run one after the other (reference nodes.py:191-213): same seed -> same start noise,
         one encode instead of P, one batched denoiser call per step."""
         flags = list(normalize_normal)
+        plan = self._window_plan(data_batch)
+        if plan is not None:
+            return self._generate_windowed([data_batch], [[bool(f) for f in flags]], seed, init_noise, plan)[0]
         sample = self._sample(data_batch, seed, init_noise)
         if sample.shape[0] != len(flags):
             raise ValueError(f"{len(flags)} normalize_normal flags for {sample.shape[0]} passes")
@@ -166,17 +180,80 @@ class CleanDiffusionRendererPipeline:
             outs.append(N.postprocess_u8(video.to(self.dtype).contiguous(), bool(flag)))
         return [o.cpu().numpy() for o in outs]
 
+    def generate_video_each(self, data_batches, normalize_normal, seed: int = None, init_noise: torch.Tensor = None):
+        """generate_video for several batches over ONE clip (the inverse node's passes run one after the other), returned in
+        order.  With windows the loop is windows outside, batches inside: the batches share the clip tensor, so they share each
+        window's slice of it, and the upload and encode caches still see one clip per window instead of one per window and pass."""
+        batches = list(data_batches)
+        flags = [bool(f) for f in normalize_normal]
+        if len(flags) != len(batches):
+            raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
+        plan = self._window_plan(batches[0]) if batches else None
+        if plan is None:
+            return [self.generate_video(b, f, seed, init_noise) for b, f in zip(batches, flags)]
+        return [o[0] for o in self._generate_windowed(batches, [[f] for f in flags], seed, init_noise, plan)]
+
+    def _window_plan(self, data_batch):
+        """The windows of this clip, or None where today's single-sequence path applies (windows off, or a clip that fits one)."""
+        if not self.window_frames:
+            return None
+        inst = self.pre_loaded_model_instance
+        if isinstance(inst, dict):
+            inst = inst.get(self.model_type)
+        if getattr(inst if inst is not None else self.model, "process_group", None) is not None:
+            raise NotImplementedError("windows under sequence parallelism are not implemented: set window_frames = 0")
+        ref = self._shape_tensor(data_batch)
+        T = ref.shape[2] if ref.ndim == 5 else 1
+        plan = plan_windows(T, self.window_frames, self.window_overlap)     # ValueError on a bad length / overlap
+        return plan if len(plan) > 1 else None
+
+    def _generate_windowed(self, batches, flags, seed, init_noise, plan):
+        """Walk the plan in order.  Per window and batch: slice every clip tensor, sample (same seed, same start noise: every window
+        has one shape), decode pass by pass, cross-fade with the carry of the previous window inside the uint8 post-process and
+        copy the written frames to the host.  The window's last `overlap` decoded frames become the next carry.  Device memory:
+        one window's decode plus one carry per pass, whatever T is.  -> per batch, per pass: uint8 [1, T, H, W, 3]."""
+        Wf, O = int(self.window_frames), int(self.window_overlap)
+        T = self._shape_tensor(batches[0]).shape[2]
+        ramp = torch.from_numpy(ramp_weights(O)).to(self._resolved(self.device)) if O else None
+        outs = [[None] * len(f) for f in flags]
+        carry = [[None] * len(f) for f in flags]
+        for i, win in enumerate(plan):
+            sliced = {}             # id(clip tensor) -> (tensor, its window): rgb / video, and the batches of one clip, share a slice
+            for c, (batch, fl) in enumerate(zip(batches, flags)):
+                wb = {}
+                for k, v in batch.items():
+                    if isinstance(v, torch.Tensor) and v.ndim == 5 and v.shape[2] == T:
+                        if id(v) not in sliced:
+                            sliced[id(v)] = (v, v[:, :, win.start:win.start + Wf].contiguous())
+                        v = sliced[id(v)][1]
+                    wb[k] = v
+                sample = self._sample(wb, seed, init_noise)
+                if sample.shape[0] != len(fl):
+                    raise ValueError(f"{len(fl)} normalize_normal flags for {sample.shape[0]} passes")
+                for p, flag in enumerate(fl):
+                    video = self.model.decode(sample[p:p + 1]).to(self.dtype).contiguous()
+                    if video.shape[2] != Wf:
+                        raise ValueError(f"the tokenizer decoded {video.shape[2]} frames for a window of {Wf}")
+                    prev = carry[c][p] if i > 0 and O else None
+                    u8 = N.postprocess_window_u8(video, prev, ramp if prev is not None else None, win.ramp_at, win.write_lo,
+                                                 win.write_hi, flag)
+                    if outs[c][p] is None:
+                        outs[c][p] = torch.empty((1, T) + tuple(u8.shape[2:]), dtype=torch.uint8)
+                    outs[c][p][:, win.out_at:win.out_at + u8.shape[1]].copy_(u8)      # D2H straight into the clip's frames
+                    carry[c][p] = video[:, :, Wf - O:].contiguous() if O and i + 1 < len(plan) else None
+        return [[o.numpy() for o in per_batch] for per_batch in outs]
+
+    @staticmethod
+    def _shape_tensor(data_batch):
+        for key in _SHAPE_KEYS:
+            if key in data_batch:
+                return data_batch[key]
+        raise ValueError(f"No suitable input tensor for shape inference found in data_batch. Looked for {list(_SHAPE_KEYS)}")
+
     def _sample(self, data_batch, seed, init_noise):
         effective_seed = seed if seed is not None else self.seed
         data_batch = self._move_to_device(data_batch)
-        video_tensor = None
-        for key in ("rgb", "image", "basecolor", "normal", "depth", "roughness", "metallic"):
-            if key in data_batch:
-                video_tensor = data_batch[key]
-                break
-        if video_tensor is None:
-            raise ValueError("No suitable input tensor for shape inference found in data_batch. Looked for "
-                             "['rgb', 'image', 'basecolor', 'normal', 'depth', 'roughness', 'metallic']")
+        video_tensor = self._shape_tensor(data_batch)
         self._ensure_model_loaded(tuple(video_tensor.shape))
         C = self.config["latent_shape"][0]
         _, _, T, H, W = video_tensor.shape

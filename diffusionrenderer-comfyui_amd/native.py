@@ -113,6 +113,7 @@ SIGNATURES = {
     "drn_edm_step": [_P, _P, _P, _L, _F, _F, _F, _F, _P],
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
@@ -810,6 +811,29 @@ def postprocess_u8(video, normalize_normal: bool):
     out = torch.empty((B, T, H, W, 3), dtype=torch.uint8, device=video.device)
     _check(load_library().drn_postprocess_u8(_ptr(video), _ptr(out), B, T, H, W, 1 if normalize_normal else 0, _stream()),
            "drn_postprocess_u8")
+    return out
+
+
+def postprocess_window_u8(video, prev_tail, ramp_w, ramp_at: int, write_lo: int, write_hi: int, normalize_normal: bool, out=None):
+    """One window of a long clip (drn_postprocess_window_u8): video [B,3,Tw,H,W] bf16, frames [write_lo, write_hi) -> uint8
+    [B, write_hi - write_lo, H, W, 3]; with prev_tail [B,3,O,H,W] bf16 (the previous window's last O decoded frames) and ramp_w
+    [O] fp32 on the device, frames [ramp_at, ramp_at + O) are cross-faded first.  prev_tail = ramp_w = None: no ramp."""
+    _bf16(video, prev_tail)
+    B, C, Tw, H, W = video.shape
+    assert C == 3 and video.is_contiguous()
+    assert (prev_tail is None) == (ramp_w is None), "prev_tail and ramp_w come together"
+    O = 0
+    if prev_tail is not None:
+        O = prev_tail.shape[2]
+        assert prev_tail.shape == (B, 3, O, H, W) and prev_tail.is_contiguous()
+        assert ramp_w.dtype == torch.float32 and ramp_w.shape == (O,) and ramp_w.is_contiguous()
+    shape = (B, max(write_hi - write_lo, 0), H, W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=video.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()
+    _check(load_library().drn_postprocess_window_u8(_ptr(video), _ptr(prev_tail), _ptr(ramp_w), _ptr(out), B, Tw, H, W, O, ramp_at,
+                                                    write_lo, write_hi, 1 if normalize_normal else 0, _stream()),
+           "drn_postprocess_window_u8")
     return out
 
 

@@ -27,6 +27,17 @@ def _progress_bar(n):
         return _NoBar()
 
 
+def _window_inputs():
+    """Optional inputs of both renderers for long clips (windows.py; DESIGN.md "Long clips")."""
+    return {"window_frames": ("INT", {"default": 0, "min": 0, "max": 1025, "step": 1,
+                                      "tooltip": "0 = off: the whole clip is one sequence.  8k+1 frames (57 recommended: the "
+                                                 "training length): longer clips are rendered as overlapping windows of this "
+                                                 "length, cross-faded in pixel space"}),
+            "window_overlap": ("INT", {"default": 8, "min": 0, "max": 512, "step": 1,
+                                       "tooltip": "frames two neighbouring windows share (at most (window_frames - 1) / 2); "
+                                                  "0 = hard cuts"})}
+
+
 def standardize_to_5d(image, name="image") -> torch.Tensor:
     """list / (H,W,C) / (B,H,W,C)->T=1 / (B,T,H,W,C) -> (B,T,H,W,C)   (reference nodes.py:156-177, :258-268)."""
     if isinstance(image, list):
@@ -100,7 +111,8 @@ class Cosmos1InverseRenderer:
         return {
             "required": {"pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "image": ("IMAGE",)},
             "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1}),
-                         "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff})},
+                         "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
+                         **_window_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -108,10 +120,12 @@ class Cosmos1InverseRenderer:
     FUNCTION = "run_inverse_pass"
     CATEGORY = "Cosmos1"
 
-    def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42):
+    def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8):
         pipeline.set_model_type("inverse")
         pipeline.guidance = guidance
         pipeline.seed = seed
+        pipeline.window_frames = window_frames
+        pipeline.window_overlap = window_overlap
         image_5d = standardize_to_5d(image)
         image_tensor = image_5d.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
         outputs = {}
@@ -135,12 +149,18 @@ class Cosmos1InverseRenderer:
                 outputs[gbuffer_pass] = to_image(out)
                 pbar.update(1)
             return (outputs["basecolor"], outputs["metallic"], outputs["roughness"], outputs["normal"], outputs["depth"])
-        for gbuffer_pass in INVERSE_PASSES:
-            data_batch = {
-                "rgb": image_tensor,
-                "video": image_tensor,
-                "context_index": torch.full((image_tensor.shape[0], 1), GBUFFER_INDEX_MAPPING[gbuffer_pass], dtype=torch.long),
-            }
+        batches = [{"rgb": image_tensor,
+                    "video": image_tensor,
+                    "context_index": torch.full((image_tensor.shape[0], 1), GBUFFER_INDEX_MAPPING[p], dtype=torch.long)}
+                   for p in INVERSE_PASSES]
+        if window_frames and hasattr(pipeline, "generate_video_each"):
+            # windows outside, passes inside: every window of the clip is uploaded and encoded once, not once per pass
+            outs = pipeline.generate_video_each(batches, [p == "normal" for p in INVERSE_PASSES], seed=seed)
+            for gbuffer_pass, out in zip(INVERSE_PASSES, outs):
+                outputs[gbuffer_pass] = to_image(out)
+                pbar.update(1)
+            return (outputs["basecolor"], outputs["metallic"], outputs["roughness"], outputs["normal"], outputs["depth"])
+        for gbuffer_pass, data_batch in zip(INVERSE_PASSES, batches):
             out = pipeline.generate_video(data_batch=data_batch, normalize_normal=(gbuffer_pass == "normal"), seed=seed)
             outputs[gbuffer_pass] = to_image(out)
             pbar.update(1)
@@ -159,7 +179,8 @@ class Cosmos1ForwardRenderer:
                          "env_brightness": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 2.0, "step": 0.1}),
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
-                         "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0})},
+                         "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
+                         **_window_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE",)
@@ -168,10 +189,12 @@ class Cosmos1ForwardRenderer:
 
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
-                         env_spin=0.0):
+                         env_spin=0.0, window_frames=0, window_overlap=8):
         pipeline.set_model_type("forward")
         pipeline.guidance = guidance
         pipeline.seed = seed
+        pipeline.window_frames = window_frames
+        pipeline.window_overlap = window_overlap
         key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                        "metallic": "metallic"}
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
@@ -182,7 +205,8 @@ class Cosmos1ForwardRenderer:
         B, _, T, H, W = data_batch["depth"].shape
         data_batch["video"] = data_batch["depth"]
         # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
-        # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static
+        # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static.
+        # Built for the WHOLE clip also when it is rendered in windows: the pipeline cuts them per window like the G-buffers
         from . import preprocess_envmap as pe
         env = pe.envmap_conditions(env_map, (H, W), T, env_format, env_brightness, env_flip_horizontal, env_rotation,
                                    device=getattr(pipeline, "device", "cuda"), env_spin=env_spin)

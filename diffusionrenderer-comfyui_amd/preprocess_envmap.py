@@ -247,7 +247,7 @@ def _projection(env_input, resolution, env_brightness, env_flip, env_rot, device
         h = compute_tensor_hash(env_input) if isinstance(env_input, torch.Tensor) else hashlib.md5(str(env_input).encode()).hexdigest()
         hit = _env_cache.get(h, resolution, fmt, env_brightness, env_flip, env_rot)
         if hit is not None:
-            return _expand_static(hit, num_frames)
+            return _expand_static(hit, num_frames, static=env_spin == 0)
     H, W = resolution
     latlong = apply_hdr_preprocessing(_load(env_input), env_brightness, env_flip, env_rot, device)
     cubemap = latlong_to_cubemap_official(latlong, [512, 512])
@@ -270,10 +270,14 @@ def _projection(env_input, resolution, env_brightness, env_flip, env_rot, device
     return _expand_static(result, num_frames)
 
 
-def _expand_static(d, num_frames):
+def _expand_static(d, num_frames, static=False):
     """The kernel path's one static frame [3, 1, H, W] expanded over the clip, after the cache (everything else: as stored)."""
     if "cond_ldr" in d and d["cond_ldr"].shape[1] == 1 and num_frames > 1:
         return {k: v.expand(-1, num_frames, -1, -1) for k, v in d.items()}
+    if static and "env_ldr" in d and d["env_ldr"].shape[0] != num_frames:
+        # the torch path stores its one frame expanded to the clip it was first asked for, under a key without T: a clip of
+        # another length (a long clip's windows and then one window alone, say) gets the same frame at its own length
+        return {k: _frames(v[0], num_frames) for k, v in d.items()}
     return d
 
 
@@ -300,7 +304,7 @@ def tonemap_image_direct(env_input, resolution: Tuple[int, int], device="cuda", 
         h = compute_tensor_hash(env_input) if isinstance(env_input, torch.Tensor) else hashlib.md5(str(env_input).encode()).hexdigest()
         hit = _env_cache.get(h, resolution, "ball", 1.0, False, 0.0)
         if hit is not None:
-            return hit
+            return _expand_static(hit, num_frames, static=True)
     H, W = resolution
     env = _load(env_input).to(device).float()
     if tuple(env.shape[:2]) != (H, W):

@@ -471,6 +471,21 @@ int drn_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, 
  * (1+v).clamp(0,2)/2, permute to (B,T,H,W,C), *255, truncating uint8 cast.  video: [B,3,T,H,W] bf16. Bit-exact. */
 int drn_postprocess_u8(const void* video, void* out_u8, int B, int T, int H, int W, int normalize_normal, void* stream);
 
+/* ---- the same post-process for one WINDOW of a long clip (windows.py): frames [write_lo, write_hi) of the decoded window are
+ * written, and the O ramp frames [ramp_at, ramp_at + O) are first cross-faded with the previous window's last O decoded frames:
+ *   v = bf16(a + w[f - ramp_at] * (b - a)),  a = prev_tail at frame f - ramp_at, b = the window's value, both widened to fp32;
+ * subtract, multiply and add are three separately rounded fp32 operations (no FMA).  Every other frame keeps the window's own
+ * bf16 value.  v then takes exactly the chain of drn_postprocess_u8.  Bit-exact.
+ *   video [B,3,Tw,H,W] bf16 (B passes of one window); prev_tail [B,3,O,H,W] bf16 or NULL (no ramp); ramp_w [O] fp32 on the device,
+ *   NULL iff prev_tail is NULL; out_u8 [B, write_hi - write_lo, H, W, 3].  All contiguous.
+ * H * W % 8 == 0 with 16-byte aligned inputs and an 8-byte aligned output runs 8 pixels per lane (16-byte loads, 24 contiguous
+ * bytes out); anything else one pixel per lane.  DRN_EINVAL (nothing launched): a null video / out_u8, only one of prev_tail /
+ * ramp_w, O < 0, ramp_at < 0, ramp_at + O > Tw, not (0 <= write_lo < write_hi <= Tw), a ramp with ramp_at < write_lo < ramp_at + O
+ * (a ramp is written whole or not at all), a non-positive size. */
+int drn_postprocess_window_u8(const void* video, const void* prev_tail, const void* ramp_w, void* out_u8,
+                              int B, int Tw, int H, int W, int O, int ramp_at, int write_lo, int write_hi,
+                              int normalize_normal, void* stream);
+
 /* ---- environment light of the forward renderer, turning about +Y over the clip (preprocess_envmap.py:440-450 with the unused
  * per-frame hook `y_rot = rotate_y(0.0)` (:340-348, :442) filled in, then hdr_mapping_official :119-140 and the `* 2 - 1` /
  * permute of nodes.py:283-304).  One launch over T*H*W pixels, one thread per output pixel of one frame: the direction
