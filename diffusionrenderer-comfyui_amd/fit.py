@@ -1,0 +1,160 @@
+"""Fit any clip to the model's grid (the nodes' opt-in `fit` input).
+
+The tokenizer takes T = 8k + 1 frames and H, W that are multiples of 16 (8 for the tokenizer, times the DiT's 2 x 2 patches).
+`plan_fit` decides, on the host, how a (T, H, W) clip gets there: a target size, a resize with the antialiased triangle filter of
+`F.interpolate(mode="bilinear", antialias=True)` written out as per-axis tap tables, a centre crop OF THE RESIZED picture (so the
+crop never cuts what the resize would have kept sharp), and a time index that repeats the last frame up to the next 8k + 1.
+`fit_frames` applies a plan to ComfyUI frames [B, T, H, W, 3] fp32 in [0, 1] and returns the model's [B, 3, T', H', W'] bf16 in
+[-1, 1]: resample, crop, pad, `* 2 - 1`, round, transpose.  Its torch backend is the specification and what CPU devices run;
+on a GPU one launch of drn_fit_frames (csrc/fit.hip) does all of it.  At scale 1 on both axes (identity or pure crop) both
+backends give the bits of today's ingest, `(image.permute(0, 4, 1, 2, 3) * 2 - 1).to(bf16)`, on the cropped frames.
+"""
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+GRID = 16          # H, W granularity of the model: 8 (tokenizer) x 2 (DiT patch)
+MAX_TAPS = 32      # per axis; a down-scale beyond about 15x is refused (drn_fit_frames: Ky, Kx in 1..32)
+MODES = ("crop", "stretch")
+
+
+@dataclass
+class FitPlan:
+    mode: str
+    T: int              # source frames: callers return the first T output frames
+    H: int
+    W: int
+    T_out: int          # T'
+    H_out: int          # H'
+    W_out: int          # W'
+    H_full: int         # the resized size the crop is cut from (stretch: the target itself)
+    W_full: int
+    y0: int
+    x0: int
+    t_idx: torch.Tensor     # int32 [T']: source frame of every output frame
+    y_lo_n: torch.Tensor    # int32 [H', 2]: first source row and tap count of every output row
+    y_w: torch.Tensor       # float32 [H', Ky]: its weights, zero-padded
+    x_lo_n: torch.Tensor
+    x_w: torch.Tensor
+    identity: bool
+
+    @property
+    def scale1_y(self) -> bool:
+        return self.H_full == self.H
+
+    @property
+    def scale1_x(self) -> bool:
+        return self.W_full == self.W
+
+
+def axis_taps(n_in: int, n_full: int, off: int, n_out: int):
+    """Tap table of output samples off .. off + n_out - 1 of an axis resized from n_in to n_full samples, in the arithmetic of
+    torch's antialiased bilinear resize: -> (lo_n int32 [n_out, 2], w float64 [n_out, K]).  Rows sum to 1 (normalised in
+    float64), taps of weight exactly 0 are dropped, the rest of a row is zero padding."""
+    scale = n_in / n_full
+    support = max(scale, 1.0)
+    i = np.arange(off, off + n_out, dtype=np.float64)
+    c = scale * (i + 0.5)
+    lo = np.maximum(0, (c - support + 0.5).astype(np.int64))          # the cast truncates, like torch's
+    hi = np.minimum((c + support + 0.5).astype(np.int64), n_in)
+    span = int((hi - lo).max())
+    j = lo[:, None] + np.arange(span, dtype=np.int64)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs((j - c[:, None] + 0.5) / support))
+    w[j >= hi[:, None]] = 0.0
+    w /= w.sum(axis=1, keepdims=True)
+    nz = w != 0.0
+    first = nz.argmax(axis=1)
+    last = span - 1 - nz[:, ::-1].argmax(axis=1)
+    n = last - first + 1
+    K = int(n.max())
+    cols = first[:, None] + np.arange(K)[None, :]
+    out = np.where(cols <= last[:, None], np.take_along_axis(w, np.minimum(cols, span - 1), axis=1), 0.0)
+    lo_n = np.stack([lo + first, n], axis=1).astype(np.int32)
+    return lo_n, out
+
+
+def _target(side: int, given: int, name: str) -> int:
+    if given:
+        if given < 0 or given % GRID:
+            raise ValueError(f"fit_{name} must be a positive multiple of {GRID} (or 0 = the source rounded down), got {given}")
+        return int(given)
+    if side < GRID:
+        raise ValueError(f"a source {name} of {side} is below the model's grid of {GRID}")
+    return side // GRID * GRID
+
+
+def plan_fit(T: int, H: int, W: int, mode: str, height: int = 0, width: int = 0, windowed: bool = False) -> FitPlan:
+    """How a clip of T frames of H x W reaches the model's grid.  mode 'stretch': the whole picture resampled to the target;
+    'crop': resized to cover the target, then centre-cropped (both targets 0: a pure centre crop at scale 1).  height / width:
+    the target, multiples of 16; 0 = that side of the source rounded down to one.  windowed: the clip will be rendered in
+    windows of 8k + 1 frames, which take any T, so no frames are added."""
+    if mode not in MODES:
+        raise ValueError(f"fit mode must be one of {MODES}, got {mode!r}")
+    if T < 1 or H < 1 or W < 1:
+        raise ValueError(f"empty clip: T, H, W = {T}, {H}, {W}")
+    H_out, W_out = _target(H, height, "height"), _target(W, width, "width")
+    if mode == "stretch":
+        H_full, W_full = H_out, W_out
+    else:
+        s = 1.0 if not height and not width else max(H_out / H, W_out / W)
+        H_full = max(H_out, int(math.floor(H * s + 0.5)))
+        W_full = max(W_out, int(math.floor(W * s + 0.5)))
+    y0, x0 = (H_full - H_out) // 2, (W_full - W_out) // 2
+    y_lo_n, y_w = axis_taps(H, H_full, y0, H_out)
+    x_lo_n, x_w = axis_taps(W, W_full, x0, W_out)
+    for name, w in (("height", y_w), ("width", x_w)):
+        if w.shape[1] > MAX_TAPS:
+            raise ValueError(f"the {name} down-scale needs {w.shape[1]} taps per output sample; at most {MAX_TAPS} are supported")
+    T_out = T if (T - 1) % 8 == 0 or windowed else (T - 1) // 8 * 8 + 9
+    t_idx = np.minimum(np.arange(T_out), T - 1).astype(np.int32)
+
+    def single(lo_n, w, n_in):
+        return w.shape[1] == 1 and len(lo_n) == n_in and bool((lo_n[:, 0] == np.arange(n_in)).all()) and bool((w == 1.0).all())
+    identity = T_out == T and single(y_lo_n, y_w, H) and single(x_lo_n, x_w, W)
+    return FitPlan(mode, T, H, W, T_out, H_out, W_out, H_full, W_full, y0, x0, torch.from_numpy(t_idx),
+                   torch.from_numpy(y_lo_n), torch.from_numpy(y_w.astype(np.float32)),
+                   torch.from_numpy(x_lo_n), torch.from_numpy(x_w.astype(np.float32)), identity)
+
+
+def _fit_torch(image_5d, plan: FitPlan, device, round_bf16=True):
+    """The specification: gather frames, antialiased resize, crop slice, * 2 - 1, bf16.  An axis at scale 1 is sliced, not
+    interpolated, so a pure crop is a copy."""
+    x = image_5d.to(device=device, dtype=torch.float32).permute(0, 4, 1, 2, 3)
+    x = x.index_select(2, plan.t_idx.to(device=x.device, dtype=torch.long))
+    B = x.shape[0]
+    x = x.permute(0, 2, 1, 3, 4).reshape(B * plan.T_out, 3, plan.H, plan.W)
+    if plan.scale1_y:
+        x = x[:, :, plan.y0:plan.y0 + plan.H_out]
+    if plan.scale1_x:
+        x = x[:, :, :, plan.x0:plan.x0 + plan.W_out]
+    if not (plan.scale1_y and plan.scale1_x):
+        size = (plan.H_out if plan.scale1_y else plan.H_full, plan.W_out if plan.scale1_x else plan.W_full)
+        x = F.interpolate(x.contiguous(), size=size, mode="bilinear", antialias=True, align_corners=False)
+        if not plan.scale1_y:
+            x = x[:, :, plan.y0:plan.y0 + plan.H_out]
+        if not plan.scale1_x:
+            x = x[:, :, :, plan.x0:plan.x0 + plan.W_out]
+    x = x.reshape(B, plan.T_out, 3, plan.H_out, plan.W_out).permute(0, 2, 1, 3, 4) * 2.0 - 1.0
+    return x.to(torch.bfloat16).contiguous() if round_bf16 else x.contiguous()
+
+
+def fit_frames(image_5d: torch.Tensor, plan: FitPlan, device, backend: str = "auto") -> torch.Tensor:
+    """[B, T, H, W, 3] fp32 in [0, 1] -> [B, 3, T', H', W'] bf16 in [-1, 1] on `device`.  backend: 'auto' = the HIP kernel
+    (drn_fit_frames) on a GPU device and torch on a CPU device; 'torch' / 'hip' force a path ('hip' needs a GPU device)."""
+    if backend not in ("auto", "torch", "hip"):
+        raise ValueError(f"unknown backend {backend!r}")
+    if image_5d.ndim != 5 or image_5d.shape[-1] != 3:
+        raise ValueError(f"fit needs [B, T, H, W, 3] frames, got {tuple(image_5d.shape)}")
+    if tuple(image_5d.shape[1:4]) != (plan.T, plan.H, plan.W):
+        raise ValueError(f"the plan was made for {(plan.T, plan.H, plan.W)} frames, got {tuple(image_5d.shape[1:4])}")
+    on_gpu = torch.device(device).type == "cuda"
+    if backend == "hip" and not on_gpu:
+        raise ValueError(f"backend='hip' needs a GPU device, got {device!r} (the torch path is what CPU devices run)")
+    if backend == "torch" or not on_gpu:
+        return _fit_torch(image_5d, plan, device)
+    from . import native
+    src = image_5d.to(device=device, dtype=torch.float32).contiguous()
+    return native.fit_frames(src, plan.t_idx, plan.y_lo_n, plan.y_w, plan.x_lo_n, plan.x_w)

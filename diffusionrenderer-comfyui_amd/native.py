@@ -115,6 +115,7 @@ SIGNATURES = {
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "drn_fit_frames": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
@@ -852,6 +853,31 @@ def env_project(cube, vec, rot, log_scale=10000.0, out=None):
         assert t.dtype == torch.float32 and t.shape == (3, T, H, W) and t.is_contiguous()
     _check(load_library().drn_env_project(_ptr(cube), R, _ptr(vec), _ptr(rot), _ptr(out[0]), _ptr(out[1]), T, H, W, log_scale,
                                           _stream()), "drn_env_project")
+    return out
+
+
+def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
+    """Clip ingest with a fit to the model's grid (drn_fit_frames; the plan: fit.plan_fit).  src [B, Ts, Hs, Ws, 3] fp32 on the
+    device, contiguous; the plan's tables as HOST tensors (t_idx int32 [Td], per axis lo_n int32 [n_out, 2] and w fp32 [n_out, K]):
+    they are checked here, where their contents can be read, and uploaded -> [B, 3, Td, Hd, Wd] bf16 in [-1, 1].  out: such a
+    tensor to write into."""
+    assert src.dtype == torch.float32 and src.ndim == 5 and src.shape[-1] == 3 and src.is_contiguous(), \
+        "contiguous fp32 [B, T, H, W, 3] frames required"
+    B, Ts, Hs, Ws, _ = src.shape
+    assert t_idx.dtype == torch.int32 and t_idx.ndim == 1 and 0 <= int(t_idx.min()) and int(t_idx.max()) < Ts, "t_idx outside the clip"
+    for lo_n, w, n_in in ((y_lo_n, y_w, Hs), (x_lo_n, x_w, Ws)):
+        assert lo_n.dtype == torch.int32 and w.dtype == torch.float32 and lo_n.ndim == 2 and w.ndim == 2
+        assert lo_n.shape == (w.shape[0], 2) and 1 <= w.shape[1] <= 32, "tap table shapes"
+        lo, n = lo_n[:, 0].long(), lo_n[:, 1].long()
+        assert bool((lo >= 0).all()) and bool((n >= 1).all()) and bool((n <= w.shape[1]).all()) and bool((lo + n <= n_in).all()), \
+            "taps outside the source"
+    Td, Hd, Wd = t_idx.shape[0], y_lo_n.shape[0], x_lo_n.shape[0]
+    if out is None:
+        out = torch.empty((B, 3, Td, Hd, Wd), dtype=torch.bfloat16, device=src.device)
+    assert out.dtype == torch.bfloat16 and tuple(out.shape) == (B, 3, Td, Hd, Wd) and out.is_contiguous()
+    dev = [t.contiguous().to(src.device) for t in (t_idx, y_lo_n, y_w, x_lo_n, x_w)]
+    _check(load_library().drn_fit_frames(_ptr(src), _ptr(out), B, Ts, Hs, Ws, Td, Hd, Wd, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]),
+                                         y_w.shape[1], _ptr(dev[3]), _ptr(dev[4]), x_w.shape[1], _stream()), "drn_fit_frames")
     return out
 
 

@@ -38,6 +38,26 @@ def _window_inputs():
                                                   "0 = hard cuts"})}
 
 
+def _fit_inputs():
+    """Optional inputs of both renderers for clips off the model's grid (fit.py)."""
+    return {"fit": (["off", "crop", "stretch"],
+                    {"default": "off",
+                     "tooltip": "off: the clip must already be T = 8k+1 frames of H, W multiples of 16.  crop: resize (antialiased) "
+                                "to cover the target size, then centre-crop; stretch: resize the whole picture to it.  Short clips "
+                                "repeat their last frame up to the next 8k+1 and come back at their own length.  The outputs keep "
+                                "the model's size: they are not resampled back (a crop cannot be undone)"}),
+            "fit_height": ("INT", {"default": 0, "min": 0, "max": 4096, "step": 16,
+                                   "tooltip": "target height, a multiple of 16; 0 = the source height rounded down to one "
+                                              "(with fit_width 0 too, crop is a pure centre crop)"}),
+            "fit_width": ("INT", {"default": 0, "min": 0, "max": 4096, "step": 16,
+                                  "tooltip": "target width, a multiple of 16; 0 = the source width rounded down to one"})}
+
+
+def _fit_plan(T, H, W, fit, fit_height, fit_width, window_frames):
+    from .fit import plan_fit
+    return plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames)
+
+
 def standardize_to_5d(image, name="image") -> torch.Tensor:
     """list / (H,W,C) / (B,H,W,C)->T=1 / (B,T,H,W,C) -> (B,T,H,W,C)   (reference nodes.py:156-177, :258-268)."""
     if isinstance(image, list):
@@ -112,7 +132,7 @@ class Cosmos1InverseRenderer:
             "required": {"pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "image": ("IMAGE",)},
             "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1}),
                          "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
-                         **_window_inputs()},
+                         **_window_inputs(), **_fit_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -120,19 +140,28 @@ class Cosmos1InverseRenderer:
     FUNCTION = "run_inverse_pass"
     CATEGORY = "Cosmos1"
 
-    def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8):
+    def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
+                         fit="off", fit_height=0, fit_width=0):
         pipeline.set_model_type("inverse")
         pipeline.guidance = guidance
         pipeline.seed = seed
         pipeline.window_frames = window_frames
         pipeline.window_overlap = window_overlap
         image_5d = standardize_to_5d(image)
-        image_tensor = image_5d.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
+        if fit == "off":
+            image_tensor = image_5d.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
+            keep = None
+        else:
+            # resize / crop / pad in time, * 2 - 1, bf16 and the transpose in one launch on the pipeline's device (fit.py)
+            from .fit import fit_frames
+            plan = _fit_plan(*image_5d.shape[1:4], fit, fit_height, fit_width, window_frames)
+            image_tensor = fit_frames(image_5d, plan, device=getattr(pipeline, "device", "cuda"))
+            keep = plan.T
         outputs = {}
         pbar = _progress_bar(len(INVERSE_PASSES))
 
         def to_image(out):
-            t = torch.from_numpy(out).float() / 255.0
+            t = torch.from_numpy(out[:, :keep]).float() / 255.0           # a clip padded in time comes back at its own length
             b, tt, h, w, c = t.shape
             return t.reshape(b * tt, h, w, c)
 
@@ -180,7 +209,7 @@ class Cosmos1ForwardRenderer:
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
-                         **_window_inputs()},
+                         **_window_inputs(), **_fit_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE",)
@@ -189,7 +218,7 @@ class Cosmos1ForwardRenderer:
 
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
-                         env_spin=0.0, window_frames=0, window_overlap=8):
+                         env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0):
         pipeline.set_model_type("forward")
         pipeline.guidance = guidance
         pipeline.seed = seed
@@ -199,9 +228,26 @@ class Cosmos1ForwardRenderer:
                        "metallic": "metallic"}
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         data_batch = {}
-        for name, t in inputs.items():
-            t5 = standardize_to_5d(t, name)
-            data_batch[key_mapping[name]] = t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
+        keep = None
+        if fit == "off":
+            for name, t in inputs.items():
+                t5 = standardize_to_5d(t, name)
+                data_batch[key_mapping[name]] = t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
+        else:
+            # all five G-buffers through ONE plan (fit.py): they must be the same clip geometry
+            from .fit import fit_frames
+            maps = {name: standardize_to_5d(t, name) for name, t in inputs.items()}
+            shape = tuple(maps["depth"].shape[1:4])
+            for name, t5 in maps.items():
+                if tuple(t5.shape[1:4]) != shape:
+                    raise ValueError(f"fit needs G-buffers of one size: '{name}' is (T, H, W) = {tuple(t5.shape[1:4])}, "
+                                     f"'depth' is {shape}")
+            plan = _fit_plan(*shape, fit, fit_height, fit_width, window_frames)
+            for name, t5 in maps.items():
+                data_batch[key_mapping[name]] = fit_frames(t5, plan, device=getattr(pipeline, "device", "cuda"))
+            keep = plan.T
+            # frame t keeps the angle radians(env_spin) * t / T of the clip as handed in; padded frames turn on and are cut away
+            env_spin = env_spin * plan.T_out / plan.T
         B, _, T, H, W = data_batch["depth"].shape
         data_batch["video"] = data_batch["depth"]
         # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
@@ -214,7 +260,7 @@ class Cosmos1ForwardRenderer:
         data_batch["env_log"] = env["env_log"].expand(B, -1, -1, -1, -1)
         data_batch["env_nrm"] = env["env_nrm"].expand(B, -1, T, -1, -1)
         out = pipeline.generate_video(data_batch=data_batch, seed=seed)
-        return (torch.from_numpy(out).float() / 255.0,)
+        return (torch.from_numpy(out[:, :keep]).float() / 255.0,)
 
 
 class LoadHDRImage:

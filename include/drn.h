@@ -1,6 +1,7 @@
 /* drn.h - C ABI of libdrn.so: the MI355X (gfx950) kernels behind the DiffusionRenderer
  * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer),
- * and the forward renderer's per-frame environment-light projection (drn_env_project).
+ * the forward renderer's per-frame environment-light projection (drn_env_project) and the
+ * nodes' clip ingest with a fit to the model's grid (drn_fit_frames).
  *
  * The reference (eggsbenedicto/DiffusionRenderer-ComfyUI) is pure Python/torch and has no FFI;
  * each entry point below names the reference code (file:line under /root/reference) whose
@@ -498,6 +499,23 @@ int drn_postprocess_window_u8(const void* video, const void* prev_tail, const vo
  * or W < 1, T*H*W >= 2^31, a pointer not 4-byte aligned. */
 int drn_env_project(const float* cube, int R, const float* vec, const float* rot, float* env_ldr, float* env_log,
                     int T, int H, int W, float log_scale, void* stream);
+
+/* ---- clip ingest with a fit to the model's grid (the nodes' `image.permute(0, 4, 1, 2, 3) * 2.0 - 1.0`, nodes.py:156-190, with
+ * a resize, a crop and a time padding in front that the reference does not have; plan and torch specification: fit.py).
+ * ONE launch: dst[b][ch][t][y][x] = bf16(2 * acc - 1),
+ *   acc = sum_ky y_w[y][ky] * (sum_kx x_w[x][kx] * src[b][t_idx[t]][y_lo + ky][x_lo + kx][ch]),
+ * all in fp32 (fma accumulation from 0 in tap order, the row pass first), 2 * acc - 1 rounded once, then round to nearest even.
+ *   src [B,Ts,Hs,Ws,3] fp32 and dst [B,3,Td,Hd,Wd] bf16, contiguous; tables on the device: t_idx int32 [Td] (source frame of
+ *   every output frame), per axis lo_n int32 [n_out][2] (first source sample, tap count n in 1..K) and w fp32 [n_out][K]
+ *   (zero-padded past n; the crop offset is folded into lo).
+ * The loops run over every row's own n: a source index outside [lo, lo + n) is never touched and padded weights are not taps, so
+ * a single tap of weight 1.0 on both axes copies (bit for bit what `* 2 - 1` and the bf16 cast give).  lo, n and t_idx are
+ * clamped into the source before use; what they should hold is checked on the host (native.fit_frames).
+ * DRN_EINVAL (nothing launched): a null pointer, a non-positive size, Ky or Kx outside 1..32, Hd or Wd not a multiple of 16,
+ * B*3*Td*Hd*Wd or B*Ts*Hs*Ws*3 >= 2^31, src or a table not 4-byte aligned, dst not 16-byte aligned. */
+int drn_fit_frames(const float* src, void* dst_bf16, int B, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
+                   const int* t_idx, const int* y_lo_n, const float* y_w, int Ky,
+                   const int* x_lo_n, const float* x_w, int Kx, void* stream);
 
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
