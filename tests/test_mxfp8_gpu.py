@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 import mx_emul as MX
 from conftest import load_golden, rel_l2, tiny_net
+from dit_refs import SENTINEL, is_sentinel
 
 pytestmark = pytest.mark.gpu
 
@@ -97,12 +98,14 @@ def _gemm_check(pkg, gpu, M, N, K, epi, seed=0):
     aq, wq = Nn.mx_quant(a), Nn.mx_quant(w)
     lin = MX.dequantize(aq.q, aq.scales) @ MX.dequantize(wq.q, wq.scales).t()          # fp32 on the device
     gate = resid = None
+    # the output starts as NaN sentinels: a tile that is never written cannot pass on what the allocator's block held before
+    fresh = torch.full((M, N), SENTINEL, dtype=torch.int16, device=gpu).view(BF)
     if epi == Nn.EPI_NONE:
         ref = lin
-        out = Nn.gemm_mxfp8(aq, wq)
+        out = Nn.gemm_mxfp8(aq, wq, out=fresh)
     elif epi == Nn.EPI_GELU:
         ref = F.gelu(lin)
-        out = Nn.gemm_mxfp8(aq, wq, epilogue=epi)
+        out = Nn.gemm_mxfp8(aq, wq, out=fresh, epilogue=epi)
     else:
         gate = rnd((1, N), 0.5, seed + 2).to(gpu)
         resid = rnd((M, N), 1.0, seed + 3).to(gpu)
@@ -110,6 +113,7 @@ def _gemm_check(pkg, gpu, M, N, K, epi, seed=0):
         out = resid.clone()
         Nn.gemm_mxfp8(aq, wq, out=out, epilogue=epi, gate=gate, residual=out)
     torch.cuda.synchronize()
+    assert not bool(is_sentinel(out).any()), (M, N, K, epi, "cells of the output were never written")
     e = rel_l2(out.float(), ref)
     assert e < 3e-3, (M, N, K, epi, e)
     return e

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 import mx_emul as MX
 from conftest import load_golden, rel_l2, tiny_net
+from dit_refs import SENTINEL, is_sentinel
 
 pytestmark = pytest.mark.gpu
 
@@ -92,12 +93,14 @@ def _gemm_check(pkg, gpu, M, N, K, epi, splits, rows_per_batch=None, seed=0):
     w = rnd((N, K), K ** -0.5, seed + 1).to(gpu)
     aq, wq = Nn.mx_quant(a), Nn.mx_quant(w)
     lin = MX.dequantize(aq.q, aq.scales) @ MX.dequantize(wq.q, wq.scales).t()          # fp32 on the device
+    # the output starts as NaN sentinels: a tile that is never written cannot pass on what the allocator's block held before
+    fresh = torch.full((M, N), SENTINEL, dtype=torch.int16, device=gpu).view(BF)
     if epi == Nn.EPI_NONE:
         ref = lin
-        out = Nn.gemm_mxfp8(aq, wq, rows_per_batch=rows_per_batch, splitk=splits)
+        out = Nn.gemm_mxfp8(aq, wq, out=fresh, rows_per_batch=rows_per_batch, splitk=splits)
     elif epi == Nn.EPI_GELU:
         ref = F.gelu(lin)
-        out = Nn.gemm_mxfp8(aq, wq, epilogue=epi, rows_per_batch=rows_per_batch, splitk=splits)
+        out = Nn.gemm_mxfp8(aq, wq, out=fresh, epilogue=epi, rows_per_batch=rows_per_batch, splitk=splits)
     else:
         clips = M // rows_per_batch if rows_per_batch else 1
         gate = rnd((clips, N), 0.5, seed + 2).to(gpu)
@@ -106,6 +109,7 @@ def _gemm_check(pkg, gpu, M, N, K, epi, splits, rows_per_batch=None, seed=0):
         out = resid.clone()
         Nn.gemm_mxfp8(aq, wq, out=out, epilogue=epi, gate=gate, residual=out, rows_per_batch=rows_per_batch, splitk=splits)
     torch.cuda.synchronize()
+    assert not bool(is_sentinel(out).any()), (M, N, K, epi, splits, "cells of the output were never written")
     e = rel_l2(out.float(), ref)
     print(f"mxfp8 small-M gemm M={M} rpb={rows_per_batch} N={N} K={K} epi={epi} splits={splits}: rel-L2 vs emulation {e:.2e}")
     assert e < 3e-3, (M, N, K, epi, splits, e)
