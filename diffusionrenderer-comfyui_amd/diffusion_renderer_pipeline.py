@@ -7,6 +7,7 @@ search order, the md5 config cache, every tensor of the batch cast to (device, d
 key exists.  Only the pre-loaded-model path is contractual: the reference's dynamic loader calls a method that
 does not exist; here it raises a clear error instead.
 """
+import dataclasses
 import hashlib
 import json
 import os
@@ -17,6 +18,7 @@ import torch
 
 from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
+from .fit import restore_frames
 from .model_diffusion_renderer import CleanDiffusionRendererModel
 from .windows import plan_windows, ramp_weights
 
@@ -43,6 +45,9 @@ class CleanDiffusionRendererPipeline:
         # become uint8
         self.window_frames = 0
         self.window_overlap = 8
+        # the fit's way back (fit.py): a RestorePlan -> the uint8 outputs are resampled to the source's size on the device, before
+        # the D2H copy; None = the outputs keep the model's size (today's path, today's bits)
+        self.restore_plan = None
         self.device = torch.device("cuda")     # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
@@ -159,7 +164,7 @@ class CleanDiffusionRendererPipeline:
         sample = self._sample(data_batch, seed, init_noise)
         video = self.model.decode(sample)
         u8 = N.postprocess_u8(video.to(self.dtype).contiguous(), normalize_normal)   # fused :299-318
-        return u8.cpu().numpy()
+        return self._restored(u8).cpu().numpy()
 
     def generate_video_passes(self, data_batch: Dict[str, torch.Tensor], normalize_normal, seed: int = None,
                               init_noise: torch.Tensor = None):
@@ -177,7 +182,7 @@ class CleanDiffusionRendererPipeline:
         outs = []
         for p, flag in enumerate(flags):
             video = self.model.decode(sample[p:p + 1])
-            outs.append(N.postprocess_u8(video.to(self.dtype).contiguous(), bool(flag)))
+            outs.append(self._restored(N.postprocess_u8(video.to(self.dtype).contiguous(), bool(flag))))
         return [o.cpu().numpy() for o in outs]
 
     def generate_video_each(self, data_batches, normalize_normal, seed: int = None, init_noise: torch.Tensor = None):
@@ -192,6 +197,14 @@ class CleanDiffusionRendererPipeline:
         if plan is None:
             return [self.generate_video(b, f, seed, init_noise) for b, f in zip(batches, flags)]
         return [o[0] for o in self._generate_windowed(batches, [[f] for f in flags], seed, init_noise, plan)]
+
+    def _restored(self, u8, frames=None):
+        """The uint8 result [B, T', H', W', 3] at the source's size where a restore plan is set (fit.restore_frames, on the device),
+        cut to the plan's T frames, or to `frames` (a window's written frames: a windowed clip has no time padding)."""
+        if self.restore_plan is None:
+            return u8
+        rplan = self.restore_plan if frames is None else dataclasses.replace(self.restore_plan, T=int(frames))
+        return restore_frames(u8, rplan)
 
     def _window_plan(self, data_batch):
         """The windows of this clip, or None where today's single-sequence path applies (windows off, or a clip that fits one)."""
@@ -237,6 +250,7 @@ class CleanDiffusionRendererPipeline:
                     prev = carry[c][p] if i > 0 and O else None
                     u8 = N.postprocess_window_u8(video, prev, ramp if prev is not None else None, win.ramp_at, win.write_lo,
                                                  win.write_hi, flag)
+                    u8 = self._restored(u8, frames=u8.shape[1])       # frames are independent: window by window = the whole clip
                     if outs[c][p] is None:
                         outs[c][p] = torch.empty((1, T) + tuple(u8.shape[2:]), dtype=torch.uint8)
                     outs[c][p][:, win.out_at:win.out_at + u8.shape[1]].copy_(u8)      # D2H straight into the clip's frames

@@ -8,6 +8,10 @@ crop never cuts what the resize would have kept sharp), and a time index that re
 [-1, 1]: resample, crop, pad, `* 2 - 1`, round, transpose.  Its torch backend is the specification and what CPU devices run;
 on a GPU one launch of drn_fit_frames (csrc/fit.hip) does all of it.  At scale 1 on both axes (identity or pure crop) both
 backends give the bits of today's ingest, `(image.permute(0, 4, 1, 2, 3) * 2 - 1).to(bf16)`, on the cropped frames.
+
+The way back (the nodes' `fit_restore`): `plan_restore` turns the plan of a fit that kept the whole picture round, and
+`restore_frames` resamples the pipeline's uint8 outputs [B, T', H', W', 3] to the source's [B, T, H, W, 3] with the same filter -
+the torch backend again the specification, on a GPU one launch of drn_restore_frames_u8 (csrc/restore.hip).
 """
 import math
 from dataclasses import dataclass
@@ -117,6 +121,86 @@ def plan_fit(T: int, H: int, W: int, mode: str, height: int = 0, width: int = 0,
     return FitPlan(mode, T, H, W, T_out, H_out, W_out, H_full, W_full, y0, x0, torch.from_numpy(t_idx),
                    torch.from_numpy(y_lo_n), torch.from_numpy(y_w.astype(np.float32)),
                    torch.from_numpy(x_lo_n), torch.from_numpy(x_w.astype(np.float32)), identity)
+
+
+@dataclass
+class RestorePlan:
+    T: int                  # frames to return: the source clip's own length (the time padding is cut)
+    H_model: int            # the size the outputs arrive in: the fit's H', W'
+    W_model: int
+    H: int                  # the size they leave in: the source's
+    W: int
+    y_lo_n: torch.Tensor    # int32 [H, 2], float32 [H, Ky]: the tables of axis_taps(H', H, 0, H)
+    y_w: torch.Tensor
+    x_lo_n: torch.Tensor
+    x_w: torch.Tensor
+    identity: bool          # both axes single taps of weight 1.0: restore_frames only cuts in time
+
+
+def plan_restore(plan: FitPlan) -> RestorePlan:
+    """The way back of a fit that kept the whole picture ('stretch', or a 'crop' that cut nothing): the model-size uint8 outputs
+    resampled to the source's H x W with the same antialiased triangle filter, and cut to its T frames.  A crop that cut cannot
+    be undone: ValueError."""
+    whole = plan.mode == "stretch" or (plan.y0 == 0 and plan.x0 == 0 and plan.H_full == plan.H_out and plan.W_full == plan.W_out)
+    if not whole:
+        raise ValueError(f"a crop cannot be undone: this fit cut {plan.H_full} x {plan.W_full} down to {plan.H_out} x {plan.W_out}, "
+                         "so the outputs cannot be restored to the source size; use fit = 'stretch' (or fit_restore off)")
+    y_lo_n, y_w = axis_taps(plan.H_out, plan.H, 0, plan.H)
+    x_lo_n, x_w = axis_taps(plan.W_out, plan.W, 0, plan.W)
+    for name, w in (("height", y_w), ("width", x_w)):
+        if w.shape[1] > MAX_TAPS:
+            raise ValueError(f"restoring the {name} needs {w.shape[1]} taps per output sample; at most {MAX_TAPS} are supported")
+
+    def single(lo_n, w, n_in):
+        return w.shape[1] == 1 and len(lo_n) == n_in and bool((lo_n[:, 0] == np.arange(n_in)).all()) and bool((w == 1.0).all())
+    identity = single(y_lo_n, y_w, plan.H_out) and single(x_lo_n, x_w, plan.W_out)
+    return RestorePlan(plan.T, plan.H_out, plan.W_out, plan.H, plan.W,
+                       torch.from_numpy(y_lo_n), torch.from_numpy(y_w.astype(np.float32)),
+                       torch.from_numpy(x_lo_n), torch.from_numpy(x_w.astype(np.float32)), identity)
+
+
+def _taps_torch(x, dim, lo_n, w):
+    """One axis of the specification: the plan's fp32 table applied tap by tap, k = 0 .. K - 1, an index_select and a
+    multiply-add each.  Padded taps have weight 0 and an index held inside the axis."""
+    lo = lo_n[:, 0].to(device=x.device, dtype=torch.long)
+    w = w.to(x.device)
+    shape = [1] * x.ndim
+    shape[dim] = -1
+    acc = None
+    for k in range(w.shape[1]):
+        term = x.index_select(dim, (lo + k).clamp_max(x.shape[dim] - 1)) * w[:, k].reshape(shape)
+        acc = term if acc is None else acc + term
+    return acc
+
+
+def _restore_torch(u8, rplan: RestorePlan, rounded=True):
+    """The specification: fp32 on the 0..255 scale, the horizontal pass, then the vertical one, round half to even, clamp."""
+    x = u8[:, :rplan.T].to(torch.float32)
+    x = _taps_torch(x, 3, rplan.x_lo_n, rplan.x_w)
+    x = _taps_torch(x, 2, rplan.y_lo_n, rplan.y_w)
+    return x.round().clamp(0.0, 255.0).to(torch.uint8) if rounded else x
+
+
+def restore_frames(u8: torch.Tensor, rplan: RestorePlan, backend: str = "auto") -> torch.Tensor:
+    """uint8 [B, T', H', W', 3] at the model's size -> uint8 [B, T, H, W, 3] at the source's, frames 0 .. T - 1, on the same
+    device.  backend: 'auto' = the HIP kernel (drn_restore_frames_u8) on a GPU tensor and torch on a CPU tensor; 'torch' / 'hip'
+    force a path ('hip' needs a GPU tensor).  An identity plan launches nothing: the input, cut in time.  Normal maps are
+    resampled like any picture and not renormalised."""
+    if backend not in ("auto", "torch", "hip"):
+        raise ValueError(f"unknown backend {backend!r}")
+    if u8.dtype != torch.uint8 or u8.ndim != 5 or u8.shape[-1] != 3:
+        raise ValueError(f"restore needs uint8 [B, T, H, W, 3] frames, got {u8.dtype} {tuple(u8.shape)}")
+    if tuple(u8.shape[2:4]) != (rplan.H_model, rplan.W_model) or u8.shape[1] < rplan.T:
+        raise ValueError(f"the plan was made for at least {rplan.T} frames of {(rplan.H_model, rplan.W_model)}, "
+                         f"got {tuple(u8.shape[1:4])}")
+    if backend == "hip" and not u8.is_cuda:
+        raise ValueError(f"backend='hip' needs a GPU tensor, got one on {u8.device} (the torch path is what CPU devices run)")
+    if rplan.identity:
+        return u8[:, :rplan.T]
+    if backend == "torch" or not u8.is_cuda:
+        return _restore_torch(u8, rplan)
+    from . import native
+    return native.restore_frames(u8.contiguous(), rplan.T, rplan.y_lo_n, rplan.y_w, rplan.x_lo_n, rplan.x_w)
 
 
 def _fit_torch(image_5d, plan: FitPlan, device, round_bf16=True):

@@ -116,6 +116,7 @@ SIGNATURES = {
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     "drn_fit_frames": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    "drn_restore_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
@@ -878,6 +879,32 @@ def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
     dev = [t.contiguous().to(src.device) for t in (t_idx, y_lo_n, y_w, x_lo_n, x_w)]
     _check(load_library().drn_fit_frames(_ptr(src), _ptr(out), B, Ts, Hs, Ws, Td, Hd, Wd, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]),
                                          y_w.shape[1], _ptr(dev[3]), _ptr(dev[4]), x_w.shape[1], _stream()), "drn_fit_frames")
+    return out
+
+
+def restore_frames(src, T, y_lo_n, y_w, x_lo_n, x_w, out=None):
+    """The fit's way back on uint8 outputs (drn_restore_frames_u8; the plan: fit.plan_restore).  src [B, Ts, Hs, Ws, 3] uint8 on
+    the device, contiguous, at any byte alignment; T <= Ts frames to return; the plan's tables as HOST tensors (per axis lo_n int32
+    [n_out, 2] and w fp32 [n_out, K]): they are checked here, where their contents can be read, and uploaded -> uint8
+    [B, T, Hd, Wd, 3].  out: such a tensor to write into."""
+    assert src.dtype == torch.uint8 and src.ndim == 5 and src.shape[-1] == 3 and src.is_contiguous(), \
+        "contiguous uint8 [B, T, H, W, 3] frames required"
+    B, Ts, Hs, Ws, _ = src.shape
+    assert 1 <= T <= Ts, "frames to return outside the clip"
+    for lo_n, w, n_in in ((y_lo_n, y_w, Hs), (x_lo_n, x_w, Ws)):
+        assert lo_n.dtype == torch.int32 and w.dtype == torch.float32 and lo_n.ndim == 2 and w.ndim == 2
+        assert lo_n.shape == (w.shape[0], 2) and 1 <= w.shape[1] <= 32, "tap table shapes"
+        lo, n = lo_n[:, 0].long(), lo_n[:, 1].long()
+        assert bool((lo >= 0).all()) and bool((n >= 1).all()) and bool((n <= w.shape[1]).all()) and bool((lo + n <= n_in).all()), \
+            "taps outside the source"
+    Hd, Wd = y_lo_n.shape[0], x_lo_n.shape[0]
+    if out is None:
+        out = torch.empty((B, T, Hd, Wd, 3), dtype=torch.uint8, device=src.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (B, T, Hd, Wd, 3) and out.is_contiguous()
+    dev = [t.contiguous().to(src.device) for t in (y_lo_n, y_w, x_lo_n, x_w)]
+    _check(load_library().drn_restore_frames_u8(_ptr(src), _ptr(out), B, Ts, Hs, Ws, T, Hd, Wd, _ptr(dev[0]), _ptr(dev[1]),
+                                                y_w.shape[1], _ptr(dev[2]), _ptr(dev[3]), x_w.shape[1], _stream()),
+           "drn_restore_frames_u8")
     return out
 
 

@@ -50,12 +50,25 @@ def _fit_inputs():
                                    "tooltip": "target height, a multiple of 16; 0 = the source height rounded down to one "
                                               "(with fit_width 0 too, crop is a pure centre crop)"}),
             "fit_width": ("INT", {"default": 0, "min": 0, "max": 4096, "step": 16,
-                                  "tooltip": "target width, a multiple of 16; 0 = the source width rounded down to one"})}
+                                  "tooltip": "target width, a multiple of 16; 0 = the source width rounded down to one"}),
+            "fit_restore": ("BOOLEAN", {"default": False,
+                                        "tooltip": "return the outputs at the source size: they are resampled back (antialiased) "
+                                                   "on the GPU.  Only works with a fit that kept the whole picture: stretch, or a "
+                                                   "crop that cut nothing; any other crop is refused.  Ignored with fit off.  "
+                                                   "Normal maps are resampled like any picture and not renormalised"})}
 
 
 def _fit_plan(T, H, W, fit, fit_height, fit_width, window_frames):
     from .fit import plan_fit
     return plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames)
+
+
+def _restore_plan(plan, fit_restore):
+    """What the pipeline's `restore_plan` is for this call: the way back of the fit's plan, or None (ValueError: a crop that cut)."""
+    if not fit_restore:
+        return None
+    from .fit import plan_restore
+    return plan_restore(plan)
 
 
 def standardize_to_5d(image, name="image") -> torch.Tensor:
@@ -141,12 +154,13 @@ class Cosmos1InverseRenderer:
     CATEGORY = "Cosmos1"
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
-                         fit="off", fit_height=0, fit_width=0):
+                         fit="off", fit_height=0, fit_width=0, fit_restore=False):
         pipeline.set_model_type("inverse")
         pipeline.guidance = guidance
         pipeline.seed = seed
         pipeline.window_frames = window_frames
         pipeline.window_overlap = window_overlap
+        pipeline.restore_plan = None
         image_5d = standardize_to_5d(image)
         if fit == "off":
             image_tensor = image_5d.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
@@ -155,6 +169,7 @@ class Cosmos1InverseRenderer:
             # resize / crop / pad in time, * 2 - 1, bf16 and the transpose in one launch on the pipeline's device (fit.py)
             from .fit import fit_frames
             plan = _fit_plan(*image_5d.shape[1:4], fit, fit_height, fit_width, window_frames)
+            pipeline.restore_plan = _restore_plan(plan, fit_restore)      # the outputs come back at the source's size
             image_tensor = fit_frames(image_5d, plan, device=getattr(pipeline, "device", "cuda"))
             keep = plan.T
         outputs = {}
@@ -218,12 +233,14 @@ class Cosmos1ForwardRenderer:
 
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
-                         env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0):
+                         env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
+                         fit_restore=False):
         pipeline.set_model_type("forward")
         pipeline.guidance = guidance
         pipeline.seed = seed
         pipeline.window_frames = window_frames
         pipeline.window_overlap = window_overlap
+        pipeline.restore_plan = None
         key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                        "metallic": "metallic"}
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
@@ -243,6 +260,7 @@ class Cosmos1ForwardRenderer:
                     raise ValueError(f"fit needs G-buffers of one size: '{name}' is (T, H, W) = {tuple(t5.shape[1:4])}, "
                                      f"'depth' is {shape}")
             plan = _fit_plan(*shape, fit, fit_height, fit_width, window_frames)
+            pipeline.restore_plan = _restore_plan(plan, fit_restore)      # the relit clip comes back at the G-buffers' size
             for name, t5 in maps.items():
                 data_batch[key_mapping[name]] = fit_frames(t5, plan, device=getattr(pipeline, "device", "cuda"))
             keep = plan.T

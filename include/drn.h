@@ -1,7 +1,8 @@
 /* drn.h - C ABI of libdrn.so: the MI355X (gfx950) kernels behind the DiffusionRenderer
  * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer),
- * the forward renderer's per-frame environment-light projection (drn_env_project) and the
- * nodes' clip ingest with a fit to the model's grid (drn_fit_frames).
+ * the forward renderer's per-frame environment-light projection (drn_env_project), the
+ * nodes' clip ingest with a fit to the model's grid (drn_fit_frames) and its way back on the
+ * uint8 outputs (drn_restore_frames_u8).
  *
  * The reference (eggsbenedicto/DiffusionRenderer-ComfyUI) is pure Python/torch and has no FFI;
  * each entry point below names the reference code (file:line under /root/reference) whose
@@ -516,6 +517,22 @@ int drn_env_project(const float* cube, int R, const float* vec, const float* rot
 int drn_fit_frames(const float* src, void* dst_bf16, int B, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
                    const int* t_idx, const int* y_lo_n, const float* y_w, int Ky,
                    const int* x_lo_n, const float* x_w, int Kx, void* stream);
+
+/* ---- the fit's way back: the uint8 result of the post-process resampled to the source's size (no reference line: the reference
+ * has neither a fit nor its inverse; this is the inverse of drn_fit_frames for fits that kept the whole picture, and replaces a
+ * resize of fp32 frames on the host; plan and torch specification: fit.py, plan_restore / restore_frames).
+ * ONE launch: dst[b][t][y][x][ch] = uint8(clamp(rint(acc), 0, 255)),
+ *   acc = sum_ky y_w[y][ky] * (sum_kx x_w[x][kx] * src[b][t][y_lo + ky][x_lo + kx][ch]),
+ * all in fp32 on the 0..255 scale (fma accumulation from 0 in tap order, the row pass first), rint = round to nearest even.
+ *   src [B,Ts,Hs,Ws,3] and dst [B,Td,Hd,Wd,3] uint8, contiguous, at ANY byte alignment; Td <= Ts: frame t of dst comes from frame
+ *   t of src (the time padding is cut); any Hd, Wd >= 1.  Tables on the device as for drn_fit_frames: per axis lo_n int32
+ *   [n_out][2] and w fp32 [n_out][K], zero-padded past n.
+ * lo and n are clamped into the source before use; what they should hold is checked on the host (native.restore_frames).  A
+ * single tap of weight 1.0 on both axes copies.  Nothing outside dst is written, nothing outside src is read.
+ * DRN_EINVAL (nothing launched): a null pointer, a non-positive size, Td > Ts, Ky or Kx outside 1..32, B*Td*Hd*Wd*3 or
+ * B*Ts*Hs*Ws*3 >= 2^31, a table not 4-byte aligned. */
+int drn_restore_frames_u8(const uint8_t* src, uint8_t* dst, int B, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
+                          const int* y_lo_n, const float* y_w, int Ky, const int* x_lo_n, const float* x_w, int Kx, void* stream);
 
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
