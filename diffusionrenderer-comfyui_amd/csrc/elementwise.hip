@@ -781,7 +781,7 @@ extern "C" int drn_cfg_combine(const void* cond, const void* uncond, void* out, 
 
 // ------------------------------------------------------------------------------------------------
 // pipeline post-process -> uint8 (B,T,H,W,3); diffusion_renderer_pipeline.py:299-318 with every bf16 rounding kept.
-// One pixel's chain, shared by both post-process kernels: c[] = the pixel's three bf16 channel values (widened), o[] = its bytes.
+// One pixel's chain: c[] = the pixel's three bf16 channel values (widened), o[] = its bytes.
 __device__ __forceinline__ void postprocess_pixel(float (&c)[3], int normalize, uint8_t (&o)[3]) {
     if (normalize) {
         const float norm = rbf(sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
@@ -803,30 +803,6 @@ __device__ __forceinline__ void postprocess_pixel(float (&c)[3], int normalize, 
         const float u = rbf((a / 2.0f) * 255.0f);
         o[ch] = (uint8_t)u;
     }
-}
-
-__global__ __launch_bounds__(256) void postprocess_kernel(const bf16_t* __restrict__ v, uint8_t* __restrict__ o, int B,
-                                                          int64_t thw, int normalize) {
-    const int64_t total = (int64_t)B * thw;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / thw, p = i - b * thw;
-        float c[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) c[ch] = bf2f(v[(b * 3 + ch) * thw + p]);
-        uint8_t u[3];
-        postprocess_pixel(c, normalize, u);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) o[i * 3 + ch] = u[ch];
-    }
-}
-
-extern "C" int drn_postprocess_u8(const void* video, void* out_u8, int B, int T, int H, int W, int normalize_normal,
-                                  void* stream) {
-    DRN_CHECK_ARG(video && out_u8 && B > 0 && T > 0 && H > 0 && W > 0);
-    const int64_t thw = (int64_t)T * H * W;
-    postprocess_kernel<<<ew_grid((int64_t)B * thw), dim3(256), 0, (hipStream_t)stream>>>(
-        (const bf16_t*)video, (uint8_t*)out_u8, B, thw, normalize_normal);
-    return drn_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -905,16 +881,9 @@ __global__ __launch_bounds__(256) void postprocess_window_kernel(const bf16_t* _
     }
 }
 
-extern "C" int drn_postprocess_window_u8(const void* video, const void* prev_tail, const void* ramp_w, void* out_u8, int B, int Tw,
-                                         int H, int W, int O, int ramp_at, int write_lo, int write_hi, int normalize_normal,
-                                         void* stream) {
-    DRN_CHECK_ARG(video && out_u8 && B > 0 && Tw > 0 && H > 0 && W > 0);
-    DRN_CHECK_ARG((prev_tail == nullptr) == (ramp_w == nullptr));
-    DRN_CHECK_ARG(O >= 0 && ramp_at >= 0 && (int64_t)ramp_at + O <= Tw);
-    DRN_CHECK_ARG(0 <= write_lo && write_lo < write_hi && write_hi <= Tw);
-    // a ramp is written whole or not at all: the frames in front of write_lo have no other writer
-    if (prev_tail && O > 0) DRN_CHECK_ARG(write_lo <= ramp_at || write_lo >= ramp_at + O);
-    DRN_CHECK_ARG(((uintptr_t)video & 1) == 0 && ((uintptr_t)prev_tail & 1) == 0 && ((uintptr_t)ramp_w & 3) == 0);
+// The one launch of the post-process: the whole-clip entry point is a window with no carry that writes every frame.
+static int launch_postprocess(const void* video, const void* prev_tail, const void* ramp_w, void* out_u8, int B, int Tw, int H, int W,
+                              int O, int ramp_at, int write_lo, int write_hi, int normalize_normal, void* stream) {
     const int nF = write_hi - write_lo;
     const int64_t hw = (int64_t)H * W, nframes = (int64_t)B * nF;
     DRN_CHECK_ARG(nframes < (1ll << 31));
@@ -932,6 +901,25 @@ extern "C" int drn_postprocess_window_u8(const void* video, const void* prev_tai
             (const bf16_t*)video, (const bf16_t*)prev_tail, (const float*)ramp_w, (uint8_t*)out_u8, (int)nframes, nF, Tw, hw, O,
             ramp_at, write_lo, normalize_normal);
     return drn_launch_status();
+}
+
+extern "C" int drn_postprocess_window_u8(const void* video, const void* prev_tail, const void* ramp_w, void* out_u8, int B, int Tw,
+                                         int H, int W, int O, int ramp_at, int write_lo, int write_hi, int normalize_normal,
+                                         void* stream) {
+    DRN_CHECK_ARG(video && out_u8 && B > 0 && Tw > 0 && H > 0 && W > 0);
+    DRN_CHECK_ARG((prev_tail == nullptr) == (ramp_w == nullptr));
+    DRN_CHECK_ARG(O >= 0 && ramp_at >= 0 && (int64_t)ramp_at + O <= Tw);
+    DRN_CHECK_ARG(0 <= write_lo && write_lo < write_hi && write_hi <= Tw);
+    // a ramp is written whole or not at all: the frames in front of write_lo have no other writer
+    if (prev_tail && O > 0) DRN_CHECK_ARG(write_lo <= ramp_at || write_lo >= ramp_at + O);
+    DRN_CHECK_ARG(((uintptr_t)video & 1) == 0 && ((uintptr_t)prev_tail & 1) == 0 && ((uintptr_t)ramp_w & 3) == 0);
+    return launch_postprocess(video, prev_tail, ramp_w, out_u8, B, Tw, H, W, O, ramp_at, write_lo, write_hi, normalize_normal, stream);
+}
+
+extern "C" int drn_postprocess_u8(const void* video, void* out_u8, int B, int T, int H, int W, int normalize_normal,
+                                  void* stream) {
+    DRN_CHECK_ARG(video && out_u8 && B > 0 && T > 0 && H > 0 && W > 0);
+    return launch_postprocess(video, nullptr, nullptr, out_u8, B, T, H, W, 0, 0, 0, T, normalize_normal, stream);
 }
 
 extern "C" int drn_abi_version(void) { return DRN_ABI_VERSION; }

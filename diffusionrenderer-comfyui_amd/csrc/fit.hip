@@ -10,7 +10,7 @@
 // columns of one row and channel vertically out of LDS (two 16-byte LDS reads per tap) and stores them as one 16-byte group.  Every loop runs over a row's own tap count; lo and n are clamped into the source before use, so no table
 // content can take a read outside the source or the stage.  A single tap of weight 1.0 passes its source value through both
 // passes unchanged (fma(1, v, 0) == v): scale 1 is a bit-exact copy.
-#include "drn_common.h"
+#include "resample_taps.h"
 
 namespace {
 
@@ -18,18 +18,6 @@ constexpr int FIT_TW = 64;        // output columns per workgroup (8 lanes x 8 c
 constexpr int FIT_RMAX = 48;      // staged source rows: 48 x 3 x 64 fp32 = 36 KiB
 constexpr int FIT_KMAX = 32;      // taps per axis
 constexpr int FIT_THREADS = 256;
-
-struct Taps {
-    int lo, n;
-};
-
-// a row of a table, forced into [0, n_in): n in 1..K, lo in 0..n_in - n (valid tables pass unchanged; n_in >= 1)
-__device__ __forceinline__ Taps taps_of(const int* __restrict__ lo_n, int i, int K, int n_in) {
-    Taps t;
-    t.n = min(max(lo_n[2 * i + 1], 1), min(K, n_in));
-    t.lo = min(max(lo_n[2 * i], 0), n_in - t.n);
-    return t;
-}
 
 __global__ void __launch_bounds__(FIT_THREADS) fit_frames_kernel(
     const float* __restrict__ src, bf16_t* __restrict__ dst, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
@@ -154,11 +142,7 @@ extern "C" int drn_fit_frames(const float* src, void* dst_bf16, int B, int Ts, i
     DRN_CHECK_ARG((((uintptr_t)src | (uintptr_t)y_w | (uintptr_t)x_w | (uintptr_t)t_idx | (uintptr_t)y_lo_n |
                     (uintptr_t)x_lo_n) & 3) == 0);
     DRN_CHECK_ARG(((uintptr_t)dst_bf16 & 15) == 0);
-    // rows per workgroup: what a down-scale of about (Ky - 1) / 2 source rows per output row lets into the stage, 16 at most.
-    // A hint only: the kernel cuts its rows into chunks that fit, whatever the tables hold
-    const double step = Ky > 3 ? 0.5 * (Ky - 1) : 1.0;
-    int tile_h = (int)((FIT_RMAX - Ky) / step) + 1;
-    tile_h = tile_h < 1 ? 1 : (tile_h > 16 ? 16 : tile_h);
+    const int tile_h = resample_tile_rows(Ky, FIT_RMAX, 16);
     const int tiles_x = (Wd + FIT_TW - 1) / FIT_TW, tiles_y = (Hd + tile_h - 1) / tile_h;
     const int64_t blocks = (int64_t)tiles_x * tiles_y * Td * B;          // <= the output's element count / 128 < 2^31
     fit_frames_kernel<<<dim3((unsigned)blocks), dim3(FIT_THREADS), 0, (hipStream_t)stream>>>(

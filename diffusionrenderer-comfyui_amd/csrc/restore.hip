@@ -23,7 +23,7 @@
 // lo and n are clamped into the source before use (taps_of), so no table content can take a read outside src or the stage.
 // LDS is sized per launch from the tap counts and the scale (stage rows, weights, output tile): 31 KiB at 576 x 1024 ->
 // 1080 x 1920, five workgroups per CU; 51 KiB at most.
-#include "drn_common.h"
+#include "resample_taps.h"
 
 namespace {
 
@@ -36,18 +36,6 @@ constexpr int RS_RAW = 8192;          // raw source bytes per pass
 constexpr int RS_OPITCH = RS_ROW / 4 + 1;     // words per output tile row: a shifted word reads its neighbour
 constexpr int RS_THREADS = 256;
 constexpr int RS_WAVES = RS_THREADS / 64;
-
-struct Taps {
-    int lo, n;
-};
-
-// a row of a table, forced into [0, n_in): n in 1..K, lo in 0..n_in - n (valid tables pass unchanged; n_in >= 1)
-__device__ __forceinline__ Taps taps_of(const int* __restrict__ lo_n, int i, int K, int n_in) {
-    Taps t;
-    t.n = min(max(lo_n[2 * i + 1], 1), min(K, n_in));
-    t.lo = min(max(lo_n[2 * i], 0), n_in - t.n);
-    return t;
-}
 
 // one output pixel of one source row: p points at the first tap's pixel, w at the column's weights ([tap][column] in LDS)
 template <typename P>
@@ -261,12 +249,8 @@ extern "C" int drn_restore_frames_u8(const uint8_t* src, uint8_t* dst, int B, in
     const int64_t lim = (int64_t)1 << 31;
     DRN_CHECK_ARG((int64_t)B * Td * Hd * Wd * 3 < lim && (int64_t)B * Ts * Hs * Ws * 3 < lim);
     DRN_CHECK_ARG((((uintptr_t)y_w | (uintptr_t)x_w | (uintptr_t)y_lo_n | (uintptr_t)x_lo_n) & 3) == 0);
-    // rows per workgroup: what a down-scale of about (Ky - 1) / 2 source rows per output row lets into the stage, RS_TH at most;
-    // stage rows: what that many output rows read at the picture's scale, Ky at least.  Hints only: the kernel cuts its rows into
-    // chunks that fit the stage, whatever the tables hold
-    const double step = Ky > 3 ? 0.5 * (Ky - 1) : 1.0;
-    int tile_h = (int)((RS_RMAX - Ky) / step) + 1;
-    tile_h = tile_h < 1 ? 1 : (tile_h > RS_TH ? RS_TH : tile_h);
+    // stage rows: what a workgroup's output rows read at the picture's scale, Ky at least.  A hint, like the rows themselves
+    int tile_h = resample_tile_rows(Ky, RS_RMAX, RS_TH);
     tile_h = tile_h > Hd ? Hd : tile_h;
     int rmax = (int)((double)tile_h * Hs / Hd) + Ky + 2;
     rmax = rmax > RS_RMAX ? RS_RMAX : rmax;

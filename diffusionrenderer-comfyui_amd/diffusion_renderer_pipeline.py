@@ -20,7 +20,7 @@ from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
 from .fit import restore_frames
 from .model_diffusion_renderer import CleanDiffusionRendererModel
-from .windows import plan_windows, ramp_weights
+from .windows import Window, plan_windows, ramp_weights
 
 _SHAPE_KEYS = ("rgb", "image", "basecolor", "normal", "depth", "roughness", "metallic")
 
@@ -158,13 +158,7 @@ class CleanDiffusionRendererPipeline:
 
     def generate_video(self, data_batch: Dict[str, torch.Tensor], normalize_normal: bool = False, seed: int = None,
                        init_noise: torch.Tensor = None) -> np.ndarray:
-        plan = self._window_plan(data_batch)
-        if plan is not None:
-            return self._generate_windowed([data_batch], [[bool(normalize_normal)]], seed, init_noise, plan)[0][0]
-        sample = self._sample(data_batch, seed, init_noise)
-        video = self.model.decode(sample)
-        u8 = N.postprocess_u8(video.to(self.dtype).contiguous(), normalize_normal)   # fused :299-318
-        return self._restored(u8).cpu().numpy()
+        return self._render([data_batch], [[bool(normalize_normal)]], seed, init_noise, clips=True)[0][0]
 
     def generate_video_passes(self, data_batch: Dict[str, torch.Tensor], normalize_normal, seed: int = None,
                               init_noise: torch.Tensor = None):
@@ -172,18 +166,7 @@ class CleanDiffusionRendererPipeline:
         clip tensors keep batch 1, `normalize_normal` is a sequence of P flags.  Returns the P uint8 arrays generate_video
         would return for the passes run one after the other (reference nodes.py:191-213): same seed -> same start noise,
         one encode instead of P, one batched denoiser call per step."""
-        flags = list(normalize_normal)
-        plan = self._window_plan(data_batch)
-        if plan is not None:
-            return self._generate_windowed([data_batch], [[bool(f) for f in flags]], seed, init_noise, plan)[0]
-        sample = self._sample(data_batch, seed, init_noise)
-        if sample.shape[0] != len(flags):
-            raise ValueError(f"{len(flags)} normalize_normal flags for {sample.shape[0]} passes")
-        outs = []
-        for p, flag in enumerate(flags):
-            video = self.model.decode(sample[p:p + 1])
-            outs.append(self._restored(N.postprocess_u8(video.to(self.dtype).contiguous(), bool(flag))))
-        return [o.cpu().numpy() for o in outs]
+        return self._render([data_batch], [[bool(f) for f in normalize_normal]], seed, init_noise)[0]
 
     def generate_video_each(self, data_batches, normalize_normal, seed: int = None, init_noise: torch.Tensor = None):
         """generate_video for several batches over ONE clip (the inverse node's passes run one after the other), returned in
@@ -193,10 +176,7 @@ class CleanDiffusionRendererPipeline:
         flags = [bool(f) for f in normalize_normal]
         if len(flags) != len(batches):
             raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
-        plan = self._window_plan(batches[0]) if batches else None
-        if plan is None:
-            return [self.generate_video(b, f, seed, init_noise) for b, f in zip(batches, flags)]
-        return [o[0] for o in self._generate_windowed(batches, [[f] for f in flags], seed, init_noise, plan)]
+        return [o[0] for o in self._render(batches, [[f] for f in flags], seed, init_noise, clips=True)]
 
     def _restored(self, u8, frames=None):
         """The uint8 result [B, T', H', W', 3] at the source's size where a restore plan is set (fit.restore_frames, on the device),
@@ -207,7 +187,7 @@ class CleanDiffusionRendererPipeline:
         return restore_frames(u8, rplan)
 
     def _window_plan(self, data_batch):
-        """The windows of this clip, or None where today's single-sequence path applies (windows off, or a clip that fits one)."""
+        """The windows of this clip, or None where the clip is one sequence (windows off, or a clip that fits one)."""
         if not self.window_frames:
             return None
         inst = self.pre_loaded_model_instance
@@ -220,39 +200,55 @@ class CleanDiffusionRendererPipeline:
         plan = plan_windows(T, self.window_frames, self.window_overlap)     # ValueError on a bad length / overlap
         return plan if len(plan) > 1 else None
 
-    def _generate_windowed(self, batches, flags, seed, init_noise, plan):
-        """Walk the plan in order.  Per window and batch: slice every clip tensor, sample (same seed, same start noise: every window
-        has one shape), decode pass by pass, cross-fade with the carry of the previous window inside the uint8 post-process and
-        copy the written frames to the host.  The window's last `overlap` decoded frames become the next carry.  Device memory:
-        one window's decode plus one carry per pass, whatever T is.  -> per batch, per pass: uint8 [1, T, H, W, 3]."""
-        Wf, O = int(self.window_frames), int(self.window_overlap)
-        T = self._shape_tensor(batches[0]).shape[2]
-        ramp = torch.from_numpy(ramp_weights(O)).to(self._resolved(self.device)) if O else None
+    def _render(self, batches, flags, seed, init_noise, clips=False):
+        """The one walk from batches to uint8 frames on the host -> per batch, per pass: uint8 [B, T, H, W, 3].  Walk the clip's
+        windows in order.  Per window and batch: slice every clip tensor, sample (same seed, same start noise: every window has one
+        shape), decode pass by pass, cross-fade with the carry of the previous window inside the uint8 post-process, resample to
+        the source's size where a restore plan is set, and copy the written frames to the host.  The window's last `overlap`
+        decoded frames become the next carry.  Device memory: one window's decode plus one carry per pass, whatever T is.
+
+        A clip that is one sequence is one window over the caller's own tensors (the upload cache knows them by identity) that
+        writes every frame the tokenizer decoded, with no ramp and no carry.  clips: generate_video's contract for such a clip - the
+        sample's rows are clips under the one flag, decoded together - where otherwise every row is a pass with a flag of its own."""
+        if not batches:
+            return []
+        plan = self._window_plan(batches[0])
+        whole = plan is None
+        if whole:
+            plan, Wf, O, T, ramp = [Window(0, 0, 0, 0, 0)], 0, 0, 0, None       # (write_hi 0: every frame the tokenizer decodes)
+        else:
+            Wf, O = int(self.window_frames), int(self.window_overlap)
+            T = self._shape_tensor(batches[0]).shape[2]
+            ramp = torch.from_numpy(ramp_weights(O)).to(self._resolved(self.device)) if O else None
+        together = clips and whole
         outs = [[None] * len(f) for f in flags]
         carry = [[None] * len(f) for f in flags]
         for i, win in enumerate(plan):
             sliced = {}             # id(clip tensor) -> (tensor, its window): rgb / video, and the batches of one clip, share a slice
+
+            def cut(v):
+                if not (isinstance(v, torch.Tensor) and v.ndim == 5 and v.shape[2] == T):
+                    return v
+                if id(v) not in sliced:
+                    sliced[id(v)] = (v, v[:, :, win.start:win.start + Wf].contiguous())
+                return sliced[id(v)][1]
             for c, (batch, fl) in enumerate(zip(batches, flags)):
-                wb = {}
-                for k, v in batch.items():
-                    if isinstance(v, torch.Tensor) and v.ndim == 5 and v.shape[2] == T:
-                        if id(v) not in sliced:
-                            sliced[id(v)] = (v, v[:, :, win.start:win.start + Wf].contiguous())
-                        v = sliced[id(v)][1]
-                    wb[k] = v
-                sample = self._sample(wb, seed, init_noise)
-                if sample.shape[0] != len(fl):
+                sample = self._sample(batch if whole else {k: cut(v) for k, v in batch.items()}, seed, init_noise)
+                if not together and sample.shape[0] != len(fl):
                     raise ValueError(f"{len(fl)} normalize_normal flags for {sample.shape[0]} passes")
                 for p, flag in enumerate(fl):
-                    video = self.model.decode(sample[p:p + 1]).to(self.dtype).contiguous()
-                    if video.shape[2] != Wf:
+                    video = self.model.decode(sample if together else sample[p:p + 1]).to(self.dtype).contiguous()
+                    if not whole and video.shape[2] != Wf:
                         raise ValueError(f"the tokenizer decoded {video.shape[2]} frames for a window of {Wf}")
-                    prev = carry[c][p] if i > 0 and O else None
+                    prev = carry[c][p]                                                # None: window 0, or hard cuts
                     u8 = N.postprocess_window_u8(video, prev, ramp if prev is not None else None, win.ramp_at, win.write_lo,
-                                                 win.write_hi, flag)
-                    u8 = self._restored(u8, frames=u8.shape[1])       # frames are independent: window by window = the whole clip
+                                                 win.write_hi or video.shape[2], flag)
+                    # frames are independent: window by window = the whole clip.  Kept: those written, up to the restore plan's T
+                    # (the time padding of a whole clip is cut; a windowed clip has none)
+                    if self.restore_plan is not None:
+                        u8 = self._restored(u8, frames=min(u8.shape[1], self.restore_plan.T - win.out_at))
                     if outs[c][p] is None:
-                        outs[c][p] = torch.empty((1, T) + tuple(u8.shape[2:]), dtype=torch.uint8)
+                        outs[c][p] = torch.empty((u8.shape[0], u8.shape[1] if whole else T) + tuple(u8.shape[2:]), dtype=torch.uint8)
                     outs[c][p][:, win.out_at:win.out_at + u8.shape[1]].copy_(u8)      # D2H straight into the clip's frames
                     carry[c][p] = video[:, :, Wf - O:].contiguous() if O and i + 1 < len(plan) else None
         return [[o.numpy() for o in per_batch] for per_batch in outs]

@@ -80,6 +80,11 @@ def axis_taps(n_in: int, n_full: int, off: int, n_out: int):
     return lo_n, out
 
 
+def _single(lo_n, w, n_in) -> bool:
+    """An axis table that copies its n_in samples: one tap of weight 1.0 per output sample, in place."""
+    return w.shape[1] == 1 and len(lo_n) == n_in and bool((lo_n[:, 0] == np.arange(n_in)).all()) and bool((w == 1.0).all())
+
+
 def _target(side: int, given: int, name: str) -> int:
     if given:
         if given < 0 or given % GRID:
@@ -114,10 +119,7 @@ def plan_fit(T: int, H: int, W: int, mode: str, height: int = 0, width: int = 0,
             raise ValueError(f"the {name} down-scale needs {w.shape[1]} taps per output sample; at most {MAX_TAPS} are supported")
     T_out = T if (T - 1) % 8 == 0 or windowed else (T - 1) // 8 * 8 + 9
     t_idx = np.minimum(np.arange(T_out), T - 1).astype(np.int32)
-
-    def single(lo_n, w, n_in):
-        return w.shape[1] == 1 and len(lo_n) == n_in and bool((lo_n[:, 0] == np.arange(n_in)).all()) and bool((w == 1.0).all())
-    identity = T_out == T and single(y_lo_n, y_w, H) and single(x_lo_n, x_w, W)
+    identity = T_out == T and _single(y_lo_n, y_w, H) and _single(x_lo_n, x_w, W)
     return FitPlan(mode, T, H, W, T_out, H_out, W_out, H_full, W_full, y0, x0, torch.from_numpy(t_idx),
                    torch.from_numpy(y_lo_n), torch.from_numpy(y_w.astype(np.float32)),
                    torch.from_numpy(x_lo_n), torch.from_numpy(x_w.astype(np.float32)), identity)
@@ -150,10 +152,7 @@ def plan_restore(plan: FitPlan) -> RestorePlan:
     for name, w in (("height", y_w), ("width", x_w)):
         if w.shape[1] > MAX_TAPS:
             raise ValueError(f"restoring the {name} needs {w.shape[1]} taps per output sample; at most {MAX_TAPS} are supported")
-
-    def single(lo_n, w, n_in):
-        return w.shape[1] == 1 and len(lo_n) == n_in and bool((lo_n[:, 0] == np.arange(n_in)).all()) and bool((w == 1.0).all())
-    identity = single(y_lo_n, y_w, plan.H_out) and single(x_lo_n, x_w, plan.W_out)
+    identity = _single(y_lo_n, y_w, plan.H_out) and _single(x_lo_n, x_w, plan.W_out)
     return RestorePlan(plan.T, plan.H_out, plan.W_out, plan.H, plan.W,
                        torch.from_numpy(y_lo_n), torch.from_numpy(y_w.astype(np.float32)),
                        torch.from_numpy(x_lo_n), torch.from_numpy(x_w.astype(np.float32)), identity)

@@ -857,6 +857,15 @@ def env_project(cube, vec, rot, log_scale=10000.0, out=None):
     return out
 
 
+def _check_tap_table(lo_n, w, n_in):
+    """One axis of a resampling plan as HOST tensors: lo_n int32 [n_out, 2], w fp32 [n_out, K <= 32], every row inside [0, n_in)."""
+    assert lo_n.dtype == torch.int32 and w.dtype == torch.float32 and lo_n.ndim == 2 and w.ndim == 2
+    assert lo_n.shape == (w.shape[0], 2) and 1 <= w.shape[1] <= 32, "tap table shapes"
+    lo, n = lo_n[:, 0].long(), lo_n[:, 1].long()
+    assert bool((lo >= 0).all()) and bool((n >= 1).all()) and bool((n <= w.shape[1]).all()) and bool((lo + n <= n_in).all()), \
+        "taps outside the source"
+
+
 def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
     """Clip ingest with a fit to the model's grid (drn_fit_frames; the plan: fit.plan_fit).  src [B, Ts, Hs, Ws, 3] fp32 on the
     device, contiguous; the plan's tables as HOST tensors (t_idx int32 [Td], per axis lo_n int32 [n_out, 2] and w fp32 [n_out, K]):
@@ -866,12 +875,8 @@ def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
         "contiguous fp32 [B, T, H, W, 3] frames required"
     B, Ts, Hs, Ws, _ = src.shape
     assert t_idx.dtype == torch.int32 and t_idx.ndim == 1 and 0 <= int(t_idx.min()) and int(t_idx.max()) < Ts, "t_idx outside the clip"
-    for lo_n, w, n_in in ((y_lo_n, y_w, Hs), (x_lo_n, x_w, Ws)):
-        assert lo_n.dtype == torch.int32 and w.dtype == torch.float32 and lo_n.ndim == 2 and w.ndim == 2
-        assert lo_n.shape == (w.shape[0], 2) and 1 <= w.shape[1] <= 32, "tap table shapes"
-        lo, n = lo_n[:, 0].long(), lo_n[:, 1].long()
-        assert bool((lo >= 0).all()) and bool((n >= 1).all()) and bool((n <= w.shape[1]).all()) and bool((lo + n <= n_in).all()), \
-            "taps outside the source"
+    _check_tap_table(y_lo_n, y_w, Hs)
+    _check_tap_table(x_lo_n, x_w, Ws)
     Td, Hd, Wd = t_idx.shape[0], y_lo_n.shape[0], x_lo_n.shape[0]
     if out is None:
         out = torch.empty((B, 3, Td, Hd, Wd), dtype=torch.bfloat16, device=src.device)
@@ -891,12 +896,8 @@ def restore_frames(src, T, y_lo_n, y_w, x_lo_n, x_w, out=None):
         "contiguous uint8 [B, T, H, W, 3] frames required"
     B, Ts, Hs, Ws, _ = src.shape
     assert 1 <= T <= Ts, "frames to return outside the clip"
-    for lo_n, w, n_in in ((y_lo_n, y_w, Hs), (x_lo_n, x_w, Ws)):
-        assert lo_n.dtype == torch.int32 and w.dtype == torch.float32 and lo_n.ndim == 2 and w.ndim == 2
-        assert lo_n.shape == (w.shape[0], 2) and 1 <= w.shape[1] <= 32, "tap table shapes"
-        lo, n = lo_n[:, 0].long(), lo_n[:, 1].long()
-        assert bool((lo >= 0).all()) and bool((n >= 1).all()) and bool((n <= w.shape[1]).all()) and bool((lo + n <= n_in).all()), \
-            "taps outside the source"
+    _check_tap_table(y_lo_n, y_w, Hs)
+    _check_tap_table(x_lo_n, x_w, Ws)
     Hd, Wd = y_lo_n.shape[0], x_lo_n.shape[0]
     if out is None:
         out = torch.empty((B, T, Hd, Wd, 3), dtype=torch.uint8, device=src.device)

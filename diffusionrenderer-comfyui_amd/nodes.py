@@ -58,19 +58,6 @@ def _fit_inputs():
                                                    "Normal maps are resampled like any picture and not renormalised"})}
 
 
-def _fit_plan(T, H, W, fit, fit_height, fit_width, window_frames):
-    from .fit import plan_fit
-    return plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames)
-
-
-def _restore_plan(plan, fit_restore):
-    """What the pipeline's `restore_plan` is for this call: the way back of the fit's plan, or None (ValueError: a crop that cut)."""
-    if not fit_restore:
-        return None
-    from .fit import plan_restore
-    return plan_restore(plan)
-
-
 def standardize_to_5d(image, name="image") -> torch.Tensor:
     """list / (H,W,C) / (B,H,W,C)->T=1 / (B,T,H,W,C) -> (B,T,H,W,C)   (reference nodes.py:156-177, :258-268)."""
     if isinstance(image, list):
@@ -87,6 +74,37 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
             return image
         raise ValueError(f"Unsupported tensor dimension for '{name}': {image.ndim}. Expected 3D, 4D, or 5D.")
     raise TypeError(f"Unsupported input type for '{name}': {type(image)}. Expected torch.Tensor or list of Tensors.")
+
+
+def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap):
+    """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared."""
+    pipeline.set_model_type(model_type)
+    pipeline.guidance = guidance
+    pipeline.seed = seed
+    pipeline.window_frames = window_frames
+    pipeline.window_overlap = window_overlap
+    pipeline.restore_plan = None
+
+
+def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_frames):
+    """{name: frames in [0, 1]} -> ({name: (B,C,T,H,W) in [-1, 1]}, the fit's plan).  fit off: no plan, the clips must be on the
+    model's grid.  Otherwise all clips go through ONE plan (fit.py: resize / crop / pad in time, * 2 - 1, bf16 and the transpose in
+    one launch on the pipeline's device), so they must be one size; with fit_restore the pipeline is handed the way back
+    (ValueError for a crop that cut, before anything runs)."""
+    clips = {name: standardize_to_5d(t, name) for name, t in clips.items()}
+    if fit == "off":
+        return {name: t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0 for name, t5 in clips.items()}, None
+    from .fit import fit_frames, plan_fit, plan_restore
+    first, shape = next((name, tuple(t5.shape[1:4])) for name, t5 in clips.items())
+    for name, t5 in clips.items():
+        if tuple(t5.shape[1:4]) != shape:
+            raise ValueError(f"fit needs G-buffers of one size: '{name}' is (T, H, W) = {tuple(t5.shape[1:4])}, "
+                             f"'{first}' is {shape}")
+    plan = plan_fit(*shape, fit, fit_height, fit_width, windowed=window_frames > 0 and shape[0] > window_frames)
+    if fit_restore:
+        pipeline.restore_plan = plan_restore(plan)      # the outputs come back at the source's size
+    device = getattr(pipeline, "device", "cuda")
+    return {name: fit_frames(t5, plan, device=device) for name, t5 in clips.items()}, plan
 
 
 class LoadDiffusionRendererModel:
@@ -155,31 +173,11 @@ class Cosmos1InverseRenderer:
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False):
-        pipeline.set_model_type("inverse")
-        pipeline.guidance = guidance
-        pipeline.seed = seed
-        pipeline.window_frames = window_frames
-        pipeline.window_overlap = window_overlap
-        pipeline.restore_plan = None
-        image_5d = standardize_to_5d(image)
-        if fit == "off":
-            image_tensor = image_5d.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
-            keep = None
-        else:
-            # resize / crop / pad in time, * 2 - 1, bf16 and the transpose in one launch on the pipeline's device (fit.py)
-            from .fit import fit_frames
-            plan = _fit_plan(*image_5d.shape[1:4], fit, fit_height, fit_width, window_frames)
-            pipeline.restore_plan = _restore_plan(plan, fit_restore)      # the outputs come back at the source's size
-            image_tensor = fit_frames(image_5d, plan, device=getattr(pipeline, "device", "cuda"))
-            keep = plan.T
-        outputs = {}
-        pbar = _progress_bar(len(INVERSE_PASSES))
-
-        def to_image(out):
-            t = torch.from_numpy(out[:, :keep]).float() / 255.0           # a clip padded in time comes back at its own length
-            b, tt, h, w, c = t.shape
-            return t.reshape(b * tt, h, w, c)
-
+        _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap)
+        clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
+        image_tensor = clips["image"]
+        keep = plan.T if plan is not None else None
+        normalize = [p == "normal" for p in INVERSE_PASSES]
         if image_tensor.shape[0] == 1 and getattr(pipeline, "batch_passes", True) and hasattr(pipeline, "generate_video_passes"):
             # the five passes share the clip, the seed and every weight: step them as one batch
             data_batch = {
@@ -187,28 +185,25 @@ class Cosmos1InverseRenderer:
                 "video": image_tensor,
                 "context_index": torch.tensor([[GBUFFER_INDEX_MAPPING[p]] for p in INVERSE_PASSES], dtype=torch.long),
             }
-            outs = pipeline.generate_video_passes(data_batch=data_batch, seed=seed,
-                                                  normalize_normal=[p == "normal" for p in INVERSE_PASSES])
-            for gbuffer_pass, out in zip(INVERSE_PASSES, outs):
-                outputs[gbuffer_pass] = to_image(out)
-                pbar.update(1)
-            return (outputs["basecolor"], outputs["metallic"], outputs["roughness"], outputs["normal"], outputs["depth"])
-        batches = [{"rgb": image_tensor,
-                    "video": image_tensor,
-                    "context_index": torch.full((image_tensor.shape[0], 1), GBUFFER_INDEX_MAPPING[p], dtype=torch.long)}
-                   for p in INVERSE_PASSES]
-        if window_frames and hasattr(pipeline, "generate_video_each"):
-            # windows outside, passes inside: every window of the clip is uploaded and encoded once, not once per pass
-            outs = pipeline.generate_video_each(batches, [p == "normal" for p in INVERSE_PASSES], seed=seed)
-            for gbuffer_pass, out in zip(INVERSE_PASSES, outs):
-                outputs[gbuffer_pass] = to_image(out)
-                pbar.update(1)
-            return (outputs["basecolor"], outputs["metallic"], outputs["roughness"], outputs["normal"], outputs["depth"])
-        for gbuffer_pass, data_batch in zip(INVERSE_PASSES, batches):
-            out = pipeline.generate_video(data_batch=data_batch, normalize_normal=(gbuffer_pass == "normal"), seed=seed)
-            outputs[gbuffer_pass] = to_image(out)
+            outs = pipeline.generate_video_passes(data_batch=data_batch, seed=seed, normalize_normal=normalize)
+        else:
+            batches = [{"rgb": image_tensor,
+                        "video": image_tensor,
+                        "context_index": torch.full((image_tensor.shape[0], 1), GBUFFER_INDEX_MAPPING[p], dtype=torch.long)}
+                       for p in INVERSE_PASSES]
+            if window_frames and hasattr(pipeline, "generate_video_each"):
+                # windows outside, passes inside: every window of the clip is uploaded and encoded once, not once per pass
+                outs = pipeline.generate_video_each(batches, normalize, seed=seed)
+            else:       # pass by pass, each rendered as the loop below asks for it: the progress bar moves per pass
+                outs = (pipeline.generate_video(data_batch=b, normalize_normal=f, seed=seed) for b, f in zip(batches, normalize))
+        images = []
+        pbar = _progress_bar(len(INVERSE_PASSES))
+        for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
+            t = torch.from_numpy(out[:, :keep]).float() / 255.0               # a clip padded in time comes back at its own length
+            b, tt, h, w, c = t.shape
+            images.append(t.reshape(b * tt, h, w, c))
             pbar.update(1)
-        return (outputs["basecolor"], outputs["metallic"], outputs["roughness"], outputs["normal"], outputs["depth"])
+        return tuple(images)
 
 
 class Cosmos1ForwardRenderer:
@@ -235,34 +230,15 @@ class Cosmos1ForwardRenderer:
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
                          fit_restore=False):
-        pipeline.set_model_type("forward")
-        pipeline.guidance = guidance
-        pipeline.seed = seed
-        pipeline.window_frames = window_frames
-        pipeline.window_overlap = window_overlap
-        pipeline.restore_plan = None
+        _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap)
         key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                        "metallic": "metallic"}
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
-        data_batch = {}
+        # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
+        clips, plan = _ingest(pipeline, inputs, fit, fit_height, fit_width, fit_restore, window_frames)
+        data_batch = {key_mapping[name]: t for name, t in clips.items()}
         keep = None
-        if fit == "off":
-            for name, t in inputs.items():
-                t5 = standardize_to_5d(t, name)
-                data_batch[key_mapping[name]] = t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
-        else:
-            # all five G-buffers through ONE plan (fit.py): they must be the same clip geometry
-            from .fit import fit_frames
-            maps = {name: standardize_to_5d(t, name) for name, t in inputs.items()}
-            shape = tuple(maps["depth"].shape[1:4])
-            for name, t5 in maps.items():
-                if tuple(t5.shape[1:4]) != shape:
-                    raise ValueError(f"fit needs G-buffers of one size: '{name}' is (T, H, W) = {tuple(t5.shape[1:4])}, "
-                                     f"'depth' is {shape}")
-            plan = _fit_plan(*shape, fit, fit_height, fit_width, window_frames)
-            pipeline.restore_plan = _restore_plan(plan, fit_restore)      # the relit clip comes back at the G-buffers' size
-            for name, t5 in maps.items():
-                data_batch[key_mapping[name]] = fit_frames(t5, plan, device=getattr(pipeline, "device", "cuda"))
+        if plan is not None:
             keep = plan.T
             # frame t keeps the angle radians(env_spin) * t / T of the clip as handed in; padded frames turn on and are cut away
             env_spin = env_spin * plan.T_out / plan.T

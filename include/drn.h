@@ -470,14 +470,16 @@ int drn_edm_step(const void* model_out, const void* sample, void* out, int64_t n
 int drn_cfg_combine(const void* cond, const void* uncond, void* out, int64_t n, float guidance, void* stream);
 
 /* ---- pipeline post-process (diffusion_renderer_pipeline.py:299-318): optional normal re-normalisation blend,
- * (1+v).clamp(0,2)/2, permute to (B,T,H,W,C), *255, truncating uint8 cast.  video: [B,3,T,H,W] bf16. Bit-exact. */
+ * (1+v).clamp(0,2)/2, permute to (B,T,H,W,C), *255, truncating uint8 cast.  video: [B,3,T,H,W] bf16. Bit-exact.
+ * One kernel serves this entry point and the next: this is drn_postprocess_window_u8 with no carry (prev_tail = ramp_w = NULL,
+ * O = 0, ramp_at = 0) writing frames [0, T), and takes its 8-pixels-per-lane or one-pixel-per-lane form by the same rule. */
 int drn_postprocess_u8(const void* video, void* out_u8, int B, int T, int H, int W, int normalize_normal, void* stream);
 
-/* ---- the same post-process for one WINDOW of a long clip (windows.py): frames [write_lo, write_hi) of the decoded window are
+/* ---- the post-process for one WINDOW of a long clip (windows.py): frames [write_lo, write_hi) of the decoded window are
  * written, and the O ramp frames [ramp_at, ramp_at + O) are first cross-faded with the previous window's last O decoded frames:
  *   v = bf16(a + w[f - ramp_at] * (b - a)),  a = prev_tail at frame f - ramp_at, b = the window's value, both widened to fp32;
  * subtract, multiply and add are three separately rounded fp32 operations (no FMA).  Every other frame keeps the window's own
- * bf16 value.  v then takes exactly the chain of drn_postprocess_u8.  Bit-exact.
+ * bf16 value.  v then takes exactly the chain above.  Bit-exact.
  *   video [B,3,Tw,H,W] bf16 (B passes of one window); prev_tail [B,3,O,H,W] bf16 or NULL (no ramp); ramp_w [O] fp32 on the device,
  *   NULL iff prev_tail is NULL; out_u8 [B, write_hi - write_lo, H, W, 3].  All contiguous.
  * H * W % 8 == 0 with 16-byte aligned inputs and an 8-byte aligned output runs 8 pixels per lane (16-byte loads, 24 contiguous

@@ -1,4 +1,5 @@
 """Drop-in boundary surface: node mappings, INPUT/RETURN types, tensor conventions, errors.  CPU only."""
+import numpy as np
 import pytest
 import torch
 
@@ -99,3 +100,62 @@ def test_state_dict_names_equal_reference_manifest(pkg):
         assert mine == man[kind], kind
     assert man["inverse"]["net.x_embedder.proj.1.weight"] == [4096, 132]
     assert man["forward"]["net.x_embedder.proj.1.weight"] == [4096, 612]
+
+
+class _RoutingRecorder:
+    """Stands where the pipeline stands and implements all three entry points: records which were called and answers each pass
+    with frames of its own grey level (the G-buffer index of the pass)."""
+    device = "cpu"
+    batch_passes = True
+    restore_plan = None
+
+    def __init__(self):
+        self.calls = []
+
+    def set_model_type(self, t):
+        self.model_type = t
+
+    @staticmethod
+    def _frames(data_batch, index):
+        B, _, T, H, W = data_batch["video"].shape
+        return np.full((B, T, H, W, 3), int(index), dtype=np.uint8)
+
+    def generate_video(self, data_batch, normalize_normal=False, seed=None):
+        self.calls.append(("video", bool(normalize_normal)))
+        assert data_batch["context_index"].shape == (data_batch["video"].shape[0], 1)
+        return self._frames(data_batch, data_batch["context_index"][0, 0])
+
+    def generate_video_passes(self, data_batch, normalize_normal, seed=None):
+        self.calls.append(("passes", [bool(f) for f in normalize_normal]))
+        return [self._frames(data_batch, i) for i in data_batch["context_index"][:, 0]]
+
+    def generate_video_each(self, data_batches, normalize_normal, seed=None):
+        self.calls.append(("each", [bool(f) for f in normalize_normal]))
+        return [self._frames(b, b["context_index"][0, 0]) for b in data_batches]
+
+
+def test_inverse_node_calls_one_pipeline_entry_point_per_run(pkg):
+    from diffusionrenderer_comfyui_amd.nodes import GBUFFER_INDEX_MAPPING
+    node_cls = pkg.NODE_CLASS_MAPPINGS["Cosmos1InverseRenderer"]
+    node = node_cls()
+    flags = [False, False, False, True, False]                                  # the normal pass alone is renormalised
+    want = [GBUFFER_INDEX_MAPPING[n] for n in ("basecolor", "metallic", "roughness", "normal", "depth")]
+    assert node_cls.RETURN_NAMES == ("base_color", "metallic", "roughness", "normal", "depth")
+
+    def run(p, B=1, **kw):
+        outs = node.run_inverse_pass(p, torch.rand(B, 9, 16, 16, 3), **kw)
+        assert len(outs) == 5
+        for o, index in zip(outs, want):                                        # RETURN_NAMES order, whichever call made them
+            assert o.shape == (B * 9, 16, 16, 3) and o.dtype == torch.float32 and bool((o == index / 255.0).all())
+        return p.calls
+
+    assert run(_RoutingRecorder()) == [("passes", flags)]                       # B = 1: the five passes as one batch
+    assert run(_RoutingRecorder(), window_frames=9) == [("passes", flags)]
+    p = _RoutingRecorder()
+    p.batch_passes = False
+    assert run(p, window_frames=9) == [("each", flags)]                         # windowed, pass by pass: windows outside
+    p = _RoutingRecorder()
+    p.batch_passes = False
+    assert run(p) == [("video", f) for f in flags]                              # otherwise generate_video, five times
+    assert run(_RoutingRecorder(), B=2) == [("video", f) for f in flags]        # a batch of clips is not stepped as passes
+    assert run(_RoutingRecorder(), B=2, window_frames=9) == [("each", flags)]

@@ -2,6 +2,7 @@
 tests/test_windows_cpu.py shows to separate the wrong kernels), its argument checks, and the windowed pipeline and nodes
 against the composition done by hand."""
 import ctypes
+import importlib
 
 import numpy as np
 import pytest
@@ -83,11 +84,14 @@ def test_window_kernel_unaligned_buffers_take_the_pixel_path(pkg, gpu):
 
 @pytest.mark.parametrize("normalize", [False, True])
 def test_window_kernel_without_a_ramp_is_postprocess_u8(pkg, gpu, normalize):
+    """drn_postprocess_u8 is the window kernel with no carry over every frame: both against the CPU reference of the chain."""
     for (H, W) in ((8, 12), (5, 7), (64, 64)):
-        video = pkg.synthetic_weights.synth_tensor(f"win.id.{H}", (2, 3, R.TW, H, W), torch.float32, scale=0.8).to(BF).to(gpu)
-        old = pkg.native.postprocess_u8(video, normalize)
-        assert torch.equal(pkg.native.postprocess_window_u8(video, None, None, 0, 0, R.TW, normalize), old)
-        assert torch.equal(pkg.native.postprocess_window_u8(video, None, None, 3, 2, 7, normalize), old[:, 2:7])
+        cpu = pkg.synthetic_weights.synth_tensor(f"win.id.{H}", (2, 3, R.TW, H, W), torch.float32, scale=0.8).to(BF)
+        video = cpu.to(gpu)
+        ref = O.postprocess(cpu, normalize)
+        assert torch.equal(pkg.native.postprocess_u8(video, normalize).cpu(), ref)
+        assert torch.equal(pkg.native.postprocess_window_u8(video, None, None, 0, 0, R.TW, normalize).cpu(), ref)
+        assert torch.equal(pkg.native.postprocess_window_u8(video, None, None, 3, 2, 7, normalize).cpu(), ref[:, 2:7])
 
 
 def test_window_kernel_argument_checks(pkg, gpu):
@@ -230,6 +234,53 @@ def test_windowed_passes_match_the_passes_run_singly(pkg, gpu):
     assert all(np.array_equal(a, b) for a, b in zip(each, singles))
     with pytest.raises(ValueError, match="normalize_normal flags"):
         p.generate_video_passes({"rgb": rgb, "video": rgb, "context_index": idx}, normalize_normal=[False])
+
+
+def test_generate_video_of_a_batch_of_clips(pkg, gpu, monkeypatch):
+    """Windows off, a sample of two different clips: one decode, one flag, one host buffer of B = 2, byte for byte the chain by hand.
+    The renderer model itself samples one clip per call (its noise is drawn with batch 1, as in the reference), so the two-clip
+    sample is the two clips' samples stacked and stands in for _sample; everything after it is the pipeline's own walk."""
+    sw = pkg.synthetic_weights
+    p = _pipeline(pkg, gpu, StubVAE())
+    rgb = sw.synth_tensor("winb.rgb", (2, 3, 9, 64, 64), torch.float32, scale=1.0)
+    batch = {"rgb": rgb, "video": rgb, "context_index": torch.full((2, 1), 3, dtype=torch.long)}
+    with pytest.raises(ValueError, match="one clip per call"):
+        p.generate_video(batch, seed=7)
+    rows = []
+    for k in range(2):
+        clip = rgb[k:k + 1].contiguous()
+        rows.append(p._sample({"rgb": clip, "video": clip, "context_index": batch["context_index"][k:k + 1]}, 7, None))
+    sample = torch.cat(rows)
+    monkeypatch.setattr(p, "_sample", lambda *a, **k: sample)
+    video = p.model.decode(p._sample(batch, 7, None)).to(BF).cpu()
+    for normalize in (False, True):
+        got = p.generate_video(batch, normalize_normal=normalize, seed=7)
+        ref = O.postprocess(video, normalize).numpy()
+        assert got.shape == (2, 9, 64, 64, 3) and got.dtype == np.uint8
+        assert np.array_equal(got, ref), f"normalize={normalize}: {(got != ref).sum()} bytes differ"
+    assert not np.array_equal(got[0], got[1])
+
+
+def test_restore_through_one_window(pkg, gpu):
+    """A clip padded in time by the fit (12 -> 17 frames) with a restore plan: the whole-clip window restores what it wrote and
+    keeps the plan's 12 frames, with windows off and with one window of 17."""
+    fit = importlib.import_module(pkg.__name__ + ".fit")
+    p = _pipeline(pkg, gpu, _RaggedStubVAE())
+    image = pkg.synthetic_weights.synth_tensor("winr.img", (1, 12, 40, 36, 3), torch.float32).abs().clamp(max=1.0)
+    plan = fit.plan_fit(12, 40, 36, "stretch", 32, 32)
+    clip = fit.fit_frames(image, plan, device=gpu)
+    assert clip.shape == (1, 3, 17, 32, 32)
+    batch = {"rgb": clip, "video": clip, "context_index": torch.full((1, 1), 3, dtype=torch.long)}
+    p.restore_plan = fit.plan_restore(plan)
+    sample = p._sample(batch, 5, None)
+    u8 = pkg.native.postprocess_u8(p.model.decode(sample).to(BF).contiguous(), True)
+    ref = fit.restore_frames(u8, p.restore_plan).cpu().numpy()
+    assert u8.shape == (1, 17, 32, 32, 3) and ref.shape == (1, 12, 40, 36, 3)
+    off = p.generate_video(batch, normalize_normal=True, seed=5)
+    assert np.array_equal(off, ref), f"{(off != ref).sum()} bytes differ"
+    p.window_frames = 17
+    assert len(pkg.windows.plan_windows(17, p.window_frames, p.window_overlap)) == 1
+    assert np.array_equal(p.generate_video(batch, normalize_normal=True, seed=5), ref)
 
 
 # ----------------------------------------------------------------------------------------------- nodes

@@ -10,7 +10,7 @@ Kernel legs (device events, median of `--reps` runs after a warm-up, variants al
        drn_postprocess_u8 over the window
   (b)  drn_postprocess_window_u8 on the same window - once writing all 57 frames (the last window of a clip: the same frames as
        (a)), once writing 49 (a middle window, whose last 8 frames are the carry and are not written)
-  (c)  drn_postprocess_window_u8 without a ramp against drn_postprocess_u8, all 57 frames
+  (c)  drn_postprocess_window_u8 without a ramp, all 57 frames: what drn_postprocess_u8 launches (one kernel serves both)
 Pipeline leg (host clock around calls that end in the D2H copy): one windowed generate_video of the clip against the windows of
 its plan cut from the clip and run as separate generate_video calls (windows off; the cuts are inside the timed region on both
 sides) - the full 28-block network with synthetic weights, the HIP tokenizer, `--steps` Euler steps.  The separate calls produce
@@ -77,14 +77,11 @@ def kernel_legs(H, W, Wf, Ov, reps):
         "(b) drn_postprocess_window_u8, ramp, 57 frames written": lambda: N.postprocess_window_u8(video, prev, w, 0, 0, Wf, True, out=out_full),
         "(b) drn_postprocess_window_u8, ramp, 49 frames written": lambda: N.postprocess_window_u8(video, prev, w, 0, 0, Wf - Ov, True, out=out_mid),
         "(c) drn_postprocess_window_u8, no ramp, 57 frames": lambda: N.postprocess_window_u8(video, None, None, 0, 0, Wf, True, out=out_full),
-        "    drn_postprocess_u8, 57 frames": lambda: N.postprocess_u8(video, True),
         "(c) drn_postprocess_window_u8, no ramp, no normal blend": lambda: N.postprocess_window_u8(video, None, None, 0, 0, Wf, False, out=out_full),
-        "    drn_postprocess_u8, no normal blend": lambda: N.postprocess_u8(video, False),
     }
     # same bytes first: faster and different is not faster
     ref = torch_lerp_then_old()
     assert torch.equal(N.postprocess_window_u8(video, prev, w, 0, 0, Wf, True), ref)
-    assert torch.equal(N.postprocess_window_u8(video, None, None, 0, 0, Wf, True), N.postprocess_u8(video, True))
     del ref
     px = Wf * H * W
     say(f"kernel legs: window [1,3,{Wf},{H},{W}] bf16 ({px * 6 / 2**20:.0f} MiB in, {px * 3 / 2**20:.0f} MiB out), carry {Ov} frames, "
