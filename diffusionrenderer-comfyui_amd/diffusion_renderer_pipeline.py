@@ -157,18 +157,21 @@ class CleanDiffusionRendererPipeline:
         return model
 
     def generate_video(self, data_batch: Dict[str, torch.Tensor], normalize_normal: bool = False, seed: int = None,
-                       init_noise: torch.Tensor = None) -> np.ndarray:
-        return self._render([data_batch], [[bool(normalize_normal)]], seed, init_noise, clips=True)[0][0]
+                       init_noise: torch.Tensor = None, to_host: bool = True) -> np.ndarray:
+        """to_host=False (here and in the two methods below): the result stays on the pipeline's device, a torch.uint8 tensor
+        [B, T, H, W, 3] with the bytes of the array the default call returns."""
+        return self._render([data_batch], [[bool(normalize_normal)]], seed, init_noise, clips=True, to_host=to_host)[0][0]
 
     def generate_video_passes(self, data_batch: Dict[str, torch.Tensor], normalize_normal, seed: int = None,
-                              init_noise: torch.Tensor = None):
+                              init_noise: torch.Tensor = None, to_host: bool = True):
         """P G-buffer passes of ONE clip stepped together: `data_batch["context_index"]` is [P, 1], the
         clip tensors keep batch 1, `normalize_normal` is a sequence of P flags.  Returns the P uint8 arrays generate_video
         would return for the passes run one after the other (reference nodes.py:191-213): same seed -> same start noise,
         one encode instead of P, one batched denoiser call per step."""
-        return self._render([data_batch], [[bool(f) for f in normalize_normal]], seed, init_noise)[0]
+        return self._render([data_batch], [[bool(f) for f in normalize_normal]], seed, init_noise, to_host=to_host)[0]
 
-    def generate_video_each(self, data_batches, normalize_normal, seed: int = None, init_noise: torch.Tensor = None):
+    def generate_video_each(self, data_batches, normalize_normal, seed: int = None, init_noise: torch.Tensor = None,
+                            to_host: bool = True):
         """generate_video for several batches over ONE clip (the inverse node's passes run one after the other), returned in
         order.  With windows the loop is windows outside, batches inside: the batches share the clip tensor, so they share each
         window's slice of it, and the upload and encode caches still see one clip per window instead of one per window and pass."""
@@ -176,7 +179,7 @@ class CleanDiffusionRendererPipeline:
         flags = [bool(f) for f in normalize_normal]
         if len(flags) != len(batches):
             raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
-        return [o[0] for o in self._render(batches, [[f] for f in flags], seed, init_noise, clips=True)]
+        return [o[0] for o in self._render(batches, [[f] for f in flags], seed, init_noise, clips=True, to_host=to_host)]
 
     def _restored(self, u8, frames=None):
         """The uint8 result [B, T', H', W', 3] at the source's size where a restore plan is set (fit.restore_frames, on the device),
@@ -200,8 +203,10 @@ class CleanDiffusionRendererPipeline:
         plan = plan_windows(T, self.window_frames, self.window_overlap)     # ValueError on a bad length / overlap
         return plan if len(plan) > 1 else None
 
-    def _render(self, batches, flags, seed, init_noise, clips=False):
-        """The one walk from batches to uint8 frames on the host -> per batch, per pass: uint8 [B, T, H, W, 3].  Walk the clip's
+    def _render(self, batches, flags, seed, init_noise, clips=False, to_host=True):
+        """The one walk from batches to uint8 frames -> per batch, per pass: uint8 [B, T, H, W, 3], numpy arrays on the host, or
+        with to_host=False torch tensors on the pipeline's device (the same walk: only the buffer the written frames are copied
+        into lives there, so what the inverse renderer made can feed the forward renderer without a host round trip).  Walk the clip's
         windows in order.  Per window and batch: slice every clip tensor, sample (same seed, same start noise: every window has one
         shape), decode pass by pass, cross-fade with the carry of the previous window inside the uint8 post-process, resample to
         the source's size where a restore plan is set, and copy the written frames to the host.  The window's last `overlap`
@@ -248,10 +253,11 @@ class CleanDiffusionRendererPipeline:
                     if self.restore_plan is not None:
                         u8 = self._restored(u8, frames=min(u8.shape[1], self.restore_plan.T - win.out_at))
                     if outs[c][p] is None:
-                        outs[c][p] = torch.empty((u8.shape[0], u8.shape[1] if whole else T) + tuple(u8.shape[2:]), dtype=torch.uint8)
+                        outs[c][p] = torch.empty((u8.shape[0], u8.shape[1] if whole else T) + tuple(u8.shape[2:]), dtype=torch.uint8,
+                                                 device="cpu" if to_host else u8.device)
                     outs[c][p][:, win.out_at:win.out_at + u8.shape[1]].copy_(u8)      # D2H straight into the clip's frames
                     carry[c][p] = video[:, :, Wf - O:].contiguous() if O and i + 1 < len(plan) else None
-        return [[o.numpy() for o in per_batch] for per_batch in outs]
+        return [[o.numpy() if to_host else o for o in per_batch] for per_batch in outs]
 
     @staticmethod
     def _shape_tensor(data_batch):

@@ -4,7 +4,7 @@ The tokenizer takes T = 8k + 1 frames and H, W that are multiples of 16 (8 for t
 `plan_fit` decides, on the host, how a (T, H, W) clip gets there: a target size, a resize with the antialiased triangle filter of
 `F.interpolate(mode="bilinear", antialias=True)` written out as per-axis tap tables, a centre crop OF THE RESIZED picture (so the
 crop never cuts what the resize would have kept sharp), and a time index that repeats the last frame up to the next 8k + 1.
-`fit_frames` applies a plan to ComfyUI frames [B, T, H, W, 3] fp32 in [0, 1] and returns the model's [B, 3, T', H', W'] bf16 in
+`fit_frames` applies a plan to ComfyUI frames [B, T, H, W, 3] fp32 in [0, 1] (or uint8, a byte i standing for i / 255) and returns the model's [B, 3, T', H', W'] bf16 in
 [-1, 1]: resample, crop, pad, `* 2 - 1`, round, transpose.  Its torch backend is the specification and what CPU devices run;
 on a GPU one launch of drn_fit_frames (csrc/fit.hip) does all of it.  At scale 1 on both axes (identity or pure crop) both
 backends give the bits of today's ingest, `(image.permute(0, 4, 1, 2, 3) * 2 - 1).to(bf16)`, on the cropped frames.
@@ -202,6 +202,19 @@ def restore_frames(u8: torch.Tensor, rplan: RestorePlan, backend: str = "auto") 
     return native.restore_frames(u8.contiguous(), rplan.T, rplan.y_lo_n, rplan.y_w, rplan.x_lo_n, rplan.x_w)
 
 
+# a source byte i enters the fit as fp32(i) / 255, correctly rounded: the true division, done once on the CPU.  (i * (1 / 255) in
+# fp32 differs from it at 126 of the 256 values; the kernel builds the same table with a correctly rounded division.)
+U8_UNIT = torch.arange(256, dtype=torch.float32) / 255.0
+
+
+def u8_unit(u8: torch.Tensor) -> torch.Tensor:
+    """uint8 frames -> the fp32 frames they stand for, `u8.float() / 255.0` as the CPU computes it, by table lookup: the same
+    bits on any device (no division on the device)."""
+    if u8.dtype != torch.uint8:
+        raise ValueError(f"u8_unit needs uint8, got {u8.dtype}")
+    return U8_UNIT.to(u8.device)[u8.long()]
+
+
 def _fit_torch(image_5d, plan: FitPlan, device, round_bf16=True):
     """The specification: gather frames, antialiased resize, crop slice, * 2 - 1, bf16.  An axis at scale 1 is sliced, not
     interpolated, so a pure crop is a copy."""
@@ -225,19 +238,27 @@ def _fit_torch(image_5d, plan: FitPlan, device, round_bf16=True):
 
 
 def fit_frames(image_5d: torch.Tensor, plan: FitPlan, device, backend: str = "auto") -> torch.Tensor:
-    """[B, T, H, W, 3] fp32 in [0, 1] -> [B, 3, T', H', W'] bf16 in [-1, 1] on `device`.  backend: 'auto' = the HIP kernel
-    (drn_fit_frames) on a GPU device and torch on a CPU device; 'torch' / 'hip' force a path ('hip' needs a GPU device)."""
+    """[B, T, H, W, 3] fp32 in [0, 1], or uint8 (a byte i standing for i / 255, `u8_unit`), on the host or on a device ->
+    [B, 3, T', H', W'] bf16 in [-1, 1] on `device`.  backend: 'auto' = the HIP kernel (drn_fit_frames, for uint8 frames
+    drn_fit_frames_u8: the bytes are what is uploaded) on a GPU device and torch on a CPU device; 'torch' / 'hip' force a path
+    ('hip' needs a GPU device).  The torch path on uint8 frames is `u8_unit`, then the fp32 specification."""
     if backend not in ("auto", "torch", "hip"):
         raise ValueError(f"unknown backend {backend!r}")
     if image_5d.ndim != 5 or image_5d.shape[-1] != 3:
         raise ValueError(f"fit needs [B, T, H, W, 3] frames, got {tuple(image_5d.shape)}")
+    if image_5d.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"fit needs float32 or uint8 frames, got {image_5d.dtype}")
     if tuple(image_5d.shape[1:4]) != (plan.T, plan.H, plan.W):
         raise ValueError(f"the plan was made for {(plan.T, plan.H, plan.W)} frames, got {tuple(image_5d.shape[1:4])}")
     on_gpu = torch.device(device).type == "cuda"
     if backend == "hip" and not on_gpu:
         raise ValueError(f"backend='hip' needs a GPU device, got {device!r} (the torch path is what CPU devices run)")
+    u8 = image_5d.dtype == torch.uint8
     if backend == "torch" or not on_gpu:
-        return _fit_torch(image_5d, plan, device)
+        return _fit_torch(u8_unit(image_5d) if u8 else image_5d, plan, device)
     from . import native
+    if u8:
+        src = image_5d.to(device=device).contiguous()
+        return native.fit_frames_u8(src, plan.t_idx, plan.y_lo_n, plan.y_w, plan.x_lo_n, plan.x_w)
     src = image_5d.to(device=device, dtype=torch.float32).contiguous()
     return native.fit_frames(src, plan.t_idx, plan.y_lo_n, plan.y_w, plan.x_lo_n, plan.x_w)

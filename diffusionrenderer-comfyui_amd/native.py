@@ -116,6 +116,7 @@ SIGNATURES = {
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     "drn_fit_frames": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    "drn_fit_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_restore_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
@@ -866,13 +867,10 @@ def _check_tap_table(lo_n, w, n_in):
         "taps outside the source"
 
 
-def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
-    """Clip ingest with a fit to the model's grid (drn_fit_frames; the plan: fit.plan_fit).  src [B, Ts, Hs, Ws, 3] fp32 on the
-    device, contiguous; the plan's tables as HOST tensors (t_idx int32 [Td], per axis lo_n int32 [n_out, 2] and w fp32 [n_out, K]):
-    they are checked here, where their contents can be read, and uploaded -> [B, 3, Td, Hd, Wd] bf16 in [-1, 1].  out: such a
-    tensor to write into."""
-    assert src.dtype == torch.float32 and src.ndim == 5 and src.shape[-1] == 3 and src.is_contiguous(), \
-        "contiguous fp32 [B, T, H, W, 3] frames required"
+def _fit_frames(symbol, dtype, what, src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out):
+    """drn_fit_frames / drn_fit_frames_u8: one argument list, the source's element type apart."""
+    assert src.dtype == dtype and src.ndim == 5 and src.shape[-1] == 3 and src.is_contiguous(), \
+        f"contiguous {what} [B, T, H, W, 3] frames required"
     B, Ts, Hs, Ws, _ = src.shape
     assert t_idx.dtype == torch.int32 and t_idx.ndim == 1 and 0 <= int(t_idx.min()) and int(t_idx.max()) < Ts, "t_idx outside the clip"
     _check_tap_table(y_lo_n, y_w, Hs)
@@ -882,9 +880,24 @@ def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
         out = torch.empty((B, 3, Td, Hd, Wd), dtype=torch.bfloat16, device=src.device)
     assert out.dtype == torch.bfloat16 and tuple(out.shape) == (B, 3, Td, Hd, Wd) and out.is_contiguous()
     dev = [t.contiguous().to(src.device) for t in (t_idx, y_lo_n, y_w, x_lo_n, x_w)]
-    _check(load_library().drn_fit_frames(_ptr(src), _ptr(out), B, Ts, Hs, Ws, Td, Hd, Wd, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]),
-                                         y_w.shape[1], _ptr(dev[3]), _ptr(dev[4]), x_w.shape[1], _stream()), "drn_fit_frames")
+    _check(getattr(load_library(), symbol)(_ptr(src), _ptr(out), B, Ts, Hs, Ws, Td, Hd, Wd, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]),
+                                           y_w.shape[1], _ptr(dev[3]), _ptr(dev[4]), x_w.shape[1], _stream()), symbol)
     return out
+
+
+def fit_frames(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
+    """Clip ingest with a fit to the model's grid (drn_fit_frames; the plan: fit.plan_fit).  src [B, Ts, Hs, Ws, 3] fp32 on the
+    device, contiguous; the plan's tables as HOST tensors (t_idx int32 [Td], per axis lo_n int32 [n_out, 2] and w fp32 [n_out, K]):
+    they are checked here, where their contents can be read, and uploaded -> [B, 3, Td, Hd, Wd] bf16 in [-1, 1].  out: such a
+    tensor to write into."""
+    return _fit_frames("drn_fit_frames", torch.float32, "fp32", src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out)
+
+
+def fit_frames_u8(src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out=None):
+    """fit_frames from 8-bit frames (drn_fit_frames_u8): src [B, Ts, Hs, Ws, 3] uint8 on the device, contiguous, at any byte
+    alignment; a byte i enters as fp32(i) / 255 correctly rounded, so the result is fit_frames on fit.u8_unit(src) bit for bit.
+    The tables and `out` as for fit_frames."""
+    return _fit_frames("drn_fit_frames_u8", torch.uint8, "uint8", src, t_idx, y_lo_n, y_w, x_lo_n, x_w, out)
 
 
 def restore_frames(src, T, y_lo_n, y_w, x_lo_n, x_w, out=None):

@@ -90,11 +90,24 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
     """{name: frames in [0, 1]} -> ({name: (B,C,T,H,W) in [-1, 1]}, the fit's plan).  fit off: no plan, the clips must be on the
     model's grid.  Otherwise all clips go through ONE plan (fit.py: resize / crop / pad in time, * 2 - 1, bf16 and the transpose in
     one launch on the pipeline's device), so they must be one size; with fit_restore the pipeline is handed the way back
-    (ValueError for a crop that cut, before anything runs)."""
-    clips = {name: standardize_to_5d(t, name) for name, t in clips.items()}
-    if fit == "off":
-        return {name: t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0 for name, t5 in clips.items()}, None
+    (ValueError for a crop that cut, before anything runs).  A uint8 clip (a byte i standing for i / 255) always goes through
+    fit_frames, which uploads the bytes: with fit off under the identity plan, so it must be on the grid in H and W like any clip
+    (a T off 8k+1 is refused downstream, as for fp32), and arrives as the device bf16 tensor the fp32 clip u8 / 255 becomes."""
     from .fit import fit_frames, plan_fit, plan_restore
+    clips = {name: standardize_to_5d(t, name) for name, t in clips.items()}
+    device = getattr(pipeline, "device", "cuda")
+    if fit == "off":
+        out = {}
+        for name, t5 in clips.items():
+            if t5.dtype != torch.uint8:
+                out[name] = t5.permute(0, 4, 1, 2, 3) * 2.0 - 1.0
+                continue
+            same = plan_fit(*t5.shape[1:4], "crop", 0, 0, windowed=True)
+            if not same.identity:
+                raise ValueError(f"'{name}' is uint8 frames of (H, W) = {tuple(t5.shape[2:4])}, off the model's grid of 16: "
+                                 "set fit = 'crop' or 'stretch' (with fit off a clip is taken as it is)")
+            out[name] = fit_frames(t5, same, device=device)
+        return out, None
     first, shape = next((name, tuple(t5.shape[1:4])) for name, t5 in clips.items())
     for name, t5 in clips.items():
         if tuple(t5.shape[1:4]) != shape:
@@ -103,8 +116,71 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
     plan = plan_fit(*shape, fit, fit_height, fit_width, windowed=window_frames > 0 and shape[0] > window_frames)
     if fit_restore:
         pipeline.restore_plan = plan_restore(plan)      # the outputs come back at the source's size
-    device = getattr(pipeline, "device", "cuda")
     return {name: fit_frames(t5, plan, device=device) for name, t5 in clips.items()}, plan
+
+
+def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
+                    to_host=True):
+    """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
+    as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
+    results are device tensors (the pipeline's `to_host`)."""
+    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap)
+    clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
+    image_tensor = clips["image"]
+    keep = plan.T if plan is not None else None
+    kw = {} if to_host else {"to_host": False}
+    normalize = [p == "normal" for p in INVERSE_PASSES]
+    if image_tensor.shape[0] == 1 and getattr(pipeline, "batch_passes", True) and hasattr(pipeline, "generate_video_passes"):
+        # the five passes share the clip, the seed and every weight: step them as one batch (SURVEY.md 8f N1)
+        data_batch = {
+            "rgb": image_tensor,
+            "video": image_tensor,
+            "context_index": torch.tensor([[GBUFFER_INDEX_MAPPING[p]] for p in INVERSE_PASSES], dtype=torch.long),
+        }
+        outs = pipeline.generate_video_passes(data_batch=data_batch, seed=seed, normalize_normal=normalize, **kw)
+    else:
+        batches = [{"rgb": image_tensor,
+                    "video": image_tensor,
+                    "context_index": torch.full((image_tensor.shape[0], 1), GBUFFER_INDEX_MAPPING[p], dtype=torch.long)}
+                   for p in INVERSE_PASSES]
+        if window_frames and hasattr(pipeline, "generate_video_each"):
+            # windows outside, passes inside: every window of the clip is uploaded and encoded once, not once per pass
+            outs = pipeline.generate_video_each(batches, normalize, seed=seed, **kw)
+        else:       # pass by pass, each rendered as the loop below asks for it: the progress bar moves per pass
+            outs = (pipeline.generate_video(data_batch=b, normalize_normal=f, seed=seed, **kw) for b, f in zip(batches, normalize))
+    return outs, keep, plan
+
+
+def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
+                  env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None):
+    """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
+    (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit)."""
+    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap)
+    key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
+                   "metallic": "metallic"}
+    # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
+    clips, plan = _ingest(pipeline, inputs, fit, fit_height, fit_width, fit_restore, window_frames)
+    if restore_plan is not None:
+        pipeline.restore_plan = restore_plan
+    data_batch = {key_mapping[name]: t for name, t in clips.items()}
+    keep = None
+    if plan is not None:
+        keep = plan.T
+        # frame t keeps the angle radians(env_spin) * t / T of the clip as handed in; padded frames turn on and are cut away
+        env_spin = env_spin * plan.T_out / plan.T
+    B, _, T, H, W = data_batch["depth"].shape
+    data_batch["video"] = data_batch["depth"]
+    # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
+    # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static.
+    # Built for the WHOLE clip also when it is rendered in windows: the pipeline cuts them per window like the G-buffers
+    from . import preprocess_envmap as pe
+    env = pe.envmap_conditions(env_map, (H, W), T, env_format, env_brightness, env_flip_horizontal, env_rotation,
+                               device=getattr(pipeline, "device", "cuda"), env_spin=env_spin)
+    data_batch["env_ldr"] = env["env_ldr"].expand(B, -1, -1, -1, -1)
+    data_batch["env_log"] = env["env_log"].expand(B, -1, -1, -1, -1)
+    data_batch["env_nrm"] = env["env_nrm"].expand(B, -1, T, -1, -1)
+    out = pipeline.generate_video(data_batch=data_batch, seed=seed)
+    return torch.from_numpy(out[:, :keep]).float() / 255.0
 
 
 class LoadDiffusionRendererModel:
@@ -173,29 +249,8 @@ class Cosmos1InverseRenderer:
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False):
-        _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap)
-        clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
-        image_tensor = clips["image"]
-        keep = plan.T if plan is not None else None
-        normalize = [p == "normal" for p in INVERSE_PASSES]
-        if image_tensor.shape[0] == 1 and getattr(pipeline, "batch_passes", True) and hasattr(pipeline, "generate_video_passes"):
-            # the five passes share the clip, the seed and every weight: step them as one batch
-            data_batch = {
-                "rgb": image_tensor,
-                "video": image_tensor,
-                "context_index": torch.tensor([[GBUFFER_INDEX_MAPPING[p]] for p in INVERSE_PASSES], dtype=torch.long),
-            }
-            outs = pipeline.generate_video_passes(data_batch=data_batch, seed=seed, normalize_normal=normalize)
-        else:
-            batches = [{"rgb": image_tensor,
-                        "video": image_tensor,
-                        "context_index": torch.full((image_tensor.shape[0], 1), GBUFFER_INDEX_MAPPING[p], dtype=torch.long)}
-                       for p in INVERSE_PASSES]
-            if window_frames and hasattr(pipeline, "generate_video_each"):
-                # windows outside, passes inside: every window of the clip is uploaded and encoded once, not once per pass
-                outs = pipeline.generate_video_each(batches, normalize, seed=seed)
-            else:       # pass by pass, each rendered as the loop below asks for it: the progress bar moves per pass
-                outs = (pipeline.generate_video(data_batch=b, normalize_normal=f, seed=seed) for b, f in zip(batches, normalize))
+        outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
+                                        fit_restore)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -230,31 +285,9 @@ class Cosmos1ForwardRenderer:
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
                          fit_restore=False):
-        _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap)
-        key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
-                       "metallic": "metallic"}
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
-        # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
-        clips, plan = _ingest(pipeline, inputs, fit, fit_height, fit_width, fit_restore, window_frames)
-        data_batch = {key_mapping[name]: t for name, t in clips.items()}
-        keep = None
-        if plan is not None:
-            keep = plan.T
-            # frame t keeps the angle radians(env_spin) * t / T of the clip as handed in; padded frames turn on and are cut away
-            env_spin = env_spin * plan.T_out / plan.T
-        B, _, T, H, W = data_batch["depth"].shape
-        data_batch["video"] = data_batch["depth"]
-        # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
-        # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static.
-        # Built for the WHOLE clip also when it is rendered in windows: the pipeline cuts them per window like the G-buffers
-        from . import preprocess_envmap as pe
-        env = pe.envmap_conditions(env_map, (H, W), T, env_format, env_brightness, env_flip_horizontal, env_rotation,
-                                   device=getattr(pipeline, "device", "cuda"), env_spin=env_spin)
-        data_batch["env_ldr"] = env["env_ldr"].expand(B, -1, -1, -1, -1)
-        data_batch["env_log"] = env["env_log"].expand(B, -1, -1, -1, -1)
-        data_batch["env_nrm"] = env["env_nrm"].expand(B, -1, T, -1, -1)
-        out = pipeline.generate_video(data_batch=data_batch, seed=seed)
-        return (torch.from_numpy(out[:, :keep]).float() / 255.0,)
+        return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
+                              env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore),)
 
 
 class LoadHDRImage:
@@ -276,6 +309,66 @@ class LoadHDRImage:
         return (torch.from_numpy(img).float().unsqueeze(0),)
 
 
+class Cosmos1Relight:
+    """Video -> G-buffers -> the same video under a new environment light, in one call: the inverse renderer, then the forward
+    renderer on its G-buffers, which stay on the device as the bytes the post-process wrote (drn_fit_frames_u8 ingests them).
+    The bits are those of the two nodes chained through the host.  Not one of the reference's nodes: registered only with
+    DRN_EXTRA_NODES=1 (below)."""
+
+    @classmethod
+    def INPUT_TYPES(s):
+        return {
+            "required": {"inverse_pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "forward_pipeline": ("DIFFUSION_RENDERER_PIPELINE",),
+                         "image": ("IMAGE",), "env_map": ("IMAGE",)},
+            "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1,
+                                                "tooltip": "guidance of the inverse stage"}),
+                         "forward_guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 2.0, "step": 0.1}),
+                         "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
+                         "env_format": (["proj", "ball"], {"default": "proj"}),
+                         "env_brightness": ("FLOAT", {"default": 1.0, "min": 0.0, "max": 2.0, "step": 0.1}),
+                         "env_flip_horizontal": ("BOOLEAN", {"default": False}),
+                         "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
+                         "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
+                         **_window_inputs(), **_fit_inputs()},
+        }
+
+    RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
+    RETURN_NAMES = ("image", "base_color", "metallic", "roughness", "normal", "depth")
+    FUNCTION = "run_relight"
+    CATEGORY = "Cosmos1"
+
+    def run_relight(self, inverse_pipeline, forward_pipeline, image, env_map, guidance=0.0, forward_guidance=0.0, seed=42,
+                    env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
+                    window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False):
+        """The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...})."""
+        from .fit import plan_fit, plan_restore, restore_frames
+        rplan = None
+        if fit != "off" and fit_restore:        # a crop that cut is refused before any GPU work, as the two nodes refuse it
+            T, H, W = standardize_to_5d(image).shape[1:4]
+            rplan = plan_restore(plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames))
+        # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
+        outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
+                                        fit_width, False, to_host=False)
+        gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
+        # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
+        # pads time as the forward node would; the way back is the inverse fit's
+        names = {"basecolor": "base_color"}
+        inputs = {names.get(p, p): g for p, g in zip(INVERSE_PASSES, gbuffers)}
+        inputs = {k: inputs[k] for k in ("depth", "normal", "roughness", "metallic", "base_color")}
+        relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
+                              env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
+                              restore_plan=rplan)
+        # 4. the G-buffers as the inverse node returns them
+        images = []
+        for g in gbuffers:
+            if rplan is not None:
+                g = restore_frames(g, rplan)
+            t = g.cpu().float() / 255.0
+            b, tt, h, w, c = t.shape
+            images.append(t.reshape(b * tt, h, w, c))
+        return (relit, *images)
+
+
 NODE_CLASS_MAPPINGS = {
     "LoadDiffusionRendererModel": LoadDiffusionRendererModel,
     "Cosmos1InverseRenderer": Cosmos1InverseRenderer,
@@ -289,3 +382,12 @@ NODE_DISPLAY_NAME_MAPPINGS = {
     "Cosmos1ForwardRenderer": "Cosmos1 Forward Renderer",
     "LoadHDRImage": "Load HDR Image",
 }
+
+# nodes the reference does not have.  NODE_CLASS_MAPPINGS stays the reference's four entries (the drop-in surface); these join the
+# exported mappings only when DRN_EXTRA_NODES=1 is set when this module is imported
+EXTRA_NODE_CLASS_MAPPINGS = {"Cosmos1Relight": Cosmos1Relight}
+EXTRA_NODE_DISPLAY_NAME_MAPPINGS = {"Cosmos1Relight": "Cosmos1 Relight"}
+
+if os.environ.get("DRN_EXTRA_NODES") == "1":
+    NODE_CLASS_MAPPINGS.update(EXTRA_NODE_CLASS_MAPPINGS)
+    NODE_DISPLAY_NAME_MAPPINGS.update(EXTRA_NODE_DISPLAY_NAME_MAPPINGS)

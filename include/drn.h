@@ -520,6 +520,24 @@ int drn_fit_frames(const float* src, void* dst_bf16, int B, int Ts, int Hs, int 
                    const int* t_idx, const int* y_lo_n, const float* y_w, int Ky,
                    const int* x_lo_n, const float* x_w, int Kx, void* stream);
 
+/* ---- the same ingest from 8-bit frames (what decoded video is, and what the post-process leaves on the device: the uint8
+ * G-buffers of the inverse renderer become the forward renderer's conditions without a host round trip; no reference line).
+ * ONE launch: drn_fit_frames on the frames unit[src], bit for bit at every geometry, where
+ *   unit[i] = fp32(i) / 255.0f, correctly rounded (the division, NOT a multiplication by 1.0f / 255: that differs at 126 of the
+ *   256 byte values), which is what `u8.float() / 255.0` gives on the host.
+ * From there the arithmetic is drn_fit_frames': fma accumulation from 0 in tap order, the row pass first, 2 * acc - 1 rounded
+ * once, round to nearest even.  A single tap of weight 1.0 on both axes gives the bits of
+ * `((u8.float() / 255).permute(0, 4, 1, 2, 3) * 2 - 1).to(bf16)`.
+ *   src [B,Ts,Hs,Ws,3] uint8, contiguous, at ANY byte alignment; dst [B,3,Td,Hd,Wd] bf16, contiguous; the tables as for
+ *   drn_fit_frames, with the same clamping of lo, n and t_idx (what they should hold is checked on the host,
+ *   native.fit_frames_u8).  Nothing outside src is read: a row's bytes are fetched with aligned 4-byte loads inside the span the
+ *   tile's taps cover, its ragged ends bytewise.
+ * DRN_EINVAL (nothing launched): a null pointer, a non-positive size, Ky or Kx outside 1..32, Hd or Wd not a multiple of 16,
+ * B*3*Td*Hd*Wd or B*Ts*Hs*Ws*3 (bytes) >= 2^31, a table not 4-byte aligned, dst not 16-byte aligned. */
+int drn_fit_frames_u8(const uint8_t* src, void* dst_bf16, int B, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
+                      const int* t_idx, const int* y_lo_n, const float* y_w, int Ky,
+                      const int* x_lo_n, const float* x_w, int Kx, void* stream);
+
 /* ---- the fit's way back: the uint8 result of the post-process resampled to the source's size (no reference line: the reference
  * has neither a fit nor its inverse; this is the inverse of drn_fit_frames for fits that kept the whole picture, and replaces a
  * resize of fp32 frames on the host; plan and torch specification: fit.py, plan_restore / restore_frames).
