@@ -20,6 +20,7 @@ from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
 from .fit import restore_frames
 from .model_diffusion_renderer import CleanDiffusionRendererModel
+from .tiles import blend_tile, plan_tiles
 from .windows import Window, plan_windows, ramp_weights
 
 _SHAPE_KEYS = ("rgb", "image", "basecolor", "normal", "depth", "roughness", "metallic")
@@ -48,6 +49,12 @@ class CleanDiffusionRendererPipeline:
         # the fit's way back (fit.py): a RestorePlan -> the uint8 outputs are resampled to the source's size on the device, before
         # the D2H copy; None = the outputs keep the model's size (today's path, today's bits)
         self.restore_plan = None
+        # large pictures (tiles.py): a picture larger than tile_height x tile_width (multiples of 16; 0 = that axis is not tiled,
+        # both 0 = off; 576 x 1024 = the training size) is rendered as overlapping tiles of exactly that size, each an independent
+        # sample, cross-faded over `tile_overlap` rows / columns where the results lie as uint8 on the device
+        self.tile_height = 0
+        self.tile_width = 0
+        self.tile_overlap = 64
         self.device = torch.device("cuda")     # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
@@ -203,7 +210,60 @@ class CleanDiffusionRendererPipeline:
         plan = plan_windows(T, self.window_frames, self.window_overlap)     # ValueError on a bad length / overlap
         return plan if len(plan) > 1 else None
 
+    def _tile_plan(self, data_batch):
+        """The spatial tiles of this picture (tiles.plan_tiles), or None where it is one tile (tiles off, or a picture that fits)."""
+        if not (self.tile_height or self.tile_width):
+            return None
+        inst = self.pre_loaded_model_instance
+        if isinstance(inst, dict):
+            inst = inst.get(self.model_type)
+        if getattr(inst if inst is not None else self.model, "process_group", None) is not None:
+            raise NotImplementedError("tiles under sequence parallelism are not implemented: set tile_height = tile_width = 0")
+        ref = self._shape_tensor(data_batch)
+        if ref.ndim != 5:
+            return None
+        return plan_tiles(ref.shape[3], ref.shape[4], self.tile_height, self.tile_width, self.tile_overlap)   # ValueError on a bad size
+
     def _render(self, batches, flags, seed, init_noise, clips=False, to_host=True):
+        """Per batch, per pass: uint8 [B, T, H, W, 3] (numpy on the host, or with to_host=False torch tensors on the pipeline's
+        device).  A picture of one tile is `_walk`, untouched.  A larger one is rendered tile by tile in raster order around that
+        same walk: every 5-D tensor of the picture's (H, W) is cropped to the tile (once per tensor identity: rgb / video, and the
+        batches of one clip, share a crop), the walk runs on the crops with its result left on the device at the tile's size -
+        windows, carries and passes as they are, same seed, same start noise: every tile has one shape -, and each result is
+        cross-faded into that pass's full-size canvas (tiles.blend_tile).  After the last tile the restore plan is applied once
+        per canvas (it also cuts the time padding), then the copy to the host.  Device memory: one full-size uint8 canvas per
+        pass plus one tile's results."""
+        if not batches:
+            return []
+        tiles = self._tile_plan(batches[0])
+        if tiles is None:
+            return self._walk(batches, flags, seed, init_noise, clips, to_host)
+        H, W = self._shape_tensor(batches[0]).shape[3:5]
+        canvas = None
+        rplan, self.restore_plan = self.restore_plan, None         # the way back runs once, on the joined picture
+        try:
+            for tile in tiles:
+                cropped = {}
+
+                def crop(v):
+                    if not (isinstance(v, torch.Tensor) and v.ndim == 5 and tuple(v.shape[3:5]) == (H, W)):
+                        return v
+                    if id(v) not in cropped:
+                        cropped[id(v)] = (v, v[..., tile.y:tile.y + tile.h, tile.x:tile.x + tile.w].contiguous())
+                    return cropped[id(v)][1]
+                outs = self._walk([{k: crop(v) for k, v in b.items()} for b in batches], flags, seed, init_noise, clips, False)
+                if canvas is None:
+                    canvas = [[torch.empty(tuple(o.shape[:2]) + (H, W, 3), dtype=torch.uint8, device=o.device) for o in per_batch]
+                              for per_batch in outs]
+                for cs, os_ in zip(canvas, outs):
+                    for c, o in zip(cs, os_):
+                        blend_tile(c, o, tile)
+        finally:
+            self.restore_plan = rplan
+        done = [[self._restored(c) for c in cs] for cs in canvas]
+        return [[c.cpu().numpy() if to_host else c for c in cs] for cs in done]
+
+    def _walk(self, batches, flags, seed, init_noise, clips=False, to_host=True):
         """The one walk from batches to uint8 frames -> per batch, per pass: uint8 [B, T, H, W, 3], numpy arrays on the host, or
         with to_host=False torch tensors on the pipeline's device (the same walk: only the buffer the written frames are copied
         into lives there, so what the inverse renderer made can feed the forward renderer without a host round trip).  Walk the clip's

@@ -118,6 +118,7 @@ SIGNATURES = {
     "drn_fit_frames": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_fit_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_restore_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
+    "drn_tile_blend_u8": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
@@ -920,6 +921,28 @@ def restore_frames(src, T, y_lo_n, y_w, x_lo_n, x_w, out=None):
                                                 y_w.shape[1], _ptr(dev[2]), _ptr(dev[3]), x_w.shape[1], _stream()),
            "drn_restore_frames_u8")
     return out
+
+
+def tile_blend_u8(canvas, tile, wy, wx, y_at: int, x_at: int, ry: int, rx: int):
+    """One spatial tile into the picture's canvas, in place (drn_tile_blend_u8; the plan: tiles.plan_tiles).  canvas [B,T,H,W,3]
+    and tile [B,T,h,w,3] uint8 on the device, contiguous, at any byte alignment; the tile's rows from ry and columns from rx on
+    land at (y_at + ry, x_at + rx), the first len(wy) written rows and len(wx) written columns cross-faded over what the canvas
+    holds.  wy / wx: fp32 ramp weights on the device, or None for no ramp on that axis.  Returns the canvas."""
+    for t in (canvas, tile):
+        assert t.dtype == torch.uint8 and t.ndim == 5 and t.shape[-1] == 3 and t.is_contiguous(), \
+            "contiguous uint8 [B, T, H, W, 3] frames required"
+    B, T, H, W, _ = canvas.shape
+    h, w = tile.shape[2:4]
+    assert tuple(tile.shape[:2]) == (B, T) and tile.device == canvas.device, "canvas and tile are one clip on one device"
+    O = []
+    for name, t in (("wy", wy), ("wx", wx)):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.ndim == 1 and t.numel() > 0 and t.is_contiguous() and t.device == canvas.device, \
+                f"{name}: a non-empty contiguous fp32 vector on the canvas's device, or None"
+        O.append(0 if t is None else t.numel())
+    _check(load_library().drn_tile_blend_u8(_ptr(canvas), _ptr(tile), _ptr(wy), _ptr(wx), B * T, H, W, h, w, y_at, x_at, ry, rx,
+                                            O[0], O[1], _stream()), "drn_tile_blend_u8")
+    return canvas
 
 
 def dit_forward(args: "DitForwardArgs"):

@@ -38,6 +38,23 @@ def _window_inputs():
                                                   "0 = hard cuts"})}
 
 
+def _tile_inputs():
+    """Optional inputs of the renderers for large pictures (tiles.py)."""
+    return {"tile_height": ("INT", {"default": 0, "min": 0, "max": 4096, "step": 16,
+                                    "tooltip": "0 = off: the picture's whole height is one sequence.  A multiple of 16 (576 x 1024 "
+                                               "recommended: the training size): a picture larger than tile_height x tile_width "
+                                               "is rendered as overlapping tiles of exactly that size, cross-faded in pixel "
+                                               "space.  Tiles apply to the FITTED picture (after fit, before fit_restore) and are "
+                                               "independent samples: they share the seed but are not conditioned on each other, "
+                                               "so two tiles may disagree - the cross-fade hides the seam, not the disagreement"}),
+            "tile_width": ("INT", {"default": 0, "min": 0, "max": 4096, "step": 16,
+                                   "tooltip": "0 = off: the picture's whole width is one sequence.  A multiple of 16 (1024 "
+                                              "recommended, with tile_height 576)"}),
+            "tile_overlap": ("INT", {"default": 64, "min": 0, "max": 2048, "step": 1,
+                                     "tooltip": "rows / columns two neighbouring tiles share (at most half the tile's side); "
+                                                "0 = hard cuts"})}
+
+
 def _fit_inputs():
     """Optional inputs of both renderers for clips off the model's grid (fit.py)."""
     return {"fit": (["off", "crop", "stretch"],
@@ -76,13 +93,15 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
     raise TypeError(f"Unsupported input type for '{name}': {type(image)}. Expected torch.Tensor or list of Tensors.")
 
 
-def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap):
-    """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared."""
+def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64)):
+    """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
+    (tile_height, tile_width, tile_overlap)."""
     pipeline.set_model_type(model_type)
     pipeline.guidance = guidance
     pipeline.seed = seed
     pipeline.window_frames = window_frames
     pipeline.window_overlap = window_overlap
+    pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
     pipeline.restore_plan = None
 
 
@@ -120,11 +139,11 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                    to_host=True):
+                    to_host=True, tiles=(0, 0, 64)):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
-    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap)
+    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     image_tensor = clips["image"]
     keep = plan.T if plan is not None else None
@@ -152,10 +171,11 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 
 
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
-                  env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None):
+                  env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
+                  tiles=(0, 0, 64)):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
     (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit)."""
-    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap)
+    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
     # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
@@ -172,7 +192,8 @@ def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_bri
     data_batch["video"] = data_batch["depth"]
     # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
     # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static.
-    # Built for the WHOLE clip also when it is rendered in windows: the pipeline cuts them per window like the G-buffers
+    # Built for the WHOLE clip and the WHOLE picture also when it is rendered in windows or tiles: the pipeline cuts them per
+    # window and crops them per tile like the G-buffers (they are per-pixel view-direction images)
     from . import preprocess_envmap as pe
     env = pe.envmap_conditions(env_map, (H, W), T, env_format, env_brightness, env_flip_horizontal, env_rotation,
                                device=getattr(pipeline, "device", "cuda"), env_spin=env_spin)
@@ -239,7 +260,7 @@ class Cosmos1InverseRenderer:
             "required": {"pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "image": ("IMAGE",)},
             "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1}),
                          "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
-                         **_window_inputs(), **_fit_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -248,9 +269,9 @@ class Cosmos1InverseRenderer:
     CATEGORY = "Cosmos1"
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
-                         fit="off", fit_height=0, fit_width=0, fit_restore=False):
+                         fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
-                                        fit_restore)
+                                        fit_restore, tiles=(tile_height, tile_width, tile_overlap))
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -274,7 +295,7 @@ class Cosmos1ForwardRenderer:
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
-                         **_window_inputs(), **_fit_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE",)
@@ -284,10 +305,11 @@ class Cosmos1ForwardRenderer:
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
-                         fit_restore=False):
+                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64):
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
-                              env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore),)
+                              env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
+                              tiles=(tile_height, tile_width, tile_overlap)),)
 
 
 class LoadHDRImage:
@@ -329,7 +351,7 @@ class Cosmos1Relight:
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
-                         **_window_inputs(), **_fit_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -339,16 +361,18 @@ class Cosmos1Relight:
 
     def run_relight(self, inverse_pipeline, forward_pipeline, image, env_map, guidance=0.0, forward_guidance=0.0, seed=42,
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
-                    window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False):
-        """The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...})."""
+                    window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
+                    tile_height=0, tile_width=0, tile_overlap=64):
+        """Tiles apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...})."""
         from .fit import plan_fit, plan_restore, restore_frames
+        tiles = (tile_height, tile_width, tile_overlap)
         rplan = None
         if fit != "off" and fit_restore:        # a crop that cut is refused before any GPU work, as the two nodes refuse it
             T, H, W = standardize_to_5d(image).shape[1:4]
             rplan = plan_restore(plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames))
         # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
-                                        fit_width, False, to_host=False)
+                                        fit_width, False, to_host=False, tiles=tiles)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's
@@ -357,7 +381,7 @@ class Cosmos1Relight:
         inputs = {k: inputs[k] for k in ("depth", "normal", "roughness", "metallic", "base_color")}
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
-                              restore_plan=rplan)
+                              restore_plan=rplan, tiles=tiles)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:

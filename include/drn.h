@@ -1,8 +1,8 @@
 /* drn.h - C ABI of libdrn.so: the MI355X (gfx950) kernels behind the DiffusionRenderer
  * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer),
  * the forward renderer's per-frame environment-light projection (drn_env_project), the
- * nodes' clip ingest with a fit to the model's grid (drn_fit_frames) and its way back on the
- * uint8 outputs (drn_restore_frames_u8).
+ * nodes' clip ingest with a fit to the model's grid (drn_fit_frames), its way back on the
+ * uint8 outputs (drn_restore_frames_u8) and the join of spatial tiles on them (drn_tile_blend_u8).
  *
  * The reference (eggsbenedicto/DiffusionRenderer-ComfyUI) is pure Python/torch and has no FFI;
  * each entry point below names the reference code (file:line under /root/reference) whose
@@ -553,6 +553,25 @@ int drn_fit_frames_u8(const uint8_t* src, void* dst_bf16, int B, int Ts, int Hs,
  * B*Ts*Hs*Ws*3 >= 2^31, a table not 4-byte aligned. */
 int drn_restore_frames_u8(const uint8_t* src, uint8_t* dst, int B, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
                           const int* y_lo_n, const float* y_w, int Ky, const int* x_lo_n, const float* x_w, int Kx, void* stream);
+
+/* ---- spatial tiles: one rendered tile cross-faded into the picture's canvas, in place (no reference line: the reference renders
+ * a picture as one sequence; plan and torch specification: tiles.py, plan_tiles / blend_tile).
+ * ONE launch.  canvas [frames,H,W,3] and tile [frames,h,w,3] uint8, contiguous, at ANY byte alignment.  For tile-local
+ * y in [ry, h), x in [rx, w) and every channel, with a = canvas[f][y_at + y][x_at + x][ch], b = tile[f][y][x][ch] as fp32:
+ *   wgt = Wy(y - ry) * Wx(x - rx)       (one fp32 multiply; Wy(i) = wy[i] for i < Oy and 1.0f behind, Wx likewise)
+ *   wgt == 1:  canvas <- b               (the canvas is not read)
+ *   else:      canvas <- uint8(clamp(rint(a + wgt * (b - a)), 0, 255))
+ * subtract, multiply and add three separately rounded fp32 operations (never an FMA), rint = round to nearest even.
+ *   wy fp32 [Oy], wx fp32 [Ox] on the device (windows.ramp_weights); NULL exactly where the count is 0.
+ * Rows in front of ry and columns in front of rx of the tile are not used.  Nothing outside the rectangle
+ * [y_at + ry, y_at + h) x [x_at + rx, x_at + w) of the canvas is written, and nothing outside it is read from the canvas.  Frame
+ * bases are 64-bit: the canvas may pass 2^31 bytes, one frame of either side may not.
+ * DRN_EINVAL (nothing launched): a null canvas or tile, a size < 1, y_at < 0, x_at < 0, y_at + h > H, x_at + w > W, ry outside
+ * [0, h), rx outside [0, w), Oy < 0, Ox < 0, ry + Oy > h, rx + Ox > w, wy == NULL not equivalent to Oy == 0 (wx and Ox likewise),
+ * a weight table not 4-byte aligned, a frame of either side of 2^31 bytes or more, more than 2^31 workgroups (frames x 16-row x
+ * 128-pixel blocks of the written rectangle). */
+int drn_tile_blend_u8(void* canvas, const void* tile, const void* wy, const void* wx, int64_t frames, int H, int W, int h, int w,
+                      int y_at, int x_at, int ry, int rx, int Oy, int Ox, void* stream);
 
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
