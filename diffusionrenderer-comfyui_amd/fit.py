@@ -6,12 +6,12 @@ The tokenizer takes T = 8k + 1 frames and H, W that are multiples of 16 (8 for t
 crop never cuts what the resize would have kept sharp), and a time index that repeats the last frame up to the next 8k + 1.
 `fit_frames` applies a plan to ComfyUI frames [B, T, H, W, 3] fp32 in [0, 1] (or uint8, a byte i standing for i / 255) and returns the model's [B, 3, T', H', W'] bf16 in
 [-1, 1]: resample, crop, pad, `* 2 - 1`, round, transpose.  Its torch backend is the specification and what CPU devices run;
-on a GPU one launch of drn_fit_frames (csrc/fit.hip) does all of it.  At scale 1 on both axes (identity or pure crop) both
+on a GPU one launch of drn_fit_frames or, from uint8, drn_fit_frames_u8 (one kernel template, csrc/fit.hip) does all of it.  At scale 1 on both axes (identity or pure crop) both
 backends give the bits of today's ingest, `(image.permute(0, 4, 1, 2, 3) * 2 - 1).to(bf16)`, on the cropped frames.
 
 The way back (the nodes' `fit_restore`): `plan_restore` turns the plan of a fit that kept the whole picture round, and
 `restore_frames` resamples the pipeline's uint8 outputs [B, T', H', W', 3] to the source's [B, T, H, W, 3] with the same filter -
-the torch backend again the specification, on a GPU one launch of drn_restore_frames_u8 (csrc/restore.hip).
+the torch backend again the specification, on a GPU one launch of drn_restore_frames_u8 (csrc/restore.hip).  The three kernels share csrc/resample_core.h.
 """
 import math
 from dataclasses import dataclass

@@ -116,6 +116,30 @@ def grid(geometries=None):
                 yield gi, B, T
 
 
+def scattered_rows(Hs=120, Ws=40, Hd=16, Wd=32):
+    """Tables no resize produces, for the kernels' chunk cutter: output rows read 2 source rows alternately near the top
+    (0..7) and near the bottom (100..107) of the source, so no two consecutive output rows fit a 48-row stage together and a tile
+    is cut into one chunk per row.  All weights are dyadic.  -> (a plan of the five tables, the dense float64 [Hd, Hs] and
+    [Wd, Ws] matrices of the row and column tables)."""
+    i = torch.arange(Hd)
+    plan = type("P", (), {})()
+    plan.T_out, plan.H_out, plan.W_out = 3, Hd, Wd
+    plan.t_idx = torch.tensor([1, 0, 1], dtype=torch.int32)
+    plan.y_lo_n = torch.stack([i // 2 + 100 * (i % 2), torch.full((Hd,), 2)], 1).to(torch.int32)
+    plan.y_w = torch.tensor([[0.25, 0.75]], dtype=torch.float32).repeat(Hd, 1)
+    plan.x_lo_n = torch.stack([torch.arange(Wd), torch.full((Wd,), 3)], 1).to(torch.int32)
+    plan.x_w = torch.tensor([[0.5, 0.125, 0.375]], dtype=torch.float32).repeat(Wd, 1)
+    assert int(plan.y_lo_n[:, 0].max()) + 2 <= Hs and Wd + 2 <= Ws
+    assert all(abs(int(plan.y_lo_n[r + 1, 0]) - int(plan.y_lo_n[r, 0])) + 2 > 48 for r in range(Hd - 1))
+    dense = []
+    for lo_n, w, n_in in ((plan.y_lo_n, plan.y_w, Hs), (plan.x_lo_n, plan.x_w, Ws)):
+        m = torch.zeros(lo_n.shape[0], n_in, dtype=torch.float64)
+        for r, (lo, n) in enumerate(lo_n.tolist()):
+            m[r, lo:lo + n] = w[r, :n].double()
+        dense.append(m)
+    return plan, dense[0], dense[1]
+
+
 # ----------------------------------------------------------------------------------------------- wrong stand-ins
 def _shift_lo(m):
     """Every row's taps one source sample later (the last column's weight falls off the end)."""

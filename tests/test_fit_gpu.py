@@ -1,6 +1,7 @@
-"""drn_fit_frames (csrc/fit.hip) on the GPU: the kernel against the float64 reference under the bound of tests/fit_refs.py
-(whose wrong stand-ins tests/test_fit_cpu.py shows to miss it), bit for bit against today's ingest at scale 1, its argument
-checks, and both renderer nodes with fit against the composition done by hand."""
+"""drn_fit_frames (the fp32 instantiation of csrc/fit.hip's kernel, on csrc/resample_core.h) on the GPU: the kernel against the
+float64 reference under the bound of tests/fit_refs.py (whose wrong stand-ins tests/test_fit_cpu.py shows to miss it), bit for bit
+against today's ingest at scale 1, bit for bit where a tile is cut into one chunk per row, its argument checks, and both renderer
+nodes with fit against the composition done by hand."""
 import importlib
 
 import numpy as np
@@ -63,6 +64,19 @@ def test_kernel_source_off_a_16_byte_boundary(pkg, gpu):
         shifted = flat[1:].view(src.shape)
         assert shifted.data_ptr() % 16 == 4
         assert torch.equal(_launch(pkg, gpu, shifted, c["plan"]), _launch(pkg, gpu, src, c["plan"]))
+
+
+def test_scattered_row_taps_cut_a_tile_into_one_chunk_per_row(pkg, gpu):
+    """No two consecutive output rows fit the stage together (fit_refs.scattered_rows), so the 16-row tile is 16 chunks.  Source
+    values are multiples of 1/256 and all weights dyadic: every fp32 product and sum is exact, the only rounding on either side is
+    the last one to bf16, and the float64 evaluation is the kernel's result bit for bit."""
+    plan, my, mx = R.scattered_rows()
+    g = torch.Generator().manual_seed(20261019)
+    src = torch.randint(0, 257, (1, 2, 120, 40, 3), generator=g).float() / 256.0
+    want = R.apply64(src, my, mx, plan.t_idx.long()) * 2.0 - 1.0
+    assert want.shape == (1, 3, 3, 16, 32) and torch.equal(want.float().double(), want)       # exact in fp32 before the rounding
+    got = _launch(pkg, gpu, src.to(gpu), plan)
+    assert torch.equal(got, want.float().to(BF))
 
 
 def test_kernel_argument_checks(pkg, gpu):

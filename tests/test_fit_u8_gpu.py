@@ -1,6 +1,7 @@
-"""drn_fit_frames_u8 (csrc/fit_u8.hip) on the GPU: bit for bit the unchanged fp32 kernel on u8_unit(src) at every geometry, within
-the float64 bound of tests/fit_refs.py (whose uint8 inputs tests/test_fit_u8_cpu.py shows to catch the wrong stand-ins), bit for
-bit today's host chain at scale 1, a source at every byte alignment, its argument checks, and fit.fit_frames on uint8."""
+"""drn_fit_frames_u8 (the uint8 instantiation of csrc/fit.hip's kernel) on the GPU: bit for bit the fp32 kernel on u8_unit(src) at
+every geometry, within the float64 bound of tests/fit_refs.py (whose uint8 inputs tests/test_fit_u8_cpu.py shows to catch the wrong
+stand-ins), bit for bit today's host chain at scale 1, a source at every byte alignment, spans beyond the raw buffer, a tile cut
+into one chunk per row, its argument checks, and fit.fit_frames on uint8."""
 import numpy as np
 import pytest
 import torch
@@ -85,6 +86,17 @@ def test_kernel_spans_beyond_the_raw_buffer(pkg, gpu, Ws):
     plan.y_w = torch.tensor([[0.25, 0.75]], dtype=torch.float32).repeat(Hd, 1)
     plan.x_lo_n = torch.stack([torch.where(x % 2 == 0, x, Ws - 3 - x), torch.full((Wd,), 3)], 1).to(torch.int32)
     plan.x_w = torch.tensor([[0.5, 0.125, 0.375]], dtype=torch.float32).repeat(Wd, 1)
+    for off in (0, 3):
+        dev = _at_offset(src, off, gpu)
+        assert torch.equal(_launch(pkg, gpu, dev, plan), _launch(pkg, gpu, fit.u8_unit(dev), plan, fn="fit_frames"))
+
+
+def test_scattered_row_taps_cut_a_tile_into_one_chunk_per_row(pkg, gpu):
+    """No two consecutive output rows fit the stage together (fit_refs.scattered_rows): one chunk, and one raw pass, per output
+    row.  Still the fp32 kernel's bits."""
+    fit = R.fit_module(pkg)
+    plan = R.scattered_rows()[0]
+    src = U.source_u8(1, 2, 120, 40, seed=32)
     for off in (0, 3):
         dev = _at_offset(src, off, gpu)
         assert torch.equal(_launch(pkg, gpu, dev, plan), _launch(pkg, gpu, fit.u8_unit(dev), plan, fn="fit_frames"))

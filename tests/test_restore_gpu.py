@@ -1,12 +1,14 @@
-"""drn_restore_frames_u8 (csrc/restore.hip) on the GPU: the kernel against the float64 reference under the bound of
-tests/restore_refs.py (whose wrong stand-ins tests/test_restore_cpu.py shows to miss it), bit for bit where the weights are dyadic,
-flat frames, every byte alignment of src and dst, its argument checks, the dispatch of fit.restore_frames, and both renderer nodes
-with `fit_restore` against the composition done by hand.  Every launch writes into a guard-banded buffer and is issued twice."""
+"""drn_restore_frames_u8 (csrc/restore.hip, on csrc/resample_core.h) on the GPU: the kernel against the float64 reference under
+the bound of tests/restore_refs.py (whose wrong stand-ins tests/test_restore_cpu.py shows to miss it), bit for bit where the weights
+are dyadic, flat frames, every byte alignment of src and dst, scattered column and row taps, its argument checks, the dispatch of
+fit.restore_frames, and both renderer nodes with `fit_restore` against the composition done by hand.  Every launch writes into a
+guard-banded buffer and is issued twice."""
 import pytest
 import torch
 
 import restore_refs as R
 from conftest import tiny_net
+from fit_refs import scattered_rows
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -123,6 +125,16 @@ def test_scattered_taps_read_the_source_directly(pkg, gpu):
     host = buf.cpu()
     assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + n:] == SENTINEL).all()
     assert torch.equal(host[GUARD:GUARD + n].view(1, 1, Hd, Wd, 3), want)
+
+
+def test_scattered_row_taps_cut_a_tile_into_one_chunk_per_row(pkg, gpu):
+    """No grid case has a tile whose source rows overflow the stage (its 32 rows at most).  Here no two consecutive output rows
+    fit it together (fit_refs.scattered_rows): the 16-row tile is 16 chunks.  Dyadic weights: exact, ties real, bit for bit."""
+    rplan, my, mx = scattered_rows()
+    rplan.T, rplan.H, rplan.W = 2, 16, 32
+    src = R.source(2, 3, 120, 40, seed=78)
+    got = _launch(pkg, gpu, src.to(gpu), rplan)
+    assert torch.equal(got, R.round_u8(R.apply64(src, my, mx, 2)))
 
 
 def test_kernel_argument_checks(pkg, gpu):
