@@ -20,7 +20,7 @@ from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
 from .fit import restore_frames
 from .model_diffusion_renderer import CleanDiffusionRendererModel
-from .tiles import blend_tile, plan_tiles
+from .tiles import blend_tile, latent_tile, plan_tiles
 from .windows import Window, plan_windows, ramp_weights
 
 _SHAPE_KEYS = ("rgb", "image", "basecolor", "normal", "depth", "roughness", "metallic")
@@ -55,6 +55,10 @@ class CleanDiffusionRendererPipeline:
         self.tile_height = 0
         self.tile_width = 0
         self.tile_overlap = 64
+        # how tiles are joined: "pixel" = independent samples, cross-faded as uint8 (above); "latent" = joint
+        # sampling: ONE noisy latent canvas for the picture, every tile's Euler step cross-faded into it at every step, so that
+        # neighbours agree; needs tile_overlap on the tokenizer's 8-grid and a canvas-shaped init_noise
+        self.tile_join = "pixel"
         self.device = torch.device("cuda")     # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
@@ -232,7 +236,15 @@ class CleanDiffusionRendererPipeline:
         windows, carries and passes as they are, same seed, same start noise: every tile has one shape -, and each result is
         cross-faded into that pass's full-size canvas (tiles.blend_tile).  After the last tile the restore plan is applied once
         per canvas (it also cuts the time padding), then the copy to the host.  Device memory: one full-size uint8 canvas per
-        pass plus one tile's results."""
+        pass plus one tile's results.
+
+        tile_join = "latent"  changes where the tiles' samples come from and nothing behind them: `_joint_samples`
+        denoises all tiles of every window together on one latent canvas, and the same walk then decodes each tile's crop of
+        the final canvases instead of sampling - post-process, carries and the pixel cross-fade as above, because the decoder
+        sees each tile's own context.  At tile_overlap = 0 there is nothing to join: "latent" is then the hard-cut tiling above
+        with each tile started from its crop of the canvas noise (`_tile_noises`)."""
+        if self.tile_join not in ("pixel", "latent"):
+            raise ValueError(f"tile_join must be 'pixel' or 'latent', got {self.tile_join!r}")
         if not batches:
             return []
         tiles = self._tile_plan(batches[0])
@@ -240,18 +252,30 @@ class CleanDiffusionRendererPipeline:
             return self._walk(batches, flags, seed, init_noise, clips, to_host)
         H, W = self._shape_tensor(batches[0]).shape[3:5]
         canvas = None
+        # tile_join = "latent": the tiles are sampled jointly first; the walk then decodes each tile's crop of the final canvases.
+        # Without an overlap the tiles share no latent: each is sampled on its own, from its crop of the ONE canvas noise
+        joint = noises = None
+        if self.tile_join == "latent":
+            if self.tile_overlap:
+                joint = self._joint_samples(batches, tiles, seed, init_noise)
+            else:
+                noises = self._tile_noises(batches, tiles, seed, init_noise)
         rplan, self.restore_plan = self.restore_plan, None         # the way back runs once, on the joined picture
         try:
-            for tile in tiles:
-                cropped = {}
+            for n, tile in enumerate(tiles):
+                if joint is not None:
+                    outs = self._walk(batches, flags, seed, None, clips, False, provider=joint(n))
+                else:
+                    cropped = {}
 
-                def crop(v):
-                    if not (isinstance(v, torch.Tensor) and v.ndim == 5 and tuple(v.shape[3:5]) == (H, W)):
-                        return v
-                    if id(v) not in cropped:
-                        cropped[id(v)] = (v, v[..., tile.y:tile.y + tile.h, tile.x:tile.x + tile.w].contiguous())
-                    return cropped[id(v)][1]
-                outs = self._walk([{k: crop(v) for k, v in b.items()} for b in batches], flags, seed, init_noise, clips, False)
+                    def crop(v):
+                        if not (isinstance(v, torch.Tensor) and v.ndim == 5 and tuple(v.shape[3:5]) == (H, W)):
+                            return v
+                        if id(v) not in cropped:
+                            cropped[id(v)] = (v, v[..., tile.y:tile.y + tile.h, tile.x:tile.x + tile.w].contiguous())
+                        return cropped[id(v)][1]
+                    outs = self._walk([{k: crop(v) for k, v in b.items()} for b in batches], flags, seed,
+                                      init_noise if noises is None else noises[n], clips, False)
                 if canvas is None:
                     canvas = [[torch.empty(tuple(o.shape[:2]) + (H, W, 3), dtype=torch.uint8, device=o.device) for o in per_batch]
                               for per_batch in outs]
@@ -263,7 +287,86 @@ class CleanDiffusionRendererPipeline:
         done = [[self._restored(c) for c in cs] for cs in canvas]
         return [[c.cpu().numpy() if to_host else c for c in cs] for cs in done]
 
-    def _walk(self, batches, flags, seed, init_noise, clips=False, to_host=True):
+    def _latent_plan(self, batches, tiles):
+        """What tile_join = "latent" needs to know of a tiled picture -> (the clip's windows or None, the frames of one sample,
+        the tiles in latent units, the latent canvas's shape (C, F, H/f, W/f)).  Loads the model for one tile's shape;
+        ValueError for a tile_overlap off the tokenizer's grid."""
+        ref = self._shape_tensor(batches[0])
+        T, H, W = ref.shape[2:5]
+        plan = self._window_plan(batches[0])
+        Wf = T if plan is None else int(self.window_frames)
+        self._ensure_model_loaded((ref.shape[0], ref.shape[1], Wf, tiles[0].h, tiles[0].w))
+        f = int(getattr(self.model.vae if getattr(self.model, "vae", None) is not None else self.vae_instance,
+                        "spatial_compression_factor", 8))
+        if self.tile_overlap % f:
+            raise ValueError(f"tile_join = 'latent' needs tile_overlap on the tokenizer's grid (a multiple of {f}), got "
+                             f"{self.tile_overlap}: one latent pixel must be the same {f} x {f} pixels in every tile")
+        lat = [latent_tile(t, f) for t in tiles]                   # (H and W off the grid are refused here)
+        return plan, Wf, lat, (self.config["latent_shape"][0], (Wf - 1) // 8 + 1, H // f, W // f)
+
+    def _tile_noises(self, batches, tiles, seed, init_noise):
+        """tile_join = "latent" at tile_overlap = 0 -> per tile its start noise: its crop of the ONE canvas noise of the picture
+        (`init_noise`, which must be canvas-shaped, or as the joint loop draws it: the seed, one randn of the canvas shape times
+        sigma_0).  With it the pixel path renders the hard-cut tiling: tiles that share no latent are independent samples,
+        whatever canvas they are cut from.  (The joint loop would not give that where the last row or column of tiles is
+        shifted back: DESIGN.md 4i.)"""
+        _, _, lat, canvas_shape = self._latent_plan(batches, tiles)
+        if init_noise is not None:
+            if tuple(init_noise.shape[-4:]) != canvas_shape:
+                raise ValueError(f"init_noise {tuple(init_noise.shape)} is not canvas-shaped: tile_join = 'latent' starts from ONE "
+                                 f"noise canvas [1 or P, {', '.join(map(str, canvas_shape))}] for the whole picture (a tile-shaped "
+                                 "init_noise belongs to tile_join = 'pixel')")
+            noise = init_noise
+        else:
+            torch.manual_seed(seed if seed is not None else self.seed)
+            self.model.scheduler.set_timesteps(self.num_steps)
+            noise = torch.randn(size=(1, *canvas_shape), **self.model._get_tensor_kwargs()) * self.model.scheduler.sigmas[0]
+        return [noise[..., t.y:t.y + t.h, t.x:t.x + t.w].contiguous() for t in lat]
+
+    def _joint_samples(self, batches, tiles, seed, init_noise):
+        """tile_join = "latent": the joint samples of a tiled picture (model.generate_samples_joint) -> provider_of(n), the sample
+        provider `_walk` takes for tile n: (window i, batch c) -> that tile's crop of the final latent canvas of window i and
+        batch c.  Windows outside (every window starts from the same canvas noise, as every window starts from the same noise
+        without tiles), tiles inside, batches innermost: per window and tile every clip tensor is cut, cropped and uploaded once
+        (rgb / video, and the batches of one clip, share it and so share the encode), the tile's condition latents are built
+        with the model's own `_get_conditions`, and only they are kept - the pixel crops are dropped tile by tile.  Held until
+        the picture is done: one canvas [P, C, F, H/f, W/f] bf16 per window and batch."""
+        plan, Wf, lat, canvas_shape = self._latent_plan(batches, tiles)
+        T, H, W = self._shape_tensor(batches[0]).shape[2:5]
+        starts = [0] if plan is None else [win.start for win in plan]
+        dev = self._resolved(self.device)
+        samples = []
+        for start in starts:
+            conds = [[] for _ in batches]
+            for tile in tiles:
+                parts = {}
+
+                def part(v):
+                    if not isinstance(v, torch.Tensor):
+                        return v
+                    if id(v) not in parts:
+                        p = v
+                        if p.ndim == 5 and tuple(p.shape[3:5]) == (H, W):
+                            p = p[..., tile.y:tile.y + tile.h, tile.x:tile.x + tile.w]
+                        if plan is not None and p.ndim == 5 and p.shape[2] == T:
+                            p = p[:, :, start:start + Wf]
+                        parts[id(v)] = (v, p.contiguous().to(device=dev, dtype=self.dtype))
+                    return parts[id(v)][1]
+                for c, b in enumerate(batches):
+                    tb = {k: part(v) for k, v in b.items()}
+                    self.model._get_conditions(tb)
+                    conds[c].append({k: tb[k] for k in ("latent_condition", "context_index") if k in tb})
+            samples.append([self.model.generate_samples_joint(cs, lat, canvas_shape, guidance=self.guidance,
+                                                              seed=seed if seed is not None else self.seed,
+                                                              num_steps=self.num_steps, init_noise=init_noise) for cs in conds])
+            del conds
+
+        def provider_of(n):
+            t = lat[n]
+            return lambda i, c: samples[i][c][..., t.y:t.y + t.h, t.x:t.x + t.w].contiguous()
+        return provider_of
+
+    def _walk(self, batches, flags, seed, init_noise, clips=False, to_host=True, provider=None):
         """The one walk from batches to uint8 frames -> per batch, per pass: uint8 [B, T, H, W, 3], numpy arrays on the host, or
         with to_host=False torch tensors on the pipeline's device (the same walk: only the buffer the written frames are copied
         into lives there, so what the inverse renderer made can feed the forward renderer without a host round trip).  Walk the clip's
@@ -274,7 +377,9 @@ class CleanDiffusionRendererPipeline:
 
         A clip that is one sequence is one window over the caller's own tensors (the upload cache knows them by identity) that
         writes every frame the tokenizer decoded, with no ramp and no carry.  clips: generate_video's contract for such a clip - the
-        sample's rows are clips under the one flag, decoded together - where otherwise every row is a pass with a flag of its own."""
+        sample's rows are clips under the one flag, decoded together - where otherwise every row is a pass with a flag of its own.
+        provider: (window index, batch index) -> that window's sample, in place of sampling it here (`_joint_samples`); without
+        one the walk is untouched."""
         if not batches:
             return []
         plan = self._window_plan(batches[0])
@@ -298,7 +403,10 @@ class CleanDiffusionRendererPipeline:
                     sliced[id(v)] = (v, v[:, :, win.start:win.start + Wf].contiguous())
                 return sliced[id(v)][1]
             for c, (batch, fl) in enumerate(zip(batches, flags)):
-                sample = self._sample(batch if whole else {k: cut(v) for k, v in batch.items()}, seed, init_noise)
+                if provider is not None:        # sampled already (tile_join = "latent"): window i's sample of batch c
+                    sample = provider(i, c)
+                else:
+                    sample = self._sample(batch if whole else {k: cut(v) for k, v in batch.items()}, seed, init_noise)
                 if not together and sample.shape[0] != len(fl):
                     raise ValueError(f"{len(fl)} normalize_normal flags for {sample.shape[0]} passes")
                 for p, flag in enumerate(fl):

@@ -43,17 +43,23 @@ class CleanEDMEulerScheduler:
         c_in = 1 / torch.sqrt(self._sigma(timestep) ** 2 + self.sigma_data ** 2)
         return N.edm_scale_input(sample.contiguous(), float(c_in))
 
-    def step(self, model_output, timestep, sample):
+    def step_scalars(self, timestep):
+        """(c_in, c_skip, c_out, sigma, dt) of the step at `timestep`, the scheduler's current one, as host floats: the fp32 torch
+        expressions of scale_model_input and step (reference :30-82), evaluated once.  Does not advance the scheduler."""
         if self.sigmas is None or self.current_step >= len(self.sigmas) - 1:
             raise RuntimeError("Scheduler not initialized or timesteps exhausted")
         sigma = self._sigma(timestep)
         sigma_next = self.sigmas[self.current_step + 1]
         sd = self.sigma_data
+        c_in = 1 / torch.sqrt(sigma ** 2 + sd ** 2)
         c_skip = sd ** 2 / (sigma ** 2 + sd ** 2)
         c_out = (sigma * sd) / torch.sqrt(sigma ** 2 + sd ** 2)
         dt = sigma_next - sigma
-        prev = N.edm_step(model_output.contiguous(), sample.contiguous(), float(c_skip), float(c_out), float(sigma),
-                          float(dt))
+        return float(c_in), float(c_skip), float(c_out), float(sigma), float(dt)
+
+    def step(self, model_output, timestep, sample):
+        _, c_skip, c_out, sigma, dt = self.step_scalars(timestep)
+        prev = N.edm_step(model_output.contiguous(), sample.contiguous(), c_skip, c_out, sigma, dt)
         self.current_step += 1
 
         class StepResult:
@@ -285,3 +291,80 @@ class CleanDiffusionRendererModel:
                     net_output = self.net(x=xt_scaled, timesteps=t, latent_condition=lat, context_index=idx)
                 xt = self.scheduler.step(net_output, t, xt).prev_sample
             return xt
+
+    def generate_samples_joint(self, tile_batches, tiles_lat, canvas_shape: Tuple, guidance: float = 0.0, seed: int = 1000,
+                               num_steps: int = 15, init_noise: Tensor = None) -> Tensor:
+        """The denoising loop over the spatial tiles of ONE picture, joined in latent space at every step (tiles.py, DESIGN.md
+        4i): one noisy canvas [P, *canvas_shape] exists for the whole picture; per Euler step every tile, in raster order, takes
+        its crop of the current canvas through the DiT exactly as generate_samples_from_batch would, and its step result is
+        cross-faded into the next canvas (tiles.latent_gather / latent_step_join: one HIP launch each).  -> the final canvas.
+
+        tile_batches: per tile the data batch of its crop (a batch that already holds its `latent_condition` is taken as it is;
+        only the condition latents and the context indices are kept).  tiles_lat: the tiles in latent units (tiles.latent_tile),
+        whose written rectangles must cover the canvas.  canvas_shape: (C, F, Hc, Wc).  init_noise (already scaled by sigma_0)
+        must be canvas-shaped.  Seed, P passes stepped together, CFG and the errors are generate_samples_from_batch's."""
+        from . import tiles as T
+        if self.net is None:
+            raise RuntimeError("weights not loaded: call load_state_dict() first")
+        tile_batches, tiles_lat, canvas_shape = list(tile_batches), list(tiles_lat), tuple(int(v) for v in canvas_shape)
+        if not tiles_lat or len(tile_batches) != len(tiles_lat):
+            raise ValueError(f"{len(tile_batches)} tile batches for {len(tiles_lat)} tiles")
+        if len(canvas_shape) != 4:
+            raise ValueError(f"canvas_shape is (C, F, Hc, Wc), got {canvas_shape}")
+        if not T.covers(tiles_lat, *canvas_shape[2:]):
+            raise ValueError(f"the tiles do not write every latent of a {canvas_shape[2:]} canvas")
+        with torch.no_grad():
+            torch.manual_seed(seed)
+            conds = []
+            for b in tile_batches:
+                if "latent_condition" in b:
+                    condition, _ = self.conditioner.get_condition_uncondition(b)
+                else:
+                    condition, _ = self._get_conditions(b)
+                conds.append(condition.to_dict())
+            self.scheduler.set_timesteps(num_steps)
+            self.net.prepare_timesteps([float(t) for t in self.scheduler.timesteps])   # all AdaLN vectors, one batched pass
+            if init_noise is not None:
+                if tuple(init_noise.shape[-4:]) != canvas_shape:
+                    raise ValueError(f"init_noise {tuple(init_noise.shape)} is not canvas-shaped: a latent-space join starts "
+                                     f"from ONE noise canvas [1 or P, {', '.join(map(str, canvas_shape))}] for the whole picture "
+                                     "(a tile-shaped init_noise belongs to tile_join = 'pixel')")
+                cur = init_noise.to(**self._get_tensor_kwargs()).contiguous()
+            else:
+                cur = torch.randn(size=(1, *canvas_shape), **self._get_tensor_kwargs()) * self.scheduler.sigmas[0]
+            cis = [0]
+            if "context_index" in conds[0]:
+                cis = [int(v) for v in conds[0]["context_index"].flatten().tolist()]
+            P = len(cis)
+            # (a canvas of the caller's is never written: both buffers are this call's own)
+            cur = cur.expand(P, *cur.shape[1:]).contiguous() if cur.shape[0] == 1 and P > 1 else cur.clone()
+            if cur.shape[0] != P:
+                raise ValueError(f"{P} context indices for a latent batch of {cur.shape[0]}")
+            idx = cis + [0] * P if guidance > 0 else cis
+            lats = []
+            for cond, tl in zip(conds, tiles_lat):
+                if "context_index" in cond and [int(v) for v in cond["context_index"].flatten().tolist()] != cis:
+                    raise ValueError("the tiles of one picture are rendered under one set of context indices")
+                lat_c = cond["latent_condition"]
+                if lat_c.shape[0] != 1:
+                    raise ValueError("the renderer runs one clip per call (noise is drawn with batch 1)")
+                if tuple(lat_c.shape[2:]) != (canvas_shape[1], tl.h, tl.w):
+                    raise ValueError(f"a condition latent of {tuple(lat_c.shape[2:])} for {tl} of a canvas {canvas_shape}")
+                if P > 1:
+                    lat_c = lat_c.expand(P, *lat_c.shape[1:])
+                # cond and uncond halves as one batch of 2P clips, as in generate_samples_from_batch
+                lats.append(torch.cat([lat_c, torch.zeros_like(lat_c)], 0) if guidance > 0 else lat_c)
+            del conds
+            nxt = torch.empty_like(cur)
+            for t in self.scheduler.timesteps:
+                c_in, c_skip, c_out, sigma, dt = self.scheduler.step_scalars(t)
+                for lat, tl in zip(lats, tiles_lat):
+                    xs = T.latent_gather(cur, tl, c_in, copies=2 if guidance > 0 else 1)
+                    out = self.net(x=xs, timesteps=t, latent_condition=lat, context_index=idx)
+                    if guidance > 0:
+                        T.latent_step_join(out[:P], out[P:], float(guidance), cur, nxt, tl, c_skip, c_out, sigma, dt)
+                    else:
+                        T.latent_step_join(out, None, 0.0, cur, nxt, tl, c_skip, c_out, sigma, dt)
+                cur, nxt = nxt, cur            # every latent of the new canvas has been written: the tiles cover it
+                self.scheduler.current_step += 1
+            return cur

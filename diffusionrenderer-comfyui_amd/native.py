@@ -119,6 +119,8 @@ SIGNATURES = {
     "drn_fit_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_restore_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
     "drn_tile_blend_u8": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "drn_latent_tile_gather": [_P, _P, _L, _I, _I, _I, _I, _I, _I, _F, _I, _P],
+    "drn_latent_tile_step_join": [_P, _P, _F, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
 }
 _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_bytes": c_int64,
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
@@ -943,6 +945,48 @@ def tile_blend_u8(canvas, tile, wy, wx, y_at: int, x_at: int, ry: int, rx: int):
     _check(load_library().drn_tile_blend_u8(_ptr(canvas), _ptr(tile), _ptr(wy), _ptr(wx), B * T, H, W, h, w, y_at, x_at, ry, rx,
                                             O[0], O[1], _stream()), "drn_tile_blend_u8")
     return canvas
+
+
+def _latent_canvas(name, t):
+    _bf16(t)
+    assert t.ndim >= 3 and t.is_contiguous(), f"{name}: a contiguous bf16 [..., H, W] tensor required"
+    return t.numel() // (t.shape[-2] * t.shape[-1]), t.shape[-2], t.shape[-1]
+
+
+def latent_tile_gather(canvas, h: int, w: int, y_at: int, x_at: int, c_in: float, copies: int = 1):
+    """One tile's crop of the latent canvas as the DiT's input (drn_latent_tile_gather; the plan: tiles.latent_tile).  canvas
+    [P, C, F, Hc, Wc] bf16 on the device, contiguous -> [copies * P, C, F, h, w] bf16 = edm_scale_input of the crop at
+    (y_at, x_at), `copies` (1, or 2 under CFG) times along the batch."""
+    planes, Hc, Wc = _latent_canvas("canvas", canvas)
+    out = torch.empty((copies * canvas.shape[0], *canvas.shape[1:-2], h, w), dtype=torch.bfloat16, device=canvas.device)
+    _check(load_library().drn_latent_tile_gather(_ptr(canvas), _ptr(out), planes, Hc, Wc, h, w, y_at, x_at, c_in, copies, _stream()),
+           "drn_latent_tile_gather")
+    return out
+
+
+def latent_tile_step_join(model_out, uncond, guidance: float, canvas_cur, canvas_next, wy, wx, y_at: int, x_at: int, ry: int,
+                          rx: int, c_skip: float, c_out: float, sigma: float, dt: float):
+    """CFG combine, Euler step and cross-fade of one tile's DiT output into the next latent canvas, in place
+    (drn_latent_tile_step_join; the specification: tiles.latent_step_join).  model_out (and uncond, or None for no CFG)
+    [P, C, F, h, w], canvas_cur and canvas_next [P, C, F, Hc, Wc], all bf16 on one device, contiguous; the tile's rows from ry and
+    columns from rx on land at (y_at + ry, x_at + rx), the first len(wy) written rows and len(wx) written columns cross-faded over
+    what canvas_next holds.  wy / wx: fp32 ramp weights on the device, or None for no ramp on that axis.  Returns canvas_next."""
+    planes, Hc, Wc = _latent_canvas("canvas_cur", canvas_cur)
+    assert _latent_canvas("canvas_next", canvas_next) == (planes, Hc, Wc), "the two canvases have one shape"
+    tp, h, w = _latent_canvas("model_out", model_out)
+    assert tp == planes, "tile and canvas have the same planes"
+    if uncond is not None:
+        assert _latent_canvas("uncond", uncond) == (planes, h, w), "uncond has the tile's shape"
+    O = []
+    for name, t in (("wy", wy), ("wx", wx)):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.ndim == 1 and t.numel() > 0 and t.is_contiguous() and t.device == canvas_cur.device, \
+                f"{name}: a non-empty contiguous fp32 vector on the canvas's device, or None"
+        O.append(0 if t is None else t.numel())
+    _check(load_library().drn_latent_tile_step_join(_ptr(model_out), _ptr(uncond), guidance, _ptr(canvas_cur), _ptr(canvas_next),
+                                                    _ptr(wy), _ptr(wx), planes, Hc, Wc, h, w, y_at, x_at, ry, rx, O[0], O[1], c_skip,
+                                                    c_out, sigma, dt, _stream()), "drn_latent_tile_step_join")
+    return canvas_next
 
 
 def dit_forward(args: "DitForwardArgs"):

@@ -52,7 +52,16 @@ def _tile_inputs():
                                               "recommended, with tile_height 576)"}),
             "tile_overlap": ("INT", {"default": 64, "min": 0, "max": 2048, "step": 1,
                                      "tooltip": "rows / columns two neighbouring tiles share (at most half the tile's side); "
-                                                "0 = hard cuts"})}
+                                                "0 = hard cuts"}),
+            "tile_join": (["pixel", "latent"],
+                          {"default": "pixel",
+                           "tooltip": "pixel: every tile is a sample of its own, joined as 8-bit pictures (above).  latent: the "
+                                      "tiles are denoised together on ONE noisy latent canvas for the whole picture - at every "
+                                      "step each tile's result is cross-faded into the canvas its neighbours read next, so that "
+                                      "neighbouring tiles agree instead of only fading into each other; the pictures are still "
+                                      "decoded tile by tile and cross-faded.  Costs: one latent canvas per window and pass held "
+                                      "on the GPU (41 MB for five passes of 57 x 1072 x 1920), the same DiT calls, and "
+                                      "tile_overlap must be a multiple of 8 (the tokenizer's grid; the default 64 is)"})}
 
 
 def _fit_inputs():
@@ -93,15 +102,16 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
     raise TypeError(f"Unsupported input type for '{name}': {type(image)}. Expected torch.Tensor or list of Tensors.")
 
 
-def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64)):
+def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel"):
     """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
-    (tile_height, tile_width, tile_overlap)."""
+    (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent")."""
     pipeline.set_model_type(model_type)
     pipeline.guidance = guidance
     pipeline.seed = seed
     pipeline.window_frames = window_frames
     pipeline.window_overlap = window_overlap
     pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
+    pipeline.tile_join = tile_join
     pipeline.restore_plan = None
 
 
@@ -139,11 +149,11 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                    to_host=True, tiles=(0, 0, 64)):
+                    to_host=True, tiles=(0, 0, 64), tile_join="pixel"):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
-    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles)
+    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     image_tensor = clips["image"]
     keep = plan.T if plan is not None else None
@@ -172,10 +182,10 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
                   env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
-                  tiles=(0, 0, 64)):
+                  tiles=(0, 0, 64), tile_join="pixel"):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
     (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit)."""
-    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles)
+    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
     # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
@@ -269,9 +279,10 @@ class Cosmos1InverseRenderer:
     CATEGORY = "Cosmos1"
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
-                         fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64):
+                         fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
+                         tile_join="pixel"):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
-                                        fit_restore, tiles=(tile_height, tile_width, tile_overlap))
+                                        fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -305,11 +316,11 @@ class Cosmos1ForwardRenderer:
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
-                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64):
+                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel"):
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
                               env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                              tiles=(tile_height, tile_width, tile_overlap)),)
+                              tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join),)
 
 
 class LoadHDRImage:
@@ -362,8 +373,8 @@ class Cosmos1Relight:
     def run_relight(self, inverse_pipeline, forward_pipeline, image, env_map, guidance=0.0, forward_guidance=0.0, seed=42,
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
-                    tile_height=0, tile_width=0, tile_overlap=64):
-        """Tiles apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...})."""
+                    tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel"):
+        """Tiles, and the way they are joined, apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...})."""
         from .fit import plan_fit, plan_restore, restore_frames
         tiles = (tile_height, tile_width, tile_overlap)
         rplan = None
@@ -372,7 +383,7 @@ class Cosmos1Relight:
             rplan = plan_restore(plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames))
         # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
-                                        fit_width, False, to_host=False, tiles=tiles)
+                                        fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's
@@ -381,7 +392,7 @@ class Cosmos1Relight:
         inputs = {k: inputs[k] for k in ("depth", "normal", "roughness", "metallic", "base_color")}
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
-                              restore_plan=rplan, tiles=tiles)
+                              restore_plan=rplan, tiles=tiles, tile_join=tile_join)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:

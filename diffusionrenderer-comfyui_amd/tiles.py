@@ -10,6 +10,13 @@ not conditioned on each other, so two tiles may disagree, and the cross-fade hid
 
 `blend_tile`'s torch backend is the specification and what CPU devices run; on a GPU one launch of drn_tile_blend_u8
 (csrc/tile_blend.hip) does it.
+
+That is the pipeline's `tile_join = "pixel"`.  With `tile_join = "latent"` the tiles are sampled JOINTLY instead:
+one noisy latent canvas exists for the whole picture, at every Euler step each tile takes its crop of it through the DiT
+(`latent_gather`) and its step result is cross-faded into the next canvas (`latent_step_join`: this file's blend rule on bf16),
+so neighbouring tiles agree.  It rests on the tiles lying on the tokenizer's grid (`latent_tile`) and covering the canvas
+(`covers`); the final canvas is decoded tile by tile and joined in pixel space as above.  Again the torch backends are the
+specification, and on a GPU each is one launch (csrc/latent_tiles.hip).
 """
 from typing import List, NamedTuple, Optional
 
@@ -90,8 +97,129 @@ def plan_tiles(H: int, W: int, tile_h: int, tile_w: int, overlap: int) -> Option
             for i, sy in enumerate(ys) for j, sx in enumerate(xs)]
 
 
+def latent_tile(t: Tile, f: int) -> Tile:
+    """`t` in latent units: every field divided by the tokenizer's spatial compression factor `f`.  One latent
+    pixel is the same f x f pixels in every tile only where the tile's corner, written range and ramps lie on the f-grid, so a
+    field off it is refused."""
+    f = _int("f", f)
+    if f < 1:
+        raise ValueError(f"the compression factor is at least 1, got {f}")
+    for name, v in zip(Tile._fields, t):
+        if _int(name, v) % f:
+            raise ValueError(f"{t}: {name} = {v} is off the latent grid of {f} (tile_overlap and the picture's sides must be "
+                             f"multiples of {f} for a latent-space join)")
+    return Tile(*(int(v) // f for v in t))
+
+
+def covers(tiles: List[Tile], H: int, W: int) -> bool:
+    """Whether the written rectangles of `tiles` cover every sample of an H x W canvas: what lets the latent join swap its two
+    canvases after the last tile without clearing one."""
+    seen = np.zeros((H, W), dtype=bool)
+    for t in tiles:
+        seen[t.y + t.ry:t.y + t.h, t.x + t.rx:t.x + t.w] = True
+    return bool(seen.all())
+
+
 def _weights(O: int, device):
     return torch.from_numpy(ramp_weights(O)).to(device) if O else None
+
+
+def _check_latent(name, x, like=None):
+    if x.dtype != torch.bfloat16 or x.ndim != 5:
+        raise ValueError(f"{name}: bf16 [P, C, F, H, W] latents needed, got {x.dtype} {tuple(x.shape)}")
+    if like is not None and (x.device != like.device or tuple(x.shape[:3]) != tuple(like.shape[:3])):
+        raise ValueError(f"{name} {tuple(x.shape)} on {x.device} and the canvas {tuple(like.shape)} on {like.device} are not one "
+                         "sample on one device")
+
+
+def _torch_path(backend, x):
+    if backend not in ("auto", "torch", "hip"):
+        raise ValueError(f"unknown backend {backend!r}")
+    if backend == "hip" and not x.is_cuda:
+        raise ValueError(f"backend='hip' needs a GPU tensor, got one on {x.device} (the torch path is what CPU devices run)")
+    return backend == "torch" or not x.is_cuda
+
+
+def latent_gather(canvas: torch.Tensor, t: Tile, c_in: float, copies: int = 1, backend: str = "auto") -> torch.Tensor:
+    """The DiT's input for one tile: the crop of the latent canvas bf16 [P, C, F, Hc, Wc] at `t` (latent units), scaled by c_in
+    in fp32 and rounded to bf16 - edm_scale_input of the contiguous crop -, `copies` (1, or 2 under CFG) times along the batch.
+    backend as for blend_tile; the HIP path is one launch of drn_latent_tile_gather."""
+    _check_latent("canvas", canvas)
+    if copies not in (1, 2):
+        raise ValueError(f"copies must be 1 or 2, got {copies}")
+    Hc, Wc = canvas.shape[3:5]
+    if t.y < 0 or t.x < 0 or t.h < 1 or t.w < 1 or t.y + t.h > Hc or t.x + t.w > Wc:
+        raise ValueError(f"{t} does not lie inside a canvas of {(Hc, Wc)}")
+    if _torch_path(backend, canvas):
+        one = (canvas[..., t.y:t.y + t.h, t.x:t.x + t.w].float() * c_in).to(torch.bfloat16)
+        return torch.cat([one] * copies, 0).contiguous()
+    if not canvas.is_contiguous():
+        raise ValueError("the HIP path gathers from a contiguous canvas")
+    from . import native
+    return native.latent_tile_gather(canvas, t.h, t.w, t.y, t.x, float(c_in), copies)
+
+
+def _step_join_torch(model_out, uncond, guidance, cur, nxt, t: Tile, wy, wx, c_skip, c_out, sigma, dt):
+    """The specification, on slices.  m = the CFG combine of cfg_kernel (two bf16 roundings inside, one outside) or the model's
+    output; b = edm_step_kernel's update of the CURRENT canvas, rounded to bf16; then _blend_torch's rule on bf16: nxt <- b where
+    wgt == 1 (nxt is not read there), else bf16(a + wgt * (b - a)) in three fp32 operations."""
+    bf = torch.bfloat16
+    ys, xs = slice(t.y + t.ry, t.y + t.h), slice(t.x + t.rx, t.x + t.w)
+    m = model_out[..., t.ry:, t.rx:].float()
+    if uncond is not None:
+        d = (m - uncond[..., t.ry:, t.rx:].float()).to(bf).float()
+        gd = (d * float(guidance)).to(bf).float()
+        m = (m + gd).to(bf).float()
+    sm = cur[..., ys, xs].float()
+    denoised = sm * float(c_skip) + m * float(c_out)
+    deriv = (sm - denoised) / torch.tensor(float(sigma), dtype=torch.float32, device=sm.device)     # a true division on any device
+    b = (sm + deriv * float(dt)).to(bf).float()
+    fy = torch.ones(t.h - t.ry, dtype=torch.float32, device=nxt.device)
+    fx = torch.ones(t.w - t.rx, dtype=torch.float32, device=nxt.device)
+    if wy is not None:
+        fy[:t.Oy] = wy
+    if wx is not None:
+        fx[:t.Ox] = wx
+    wgt = fy[:, None] * fx[None, :]
+    a = nxt[..., ys, xs].float()
+    d = b - a
+    mm = wgt * d
+    nxt[..., ys, xs] = torch.where(wgt == 1.0, b, a + mm).to(bf)
+    return nxt
+
+
+def latent_step_join(model_out: torch.Tensor, uncond: Optional[torch.Tensor], guidance: float, canvas_cur: torch.Tensor,
+                     canvas_next: torch.Tensor, t: Tile, c_skip: float, c_out: float, sigma: float, dt: float,
+                     backend: str = "auto") -> torch.Tensor:
+    """One tile's Euler step joined into the NEXT latent canvas, IN PLACE: model_out (and uncond, or None for no CFG) bf16
+    [P, C, F, h, w], the canvases bf16 [P, C, F, Hc, Wc], `t` the tile's entry of plan_tiles in latent units (latent_tile).  The
+    sample is read from canvas_cur, the ramps run over what the tiles above and to the left wrote to canvas_next.  backend as for
+    blend_tile; the HIP path is one launch of drn_latent_tile_step_join.  Returns canvas_next."""
+    _check_latent("canvas_cur", canvas_cur)
+    _check_latent("canvas_next", canvas_next, canvas_cur)
+    _check_latent("model_out", model_out, canvas_cur)
+    if uncond is not None:
+        _check_latent("uncond", uncond, canvas_cur)
+        if tuple(uncond.shape) != tuple(model_out.shape):
+            raise ValueError(f"uncond {tuple(uncond.shape)} is not shaped like model_out {tuple(model_out.shape)}")
+    Hc, Wc = canvas_cur.shape[3:5]
+    if tuple(canvas_next.shape) != tuple(canvas_cur.shape) or canvas_next.data_ptr() == canvas_cur.data_ptr():
+        raise ValueError("the join reads one canvas and writes another of the same shape")
+    if tuple(model_out.shape[3:5]) != (t.h, t.w) or t.y < 0 or t.x < 0 or t.y + t.h > Hc or t.x + t.w > Wc:
+        raise ValueError(f"{t} does not describe a tile of {tuple(model_out.shape[3:5])} inside a canvas of {(Hc, Wc)}")
+    if not (0 <= t.ry < t.h and 0 <= t.rx < t.w and t.Oy >= 0 and t.Ox >= 0 and t.ry + t.Oy <= t.h and t.rx + t.Ox <= t.w):
+        raise ValueError(f"{t}: the written range and its ramps must lie inside the tile")
+    if float(sigma) == 0.0:
+        raise ValueError("sigma must not be 0 (the step divides by it)")
+    wy, wx = _weights(t.Oy, canvas_cur.device), _weights(t.Ox, canvas_cur.device)
+    if _torch_path(backend, canvas_cur):
+        return _step_join_torch(model_out, uncond, guidance, canvas_cur, canvas_next, t, wy, wx, c_skip, c_out, sigma, dt)
+    if not (canvas_cur.is_contiguous() and canvas_next.is_contiguous()):
+        raise ValueError("the HIP path joins contiguous canvases")
+    from . import native
+    return native.latent_tile_step_join(model_out.contiguous(), None if uncond is None else uncond.contiguous(), float(guidance),
+                                        canvas_cur, canvas_next, wy, wx, t.y, t.x, t.ry, t.rx, float(c_skip), float(c_out),
+                                        float(sigma), float(dt))
 
 
 def _blend_torch(canvas, tile, t: Tile, wy, wx):

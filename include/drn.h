@@ -573,6 +573,42 @@ int drn_restore_frames_u8(const uint8_t* src, uint8_t* dst, int B, int Ts, int H
 int drn_tile_blend_u8(void* canvas, const void* tile, const void* wy, const void* wx, int64_t frames, int H, int W, int h, int w,
                       int y_at, int x_at, int ry, int rx, int Oy, int Ox, void* stream);
 
+/* ---- spatial tiles joined in LATENT space (no reference line for the tiling: the reference samples a picture as one sequence;
+ * the arithmetic is the reference sampler's, model_diffusion_renderer.py:30-44 (scale_model_input), :232 (CFG) and :46-82 (step);
+ * plan and torch specification: tiles.py, latent_tile / latent_gather / latent_step_join).  A plane is one
+ * (pass, channel, latent frame); canvas bf16 [planes,Hc,Wc] and tile bf16 [planes,h,w], contiguous, at ANY 2-byte alignment;
+ * x_at, rx, Wc and w may be odd.  Plane bases are 64-bit: a canvas may pass 2^31 elements, one plane of either side may not.
+ *
+ * drn_latent_tile_gather - the tile's crop of the canvas as the DiT's input, ONE launch instead of slice + contiguous +
+ * drn_edm_scale_input (+ torch.cat of the result with itself under CFG):
+ *   out[k][plane][r][c] = bf16(fp32(canvas[plane][y_at + r][x_at + c]) * c_in)      for k < copies, copies 1 or 2
+ * bit for bit edm_scale_input(crop.contiguous()).  Nothing outside `out` is written; the canvas is read at the crop only.
+ * DRN_EINVAL (nothing launched): a null or odd pointer, a size < 1, y_at < 0, x_at < 0, y_at + h > Hc, x_at + w > Wc, copies
+ * outside 1..2, a plane of either side of 2^31 elements or more, more than 2^31 workgroups.
+ *
+ * drn_latent_tile_step_join - CFG combine, Euler step and cross-fade of one tile's DiT output into the NEXT canvas, ONE launch
+ * instead of drn_cfg_combine + drn_edm_step on contiguous crops + a torch blend on slices.  For tile-local y in [ry, h),
+ * x in [rx, w), with c = model_out, u = uncond, sm = canvas_cur and a = canvas_next at that element, as fp32:
+ *   m   = uncond ? bf16(c + bf16(guidance * bf16(c - u))) : c                        (drn_cfg_combine; uncond == NULL: no CFG)
+ *   b   = bf16(sm + ((sm - (c_skip * sm + c_out * m)) / sigma) * dt)                 (drn_edm_step, rounding for rounding)
+ *   wgt = Wy(y - ry) * Wx(x - rx)       (one fp32 multiply; Wy(i) = wy[i] for i < Oy and 1.0f behind, Wx likewise)
+ *   wgt == 1:  canvas_next <- b          (canvas_next is not read)
+ *   else:      canvas_next <- bf16(a + wgt * (b - a))
+ * subtract, multiply and add three separately rounded fp32 operations (never an FMA), rounded to nearest even into bf16:
+ * drn_tile_blend_u8's rule on bf16.  wy fp32 [Oy], wx fp32 [Ox] on the device (windows.ramp_weights); NULL exactly where the
+ * count is 0.  Rows in front of ry and columns in front of rx of the tile are not used.  canvas_cur is only read, and only at
+ * the tile's rectangle; nothing outside [y_at + ry, y_at + h) x [x_at + rx, x_at + w) of canvas_next is written or read.
+ * DRN_EINVAL (nothing launched): a null model_out or canvas, an odd pointer, canvas_cur == canvas_next, a size < 1, a tile
+ * outside the canvas, ry outside [0, h), rx outside [0, w), Oy < 0, Ox < 0, ry + Oy > h, rx + Ox > w, wy == NULL not equivalent
+ * to Oy == 0 (wx and Ox likewise), a weight table not 4-byte aligned, sigma == 0, a plane of either side of 2^31 elements or
+ * more, more than 2^31 workgroups (planes x 16-row x 128-element blocks of the written rectangle). */
+int drn_latent_tile_gather(const void* canvas, void* out, int64_t planes, int Hc, int Wc, int h, int w, int y_at, int x_at,
+                           float c_in, int copies, void* stream);
+int drn_latent_tile_step_join(const void* model_out, const void* uncond, float guidance, const void* canvas_cur,
+                              void* canvas_next, const float* wy, const float* wx, int64_t planes, int Hc, int Wc, int h, int w,
+                              int y_at, int x_at, int ry, int rx, int Oy, int Ox, float c_skip, float c_out, float sigma, float dt,
+                              void* stream);
+
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
  * Activations are channels-last bf16, X[t][h][w][c], stored with an optional 1-pixel zero halo in H and W
