@@ -344,7 +344,9 @@ static int gemm_impl(const void* A, const void* W, void* C, int64_t M, int64_t N
         if (epilogue == DRN_EPI_GATE_RES && rows_per_batch < M) {
             // ragged batches (the last one shorter): one launch with the tile of the whole problem, gates by row / rows_per_batch
             int tile = 0;
-            (void)gemm_plan_rows(M, N, blk[0] != 62 || blk[2] != 62, &tile);
+            const bool blocked = blk[0] != 62 || blk[2] != 62;
+            (void)gemm_plan_rows(M, N, blocked, &tile);
+            if (blocked && tile == 0) return DRN_EINVAL;   // as in gemm_clip: the 128x128 kernel has no blocked layouts
             return gemm_launch_tile(tile, A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, rows_per_batch, stream, blk);
         }
         return gemm_clip(A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, stream, blk);

@@ -69,7 +69,8 @@ int drn_gemm_bf16(const void* A, const void* W, void* C, int64_t M, int64_t N, i
  * C + (n / c_block_cols) * c_block_stride + m * ldc + n % c_block_cols (block_cols 0 = plain; powers of two, >= 64 for A,
  * >= 256 for C).  New on this path (the reference has no multi-GPU code): the sequence-parallel K|V / Q projections write
  * the rank-major send buffer of the head <-> token all-to-all directly and the output projection reads the rank-major
- * receive buffer, instead of a regroup pass either side.  DRN_EINVAL when the shape would take the 128x128 kernel. */
+ * receive buffer, instead of a regroup pass either side.  DRN_EINVAL when the shape would take the 128x128 kernel,
+ * with ragged clips (DRN_EPI_GATE_RES, rows_per_batch < M) too; nothing is launched then. */
 int drn_gemm_bf16_blocked(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K,
                           int64_t lda, int64_t ldw, int64_t ldc, int epilogue,
                           const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,

@@ -3,7 +3,9 @@
 are also what tests/test_kernels_gpu.py imports).  Nothing here touches the GPU: inputs are built on the CPU from a seed,
 references are computed from the bf16 inputs with the kernels' DOCUMENTED rounding points, and the stand-ins (with optional
 mutations) exist to show that every bound passes a correct bf16 implementation at every GRID_* case and fails a subtly wrong one.
-The GRID_* lists are iterated by both modules: what is proven on the CPU is exactly what runs on the GPU."""
+The GRID_* lists are iterated by both modules: what is proven on the CPU is exactly what runs on the GPU.
+GRID_GEMM_BLOCKED (the slab GEMM of the sequence-parallel exchange, operands in column planes) is shared in the same way by
+tests/test_sp_slab_kernels_gpu.py and tests/test_sp_slab_refs_cpu.py."""
 import math
 from collections import namedtuple
 
@@ -625,3 +627,245 @@ GRID_PATCHIFY = [(2, 16, 2, 8, 8), (3, 136, 1, 4, 6)]          # B, cond channel
 GRID_UNPATCHIFY = [(2, 2, 5, 7), (3, 1, 3, 4)]                 # B, Tp, Hp, Wp
 GRID_SAMPLER_N = [1, 7, 4097]                                  # element counts either side of every vector width
 GRID_POSTPROCESS = [(2, 3, 5, 7), (3, 1, 4, 9)]                # B, T, H, W (odd W)
+
+
+# ------------------------------------------------------------------------------------------------ slab GEMM (drn_gemm_bf16_blocked)
+# Operands in column planes (include/drn.h): logical A[m][k] at A + (k / a_block_cols) * a_block_stride + m * lda + k % a_block_cols,
+# logical C[m][n] at C + (n / c_block_cols) * c_block_stride + m * ldc + n % c_block_cols.
+def planes_of(t, cols):
+    """Logical [M, X] -> planes [X / cols, M, cols] (contiguous)."""
+    M, X = t.shape
+    assert X % cols == 0, (X, cols)
+    return t.reshape(M, X // cols, cols).permute(1, 0, 2).contiguous()
+
+
+def from_planes(p):
+    """Planes [P, M, cols] (any strides) -> logical [M, P cols]."""
+    P, M, cols = p.shape
+    return p.permute(1, 0, 2).reshape(M, P * cols)
+
+
+def place_planes(P, M, cols, ld, gap, device, value=None, pad_rows=2):
+    """P planes of M x cols in ONE sentinel-filled allocation (guarded(..., batches=P, batch_gap=gap)): row stride ld >= cols, plane
+    stride M ld + gap.  The row padding, the gaps between planes and the guard rows hold the NaN sentinel.  value: planes [P, M, cols]
+    copied in.  Returns (buffer, window [P, M, cols])."""
+    buf, v = guarded(M, cols, ld, pad_rows, device, batches=P, batch_gap=gap)
+    if P == 1:
+        v = torch.as_strided(buf, (1, M, cols), (M * ld + gap, ld, 1), pad_rows * ld)
+    if value is not None:
+        v.copy_(value)
+    return buf, v
+
+
+def gemm_cost_model(M, N):
+    """(tile, cost) of csrc/gemm.hip's pick_gemm_tile under its defaults (tests/test_dit_refs_cpu.py holds it to
+    drn_gemm_tile_choice): 0 = 128 x 128, 1 = 256 x 256, 2 = 144 x 256."""
+    if N < 256 or N % 256:
+        return 0, 1e30
+    t256, t128, t144 = -(-M // 256) * (N // 256), -(-M // 128) * (N // 128), -(-M // 144) * (N // 256)
+    c128 = 0.65 * (-(-t128 // 512))
+    c256 = float(-(-t256 // 256)) if M >= 256 else 1e30
+    c144 = 0.64 * (-(-t144 // 256)) if (M >= 144 and t144 >= 192) else 1e30
+    best = 2 if (c144 < c256 and c144 < c128) else (1 if c256 <= c128 else 0)
+    return best, (c144 if best == 2 else c256 if best == 1 else c128)
+
+
+def gemm_plan_rows(M, N, blocked=True):
+    """(rows of the first launch, its tile) as gemm_plan_rows of csrc/gemm.hip plans ONE clip: the rows that fill whole rounds of
+    256 x 256 workgroups, the rest left to a second launch (gemm_clip's recursion) when that is cheaper.  A blocked launch never
+    leaves a tail to the 128 x 128 kernel."""
+    tile, cost_all = gemm_cost_model(M, N)
+    if tile != 1:
+        return M, tile
+    tm, tn = -(-M // 256), N // 256
+    rounds, rem = tm * tn // 256, tm * tn % 256
+    tm_main = rounds * 256 // tn
+    if rounds < 1 or rem == 0 or tm_main < 1 or tm_main >= tm:
+        return M, tile
+    tail_tile, cost_tail = gemm_cost_model(M - tm_main * 256, N)
+    if blocked and tail_tile == 0:
+        cost_tail = 1e30
+    return (tm_main * 256 if -(-tm_main * tn // 256) + cost_tail + 0.02 < cost_all - 0.05 else M), tile
+
+
+# tile: 1 / 2 = drn_gemm_force_tile, -1 = automatic dispatch.  layout: "a" = A in planes of abc columns, "c" = C in planes of cbc
+# columns, "ac" = both (the other operand plain).  padded: lda / ldc = width + 64 (planes: plane gap 128 elements; the residual window
+# ldr = N + 128), else contiguous.  alias: the residual IS the (plain) output window.  rpb: rows per clip.  pre: the launch takes the
+# residual-prefetch variant of the 256-row kernel (and is repeated with the prefetch off).
+BlockedCase = namedtuple("BlockedCase", "tile M N K epi layout abc cbc padded alias rpb pre seed")
+
+
+def _widths(K):
+    """The a_block_cols a K allows out of 64 (a new plane every K step), 128 and K / 2: powers of two >= 64 that divide K."""
+    return [v for v in dict.fromkeys((64, 128, K // 2)) if v >= 64 and v & (v - 1) == 0 and K % v == 0]
+
+
+def _gemm_blocked_grid():
+    cases, seed, i = [], 7000, 0
+    ks = (64, 128, 192, 4096)                          # 1, 2, 3 and 64 K steps of 64
+    seen_k, seen_a, seen_c = {}, {}, {}                # how often a K, a K with A planes, an N with C planes has come up
+    for tile in (1, 2):
+        h = GEMM_TILE_ROWS[tile]
+        for M in (h - 1, h, h + 1, 2 * h + 1):
+            for epi in (EPI_NONE, EPI_GELU, EPI_GATE_RES):
+                for layout in ("a", "c", "ac"):
+                    seed, i = seed + 1, i + 1
+                    K, N = ks[i % 4], (512, 1024)[(i // 4) % 2]
+                    # K cycles; each K cycles through the A widths it allows, each N through its C widths; padding alternates per K
+                    abc = _widths(K)[seen_a.get(K, 0) % len(_widths(K))]
+                    cbc = (256, N // 2)[seen_c.get(N, 0) % 2]
+                    padded = seen_k.get(K, 0) % 2 == 1
+                    seen_k[K] = seen_k.get(K, 0) + 1
+                    seen_a[K] = seen_a.get(K, 0) + ("a" in layout)
+                    seen_c[N] = seen_c.get(N, 0) + ("c" in layout)
+                    alias = epi == EPI_GATE_RES and layout == "a" and M % 2 == 1
+                    cases.append(BlockedCase(tile, M, N, K, epi, layout, abc if "a" in layout else 0, cbc if "c" in layout else 0,
+                                             padded, alias, M, False, seed))
+        # gated residual, A planes, written in place (the output projection of the sharded forward); C planes with R in its own window
+        cases.append(BlockedCase(tile, 2 * h + 1, 512, 192, EPI_GATE_RES, "a", 64, 0, True, True, 2 * h + 1, False, seed + 100))
+        cases.append(BlockedCase(tile, 2 * h + 1, 1024, 128, EPI_GATE_RES, "c", 0, 256, True, False, 2 * h + 1, False, seed + 101))
+        # two clips, the boundary inside a tile: the gate row follows the row
+        for j, M in enumerate((h + 1, 2 * h + 1)):
+            cases.append(BlockedCase(tile, M, 512, 128, EPI_GATE_RES, "a", 64, 0, j == 0, True, (M + 1) // 2, False, seed + 110 + j))
+            cases.append(BlockedCase(tile, M, 1024, 192, EPI_GATE_RES, "ac", 64, 512, j == 1, False, (M + 1) // 2, False, seed + 120 + j))
+    # M = 2 h, K = 4096 on the 256-row kernel: whole tiles inside one clip, 64 K steps = the residual-prefetch variant
+    cases.append(BlockedCase(1, 512, 512, 4096, EPI_GATE_RES, "a", 64, 0, True, True, 512, True, 7300))
+    cases.append(BlockedCase(1, 512, 1024, 4096, EPI_GATE_RES, "ac", 2048, 256, False, False, 512, True, 7301))
+    # automatic dispatch at the band shapes of the "slabs" route: K | V (N = 2 D) and Q (N = D) projections into C planes of
+    # N / world columns, world = 8, 4, 2 (one seed per (rows, N): the three plane widths share one fp64 reference)
+    for r, rows in enumerate((2304, 4608, 9216)):
+        for n, N in enumerate((4096, 8192)):
+            for p, P in enumerate((8, 4, 2)):
+                cases.append(BlockedCase(-1, rows, N, 128, EPI_NONE, "c", 0, N // P, (r + n + p) % 2 == 1, False, rows, False,
+                                         7400 + 10 * r + n))
+    # the output projection: A in 8 planes of 128 columns, gated residual in place
+    for r, rows in enumerate((2304, 9216)):
+        cases.append(BlockedCase(-1, rows, 4096, 1024, EPI_GATE_RES, "a", 128, 0, r == 0, True, rows, False, 7450 + r))
+    # The tail split of gemm_clip (rows that fill whole rounds of 256 x 256 workgroups, the rest in a second launch that advances
+    # A by M_main * lda inside every plane).  drn_gemm_tile_choice / gemm_plan_rows over M < 20000: the band shape 9216 x 8192 above
+    # is one (8192 rows on the 256-row kernel, 1024 on the 144-row one); the smallest is 4817 x 8192 (4096 rows, then a ragged 721
+    # on the 144-row kernel).  The latter with A planes too, and with the gated residual in place.
+    cases.append(BlockedCase(-1, 4817, 8192, 128, EPI_NONE, "ac", 64, 1024, True, False, 4817, False, 7460))
+    cases.append(BlockedCase(-1, 4817, 8192, 128, EPI_GATE_RES, "a", 64, 0, False, True, 4817, False, 7461))
+    return cases
+
+
+GRID_GEMM_BLOCKED = _gemm_blocked_grid()
+
+
+def blocked_id(c):
+    return (f"{'auto' if c.tile < 0 else 'tile' + str(c.tile)}-M{c.M}-N{c.N}-K{c.K}-epi{c.epi}-{c.layout}-a{c.abc}-c{c.cbc}"
+            + ("-pad" if c.padded else "-contig") + ("-alias" if c.alias else "") + (f"-rpb{c.rpb}" if c.rpb != c.M else "")
+            + ("-pre" if c.pre else ""))
+
+
+_BLOCKED_REF = {}
+
+
+def blocked_inputs_ref(c):
+    """(a, w, gate, res, ref, mag) of a case: gemm_inputs and gemm_ref, computed once per (shape, epilogue, seed) and shared."""
+    key = (c.M, c.N, c.K, c.epi, c.rpb, c.seed)
+    if key not in _BLOCKED_REF:
+        if c.M * c.N > 1 << 22:
+            _BLOCKED_REF.clear()                       # one large reference resident at a time
+        a, w, gate, res = gemm_inputs(c)
+        _BLOCKED_REF[key] = (a, w, gate, res) + tuple(gemm_ref(a, w, c.epi, gate, res, c.rpb))
+    return _BLOCKED_REF[key]
+
+
+def blocked_geometry(c):
+    """dict(lda, a_stride, ldc, c_stride, ldr, gap) of a case as both the stand-in and the GPU test place it."""
+    pad, gap = (64, 128) if c.padded else (0, 0)
+    aw, cw = (c.abc or c.K), (c.cbc or c.N)
+    lda, ldc = aw + pad, cw + pad
+    return dict(lda=lda, a_stride=c.M * lda + gap if c.abc else 0, ldc=ldc, c_stride=c.M * ldc + gap if c.cbc else 0,
+                ldr=ldc if c.alias else c.N + 2 * pad, gap=gap)
+
+
+def blocked_windows(c, a, res, device):
+    """The operand windows of a case on `device`: A (planes or plain) filled, C (planes or plain; pre-filled with the residual when
+    it aliases it), R.  Returns dict(a=(buf, win), c=(buf, win), r=(buf, win) | None); win is [P, M, cols] (P = 1 when plain)."""
+    g = blocked_geometry(c)
+    pa, pc = (c.K // c.abc if c.abc else 1), (c.N // c.cbc if c.cbc else 1)
+    out = dict(a=place_planes(pa, c.M, c.K // pa, g["lda"], g["gap"] if c.abc else 0, device, planes_of(a, c.K // pa).to(device)),
+               c=place_planes(pc, c.M, c.N // pc, g["ldc"], g["gap"] if c.cbc else 0, device), r=None)
+    if c.epi == EPI_GATE_RES:
+        if c.alias:
+            assert not c.cbc, "the residual is a plain matrix: only a plain C can alias it"
+            out["c"][1][0].copy_(res)
+        else:
+            out["r"] = place_planes(1, c.M, c.N, g["ldr"], 0, device, res.to(device).unsqueeze(0))
+    return out
+
+
+BLOCKED_MUTANTS = ("a_plane_stride_ignored", "a_koff_no_wrap", "a_plane_of_tile", "c_plane_neighbour", "c_ld_plain",
+                   "tail_rows_plane0", "res_read_as_planes")
+
+
+def _gather(buf, idx):
+    """buf.flatten()[idx]; an index outside the allocation reads the sentinel (on the GPU: whatever lies there, or a fault)."""
+    flat = buf.reshape(-1)
+    ok = (idx >= 0) & (idx < flat.numel())
+    out = flat[idx.clamp(0, flat.numel() - 1)].clone()
+    out.view(torch.int16)[~ok] = SENTINEL
+    return out
+
+
+def gemm_blocked_standin(c, wins, w, gate, mutant=None, slices=1):
+    """gemm_standin's arithmetic reading A and R and writing C through the plane addressing of include/drn.h, element by element on
+    the flat allocations of blocked_windows (CPU).  Mutants:
+      a_plane_stride_ignored  A planes assumed contiguous (plane stride M lda)
+      a_koff_no_wrap          k % a_block_cols lost: past the first plane the read runs on into the row's padding / the next row
+      a_plane_of_tile         the plane taken from the tile's first K step only (every K step reads plane 0)
+      c_plane_neighbour       column tiles past the first store into the plane of the tile before them
+      c_ld_plain              rows of a C plane stored with row stride N
+      tail_rows_plane0        rows past the first launch of a tail split (gemm_plan_rows) get their row offset in plane 0 only
+      res_read_as_planes      R addressed like C (planes, ldc)
+    A store outside the allocation is dropped (on the GPU: a fault at best); what it leaves unwritten is found like any other."""
+    assert mutant is None or mutant in BLOCKED_MUTANTS, mutant
+    g = blocked_geometry(c)
+    M, N, K = c.M, c.N, c.K
+    m = torch.arange(M).view(M, 1)
+    (abuf, awin), (cbuf, cwin) = wins["a"], wins["c"]
+    # ---- A
+    k = torch.arange(K).view(1, K)
+    if c.abc:
+        plane, col = k // c.abc, k % c.abc
+        stride = M * g["lda"] if mutant == "a_plane_stride_ignored" else g["a_stride"]
+        if mutant == "a_koff_no_wrap":
+            col = k                                    # the whole k instead of k % a_block_cols
+        if mutant == "a_plane_of_tile":
+            plane = plane * 0
+        row = m.expand(M, K)
+        if mutant == "tail_rows_plane0":
+            m_main = gemm_plan_rows(M, N)[0] if c.tile < 0 else M
+            row = torch.where((m >= m_main) & (plane > 0), m - m_main, m)
+        ia = plane * stride + row * g["lda"] + col
+    else:
+        ia = m * g["lda"] + k
+    a = _gather(abuf, ia + awin.storage_offset())
+    # ---- R (read before C is written: it may be the same memory)
+    n = torch.arange(N).view(1, N)
+    res = None
+    if c.epi == EPI_GATE_RES:
+        rbuf, rwin = (cbuf, cwin) if c.alias else wins["r"]
+        ir = m * g["ldr"] + n
+        if mutant == "res_read_as_planes" and c.cbc:
+            ir = (n // c.cbc) * g["c_stride"] + m * g["ldc"] + n % c.cbc
+        res = _gather(rbuf, ir + rwin.storage_offset())
+    out = gemm_standin(a, w, c.epi, gate, res, c.rpb, slices=slices)
+    # ---- C
+    flat = cbuf.reshape(-1)
+    for r0 in range(0, M, 2048):                       # (row bands: the index tensors of a 9216 x 8192 output stay small)
+        mm = m[r0:r0 + 2048]
+        if c.cbc:
+            plane = n // c.cbc
+            if mutant == "c_plane_neighbour":
+                plane = torch.where(n >= 256, (n // 256 * 256 - 256) // c.cbc, plane)
+            ic = plane * g["c_stride"] + mm * (N if mutant == "c_ld_plain" else g["ldc"]) + n % c.cbc
+        else:
+            ic = mm * g["ldc"] + n
+        ic = (ic + cwin.storage_offset()).reshape(-1)
+        ok = (ic >= 0) & (ic < flat.numel())
+        flat[ic[ok]] = out[r0:r0 + 2048].reshape(-1)[ok]
+    return from_planes(cwin)

@@ -13,5 +13,8 @@ rc=$?
   grep "tokenizer-kernel " "$out/parity_full.log" | cut -c1-260
   grep -E "e_ref=|attention .*rel-L2|uint8 mean|x0 rel-L2|g4:|identical|prefix|batched vs single|passed|failed" gpurun_out/parity_full.log | grep -v "^tests/" | cut -c1-260
 } > gpurun_out/parity.txt
+# the slab GEMM and the regroup kernel at plane, tile and clip edges (tests/test_sp_slab_kernels_gpu.py), one line per case
+# -> sp_slab_parity.txt in the output directory (copied to profiles/sp_slab_parity.txt under that file's header)
+grep -o "sp-slab-edge .*" "$out/parity_full.log" | cut -c1-260 > "$out/sp_slab_parity.txt"
 tail -5 gpurun_out/parity.txt
 exit $rc
