@@ -18,7 +18,7 @@ import torch
 
 from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
-from .fit import restore_frames
+from .fit import restore_frames, restore_frames_guided
 from .model_diffusion_renderer import CleanDiffusionRendererModel
 from .tiles import blend_tile, latent_tile, plan_tiles
 from .windows import Window, plan_windows, ramp_weights
@@ -49,6 +49,10 @@ class CleanDiffusionRendererPipeline:
         # the fit's way back (fit.py): a RestorePlan -> the uint8 outputs are resampled to the source's size on the device, before
         # the D2H copy; None = the outputs keep the model's size (today's path, today's bits)
         self.restore_plan = None
+        # the guided way back (fit.py): a fit.RestoreGuide (the plan, the source picture and the source as the model
+        # saw it, on the device) -> where a restore plan is set, the outputs come back by joint bilateral upsampling with the
+        # source as the guide (drn_restore_guided_u8); None = the plain way back (today's path, today's bits)
+        self.restore_guide = None
         # large pictures (tiles.py): a picture larger than tile_height x tile_width (multiples of 16; 0 = that axis is not tiled,
         # both 0 = off; 576 x 1024 = the training size) is rendered as overlapping tiles of exactly that size, each an independent
         # sample, cross-faded over `tile_overlap` rows / columns where the results lie as uint8 on the device
@@ -192,11 +196,17 @@ class CleanDiffusionRendererPipeline:
             raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
         return [o[0] for o in self._render(batches, [[f] for f in flags], seed, init_noise, clips=True, to_host=to_host)]
 
-    def _restored(self, u8, frames=None):
+    def _restored(self, u8, frames=None, t0=0):
         """The uint8 result [B, T', H', W', 3] at the source's size where a restore plan is set (fit.restore_frames, on the device),
-        cut to the plan's T frames, or to `frames` (a window's written frames: a windowed clip has no time padding)."""
+        cut to the plan's T frames, or to `frames` (a window's written frames: a windowed clip has no time padding).  With a
+        restore guide the way back is fit.restore_frames_guided; t0: the clip's frame the first of these frames is (a window's
+        `out_at`), where the guide is read."""
         if self.restore_plan is None:
             return u8
+        if self.restore_guide is not None:
+            guide = self.restore_guide
+            gplan = dataclasses.replace(guide.plan, T=int(self.restore_plan.T if frames is None else frames))
+            return restore_frames_guided(u8, gplan, guide.hi, guide.lo, t0=int(t0))
         rplan = self.restore_plan if frames is None else dataclasses.replace(self.restore_plan, T=int(frames))
         return restore_frames(u8, rplan)
 
@@ -235,7 +245,7 @@ class CleanDiffusionRendererPipeline:
         batches of one clip, share a crop), the walk runs on the crops with its result left on the device at the tile's size -
         windows, carries and passes as they are, same seed, same start noise: every tile has one shape -, and each result is
         cross-faded into that pass's full-size canvas (tiles.blend_tile).  After the last tile the restore plan is applied once
-        per canvas (it also cuts the time padding), then the copy to the host.  Device memory: one full-size uint8 canvas per
+        per canvas (it also cuts the time padding; with a restore guide, guided), then the copy to the host.  Device memory: one full-size uint8 canvas per
         pass plus one tile's results.
 
         tile_join = "latent"  changes where the tiles' samples come from and nothing behind them: `_joint_samples`
@@ -419,7 +429,7 @@ class CleanDiffusionRendererPipeline:
                     # frames are independent: window by window = the whole clip.  Kept: those written, up to the restore plan's T
                     # (the time padding of a whole clip is cut; a windowed clip has none)
                     if self.restore_plan is not None:
-                        u8 = self._restored(u8, frames=min(u8.shape[1], self.restore_plan.T - win.out_at))
+                        u8 = self._restored(u8, frames=min(u8.shape[1], self.restore_plan.T - win.out_at), t0=win.out_at)
                     if outs[c][p] is None:
                         outs[c][p] = torch.empty((u8.shape[0], u8.shape[1] if whole else T) + tuple(u8.shape[2:]), dtype=torch.uint8,
                                                  device="cpu" if to_host else u8.device)

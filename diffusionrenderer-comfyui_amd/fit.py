@@ -12,6 +12,11 @@ backends give the bits of today's ingest, `(image.permute(0, 4, 1, 2, 3) * 2 - 1
 The way back (the nodes' `fit_restore`): `plan_restore` turns the plan of a fit that kept the whole picture round, and
 `restore_frames` resamples the pipeline's uint8 outputs [B, T', H', W', 3] to the source's [B, T, H, W, 3] with the same filter -
 the torch backend again the specification, on a GPU one launch of drn_restore_frames_u8 (csrc/restore.hip).  The three kernels share csrc/resample_core.h.
+
+The guided way back (the nodes' `restore_guide`): `plan_restore_guided` widens the way back's spatial tables and adds
+a range table, and `restore_frames_guided` weights every tap again by how close the full-size source pixel is to the fitted source
+at that tap (joint bilateral upsampling) - torch the specification, on a GPU one launch of drn_restore_guided_u8
+(csrc/restore_guided.hip, on the same core).
 """
 import math
 from dataclasses import dataclass
@@ -54,12 +59,13 @@ class FitPlan:
         return self.W_full == self.W
 
 
-def axis_taps(n_in: int, n_full: int, off: int, n_out: int):
+def axis_taps(n_in: int, n_full: int, off: int, n_out: int, reach: float = 1.0):
     """Tap table of output samples off .. off + n_out - 1 of an axis resized from n_in to n_full samples, in the arithmetic of
     torch's antialiased bilinear resize: -> (lo_n int32 [n_out, 2], w float64 [n_out, K]).  Rows sum to 1 (normalised in
-    float64), taps of weight exactly 0 are dropped, the rest of a row is zero padding."""
+    float64), taps of weight exactly 0 are dropped, the rest of a row is zero padding.  reach: the triangle's support widened by
+    this factor (1.0: torch's own, the same tables bit for bit; the guided way back takes 2.0)."""
     scale = n_in / n_full
-    support = max(scale, 1.0)
+    support = max(scale, 1.0) * reach
     i = np.arange(off, off + n_out, dtype=np.float64)
     c = scale * (i + 0.5)
     lo = np.maximum(0, (c - support + 0.5).astype(np.int64))          # the cast truncates, like torch's
@@ -200,6 +206,145 @@ def restore_frames(u8: torch.Tensor, rplan: RestorePlan, backend: str = "auto") 
         return _restore_torch(u8, rplan)
     from . import native
     return native.restore_frames(u8.contiguous(), rplan.T, rplan.y_lo_n, rplan.y_w, rplan.x_lo_n, rplan.x_w)
+
+
+# ----------------------------------------------------------------------------------------------- the guided way back
+GUIDED_MAX_TAPS = 8       # per axis (drn_restore_guided_u8: Ky, Kx in 1..8)
+GUIDED_REACH = 2.0        # the spatial support: max(scale, 1) * 2, four taps per axis when up-scaling
+GUIDED_EPS = 2.0 ** -10   # the floor of the range term: the denominator stays positive
+
+
+@dataclass
+class GuidedPlan:
+    T: int                  # frames to return
+    H_model: int            # the size the outputs arrive in: the fit's H', W'
+    W_model: int
+    H: int                  # the size they leave in: the source's
+    W: int
+    y_lo_n: torch.Tensor    # int32 [H, 2], float32 [H, Ky]: the tables of axis_taps(H', H, 0, H, reach)
+    y_w: torch.Tensor
+    x_lo_n: torch.Tensor
+    x_w: torch.Tensor
+    tab: torch.Tensor       # float32 [256]: exp(-d^2 / (2 sigma^2)) of a byte difference d, float64 rounded once
+    eps: float
+    sigma: float
+
+
+def range_table(sigma: float) -> torch.Tensor:
+    """The range term of one channel by byte difference d = 0 .. 255: exp(-d^2 / (2 sigma^2)) in float64, rounded to fp32 once.
+    The product over the three channels is the Gaussian of the colour distance."""
+    d = np.arange(256, dtype=np.float64)
+    return torch.from_numpy(np.exp(-d * d / (2.0 * float(sigma) ** 2)).astype(np.float32))
+
+
+def plan_restore_guided(plan: FitPlan, sigma: float, reach: float = GUIDED_REACH) -> GuidedPlan:
+    """The guided way back of a fit that kept the whole picture (joint bilateral upsampling, Kopf et al. 2007): the spatial tables
+    of `plan_restore` with the support widened by `reach` - the filter then gets past the one mixed pixel every low-resolution
+    edge has -, the range table of `sigma` (in levels of 255) and the floor.  ValueError where `plan_restore` refuses, for more
+    than 8 taps on an axis and for sigma <= 0."""
+    if not sigma > 0:
+        raise ValueError(f"restore_sigma must be positive, got {sigma}")
+    plan_restore(plan)                  # a crop that cut cannot be undone
+    y_lo_n, y_w = axis_taps(plan.H_out, plan.H, 0, plan.H, reach)
+    x_lo_n, x_w = axis_taps(plan.W_out, plan.W, 0, plan.W, reach)
+    for name, w in (("height", y_w), ("width", x_w)):
+        if w.shape[1] > GUIDED_MAX_TAPS:
+            raise ValueError(f"the guided restore of the {name} needs {w.shape[1]} taps per output sample; at most "
+                             f"{GUIDED_MAX_TAPS} are supported (restore_guide = 'off' takes up to {MAX_TAPS})")
+    return GuidedPlan(plan.T, plan.H_out, plan.W_out, plan.H, plan.W,
+                      torch.from_numpy(y_lo_n), torch.from_numpy(y_w.astype(np.float32)),
+                      torch.from_numpy(x_lo_n), torch.from_numpy(x_w.astype(np.float32)), range_table(sigma), GUIDED_EPS, float(sigma))
+
+
+def plan_guide_lo(plan: FitPlan) -> RestorePlan:
+    """The source as the model saw it, as a plan for `restore_frames`: the fit's own spatial tables applied to the source's bytes
+    (bytes by tap tables, round half to even), frames 0 .. T - 1.  For fits that kept the whole picture, as `plan_restore`."""
+    plan_restore(plan)
+    return RestorePlan(plan.T, plan.H, plan.W, plan.H_out, plan.W_out, plan.y_lo_n, plan.y_w, plan.x_lo_n, plan.x_w,
+                       _single(plan.y_lo_n.numpy(), plan.y_w.numpy(), plan.H) and _single(plan.x_lo_n.numpy(), plan.x_w.numpy(), plan.W))
+
+
+def _restore_guided_torch(u8, gplan: GuidedPlan, guide_hi, guide_lo, t0=0, rounded=True):
+    """The specification: fp32 on the 0..255 scale, tap by tap, ky outer and kx inner; per tap the range term from the table, the
+    weight, a multiply-add per channel and one for the denominator; one division, round half to even, clamp."""
+    T = gplan.T
+    dev = u8.device
+    src = u8[:, :T].to(torch.float32)
+    lo = guide_lo[:, t0:t0 + T]
+    G = guide_hi[:, t0:t0 + T].to(torch.int16)
+    tab = gplan.tab.to(dev)
+    eps = torch.tensor(gplan.eps, dtype=torch.float32, device=dev)
+    ylo, xlo = (t[:, 0].to(device=dev, dtype=torch.long) for t in (gplan.y_lo_n, gplan.x_lo_n))
+    yw, xw = gplan.y_w.to(dev), gplan.x_w.to(dev)
+    num = den = None
+    for ky in range(yw.shape[1]):
+        yi = (ylo + ky).clamp_max(gplan.H_model - 1)
+        for kx in range(xw.shape[1]):
+            xi = (xlo + kx).clamp_max(gplan.W_model - 1)
+            d = (G - lo[:, :, yi][:, :, :, xi].to(torch.int16)).abs().long()
+            t = tab[d]
+            r = t[..., 0] * t[..., 1] * t[..., 2] + eps
+            w = ((yw[:, ky, None] * xw[None, :, kx]) * r).unsqueeze(-1)          # padded taps: weight 0
+            term = w * src[:, :, yi][:, :, :, xi]
+            num = term if num is None else num + term
+            den = w if den is None else den + w
+    x = num / den
+    return x.round().clamp(0.0, 255.0).to(torch.uint8) if rounded else x
+
+
+def restore_frames_guided(u8: torch.Tensor, gplan: GuidedPlan, guide_hi: torch.Tensor, guide_lo: torch.Tensor, t0: int = 0,
+                          backend: str = "auto") -> torch.Tensor:
+    """uint8 [B, T', H', W', 3] at the model's size -> uint8 [B, T, H, W, 3] at the source's, frames 0 .. T - 1, with the source
+    as a guide: guide_hi [Bg, Tg, H, W, 3] the source picture, guide_lo [Bg, Tg, H', W', 3] the source as the model saw it
+    (`plan_guide_lo`), both uint8 on u8's device, Bg 1 or B; output frame t reads guide frames t0 + t.  backend: 'auto' = the HIP
+    kernel (drn_restore_guided_u8: 2.3 ms against the torch path's 150 ms at 57 x 1080 x 1920, profiles/restore_guided.txt) on a GPU tensor and torch
+    on a CPU tensor; 'torch' / 'hip' force a path ('hip' needs a GPU tensor).  Normal maps are not renormalised."""
+    if backend not in ("auto", "torch", "hip"):
+        raise ValueError(f"unknown backend {backend!r}")
+    for name, t in (("frames", u8), ("guide_hi", guide_hi), ("guide_lo", guide_lo)):
+        if t.dtype != torch.uint8 or t.ndim != 5 or t.shape[-1] != 3:
+            raise ValueError(f"the guided restore needs uint8 [B, T, H, W, 3] {name}, got {t.dtype} {tuple(t.shape)}")
+        if t.device != u8.device:
+            raise ValueError(f"{name} is on {t.device}, the frames on {u8.device}")
+    if tuple(u8.shape[2:4]) != (gplan.H_model, gplan.W_model) or u8.shape[1] < gplan.T:
+        raise ValueError(f"the plan was made for at least {gplan.T} frames of {(gplan.H_model, gplan.W_model)}, "
+                         f"got {tuple(u8.shape[1:4])}")
+    Bg, Tg = guide_hi.shape[:2]
+    if tuple(guide_hi.shape[2:4]) != (gplan.H, gplan.W) or tuple(guide_lo.shape) != (Bg, Tg, gplan.H_model, gplan.W_model, 3):
+        raise ValueError(f"the plan needs guides of {(gplan.H, gplan.W)} and {(gplan.H_model, gplan.W_model)} with the same clips "
+                         f"and frames, got {tuple(guide_hi.shape)} and {tuple(guide_lo.shape)}")
+    if Bg not in (1, u8.shape[0]):
+        raise ValueError(f"{Bg} guide clips for {u8.shape[0]} clips: one for all, or one each")
+    if t0 < 0 or t0 + gplan.T > Tg:
+        raise ValueError(f"frames {t0} .. {t0 + gplan.T - 1} are outside the guide's {Tg}")
+    if backend == "hip" and not u8.is_cuda:
+        raise ValueError(f"backend='hip' needs a GPU tensor, got one on {u8.device} (the torch path is what CPU devices run)")
+    if backend == "torch" or not u8.is_cuda:
+        return _restore_guided_torch(u8, gplan, guide_hi, guide_lo, t0)
+    from . import native
+    return native.restore_guided(u8.contiguous(), guide_lo.contiguous(), guide_hi.contiguous(), gplan.T, gplan.y_lo_n, gplan.y_w,
+                                 gplan.x_lo_n, gplan.x_w, gplan.tab, gplan.eps, t0=int(t0))
+
+
+@dataclass
+class RestoreGuide:
+    """What the pipeline's `restore_guide` holds: the plan and the two guides, on the pipeline's device."""
+    plan: GuidedPlan
+    hi: torch.Tensor        # uint8 [Bg, T, H, W, 3]: the source picture
+    lo: torch.Tensor        # uint8 [Bg, T, H', W', 3]: the source as the model saw it
+
+
+def source_guide(plan: FitPlan, image_5d: torch.Tensor, sigma: float, device) -> RestoreGuide:
+    """The source clip [B, T, H, W, 3] as the guide of its fit's way back.  uint8 frames are used as they are; fp32 ones in [0, 1]
+    become bytes on `device`, once; guide_lo is `restore_frames` under `plan_guide_lo`."""
+    gplan = plan_restore_guided(plan, sigma)
+    if image_5d.ndim != 5 or image_5d.shape[-1] != 3 or tuple(image_5d.shape[1:4]) != (plan.T, plan.H, plan.W):
+        raise ValueError(f"the plan was made for {(plan.T, plan.H, plan.W)} frames, got {tuple(image_5d.shape)}")
+    hi = image_5d.to(device)
+    if hi.dtype != torch.uint8:
+        hi = (hi.to(torch.float32) * 255.0).round().clamp(0, 255).to(torch.uint8)
+    hi = hi.contiguous()
+    return RestoreGuide(gplan, hi, restore_frames(hi, plan_guide_lo(plan)).contiguous())
 
 
 # a source byte i enters the fit as fp32(i) / 255, correctly rounded: the true division, done once on the CPU.  (i * (1 / 255) in

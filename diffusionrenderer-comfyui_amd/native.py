@@ -118,6 +118,7 @@ SIGNATURES = {
     "drn_fit_frames": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_fit_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_restore_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
+    "drn_restore_guided_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _F, _P],
     "drn_tile_blend_u8": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_latent_tile_gather": [_P, _P, _L, _I, _I, _I, _I, _I, _I, _F, _I, _P],
     "drn_latent_tile_step_join": [_P, _P, _F, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
@@ -922,6 +923,35 @@ def restore_frames(src, T, y_lo_n, y_w, x_lo_n, x_w, out=None):
     _check(load_library().drn_restore_frames_u8(_ptr(src), _ptr(out), B, Ts, Hs, Ws, T, Hd, Wd, _ptr(dev[0]), _ptr(dev[1]),
                                                 y_w.shape[1], _ptr(dev[2]), _ptr(dev[3]), x_w.shape[1], _stream()),
            "drn_restore_frames_u8")
+    return out
+
+
+def restore_guided(src, guide_lo, guide_hi, T, y_lo_n, y_w, x_lo_n, x_w, range_tab, eps: float, t0: int = 0, out=None):
+    """The guided way back on uint8 outputs (drn_restore_guided_u8; the plan: fit.plan_restore_guided).  src [B, Ts, Hs, Ws, 3],
+    guide_lo [Bg, Tg, Hs, Ws, 3] and guide_hi [Bg, Tg, Hd, Wd, 3] uint8 on one device, contiguous, at any byte alignment, Bg 1 or B;
+    T <= Ts frames to return, read from guide frames t0 .. t0 + T - 1; the plan's tables as HOST tensors (per axis lo_n int32
+    [n_out, 2] and w fp32 [n_out, K <= 8], range_tab fp32 [256]): they are checked here, where their contents can be read, and
+    uploaded -> uint8 [B, T, Hd, Wd, 3].  out: such a tensor to write into."""
+    for t in (src, guide_lo, guide_hi):
+        assert t.dtype == torch.uint8 and t.ndim == 5 and t.shape[-1] == 3 and t.is_contiguous() and t.device == src.device, \
+            "contiguous uint8 [B, T, H, W, 3] frames on one device required"
+    B, Ts, Hs, Ws, _ = src.shape
+    Bg, Tg = guide_hi.shape[:2]
+    Hd, Wd = y_lo_n.shape[0], x_lo_n.shape[0]
+    assert Bg in (1, B), "one guide for every clip, or one per clip"
+    assert tuple(guide_lo.shape) == (Bg, Tg, Hs, Ws, 3) and tuple(guide_hi.shape) == (Bg, Tg, Hd, Wd, 3), "guide shapes"
+    assert 1 <= T <= Ts and 0 <= t0 and t0 + T <= Tg, "frames to return outside the clip or the guide"
+    _check_tap_table(y_lo_n, y_w, Hs)
+    _check_tap_table(x_lo_n, x_w, Ws)
+    assert y_w.shape[1] <= 8 and x_w.shape[1] <= 8, "at most 8 taps per axis"
+    assert range_tab.dtype == torch.float32 and tuple(range_tab.shape) == (256,) and eps > 0, "range table fp32 [256], eps > 0"
+    if out is None:
+        out = torch.empty((B, T, Hd, Wd, 3), dtype=torch.uint8, device=src.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (B, T, Hd, Wd, 3) and out.is_contiguous()
+    dev = [t.contiguous().to(src.device) for t in (y_lo_n, y_w, x_lo_n, x_w, range_tab)]
+    _check(load_library().drn_restore_guided_u8(_ptr(src), _ptr(guide_lo), _ptr(guide_hi), _ptr(out), B, Bg, Ts, Hs, Ws, Tg, t0, T,
+                                                Hd, Wd, _ptr(dev[0]), _ptr(dev[1]), y_w.shape[1], _ptr(dev[2]), _ptr(dev[3]),
+                                                x_w.shape[1], _ptr(dev[4]), float(eps), _stream()), "drn_restore_guided_u8")
     return out
 
 

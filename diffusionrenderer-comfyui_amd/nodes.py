@@ -84,6 +84,19 @@ def _fit_inputs():
                                                    "Normal maps are resampled like any picture and not renormalised"})}
 
 
+def _guide_inputs():
+    """Optional inputs of the nodes that hold the source picture, for the guided way back (fit.py)."""
+    return {"restore_guide": (["off", "source"],
+                              {"default": "off",
+                               "tooltip": "source: fit_restore brings the outputs back with the full-size input picture as a guide "
+                                          "(joint bilateral upsampling): edges of the outputs land where the picture's edges are "
+                                          "instead of on a ramp 2-4 pixels wide.  Ignored unless fit is on and fit_restore is set"}),
+            "restore_sigma": ("FLOAT", {"default": 12.0, "min": 1.0, "max": 64.0, "step": 0.5,
+                                        "tooltip": "how close in colour (levels of 255, per channel, Gaussian) a low-resolution "
+                                                   "pixel's source must be to the full-size pixel to count; larger = closer to the "
+                                                   "plain fit_restore"})}
+
+
 def standardize_to_5d(image, name="image") -> torch.Tensor:
     """list / (H,W,C) / (B,H,W,C)->T=1 / (B,T,H,W,C) -> (B,T,H,W,C)   (reference nodes.py:156-177, :258-268)."""
     if isinstance(image, list):
@@ -113,6 +126,21 @@ def _configure(pipeline, model_type, guidance, seed, window_frames, window_overl
     pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
     pipeline.tile_join = tile_join
     pipeline.restore_plan = None
+    pipeline.restore_guide = None
+
+
+def _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma):
+    """The source clip as the guide of the way back (fit.source_guide, on the pipeline's device), or None where `restore_guide`
+    is off or ignored: fit off, or fit_restore off."""
+    if restore_guide not in ("off", "source"):
+        raise ValueError(f"restore_guide must be 'off' or 'source', got {restore_guide!r}")
+    if restore_guide == "off" or fit == "off" or not fit_restore:
+        return None
+    from .fit import plan_fit, source_guide
+    t5 = standardize_to_5d(image)
+    T, H, W = t5.shape[1:4]
+    plan = plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames)
+    return source_guide(plan, t5, restore_sigma, getattr(pipeline, "device", "cuda"))
 
 
 def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_frames):
@@ -149,12 +177,15 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                    to_host=True, tiles=(0, 0, 64), tile_join="pixel"):
+                    to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
     _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
+    guide = _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma)
+    if guide is not None:
+        pipeline.restore_guide = guide                  # the way back is guided by the source picture
     image_tensor = clips["image"]
     keep = plan.T if plan is not None else None
     kw = {} if to_host else {"to_host": False}
@@ -182,9 +213,10 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
                   env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
-                  tiles=(0, 0, 64), tile_join="pixel"):
+                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
-    (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit)."""
+    (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit);
+    restore_guide: its guide (a fit.RestoreGuide), or None for the plain way back."""
     _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
@@ -192,6 +224,7 @@ def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_bri
     clips, plan = _ingest(pipeline, inputs, fit, fit_height, fit_width, fit_restore, window_frames)
     if restore_plan is not None:
         pipeline.restore_plan = restore_plan
+        pipeline.restore_guide = restore_guide
     data_batch = {key_mapping[name]: t for name, t in clips.items()}
     keep = None
     if plan is not None:
@@ -270,7 +303,7 @@ class Cosmos1InverseRenderer:
             "required": {"pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "image": ("IMAGE",)},
             "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1}),
                          "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -280,9 +313,10 @@ class Cosmos1InverseRenderer:
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
-                         tile_join="pixel"):
+                         tile_join="pixel", restore_guide="off", restore_sigma=12.0):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
-                                        fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join)
+                                        fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join,
+                                        restore_guide=restore_guide, restore_sigma=restore_sigma)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -362,7 +396,7 @@ class Cosmos1Relight:
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -373,14 +407,17 @@ class Cosmos1Relight:
     def run_relight(self, inverse_pipeline, forward_pipeline, image, env_map, guidance=0.0, forward_guidance=0.0, seed=42,
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
-                    tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel"):
-        """Tiles, and the way they are joined, apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...})."""
-        from .fit import plan_fit, plan_restore, restore_frames
+                    tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0):
+        """Tiles, and the way they are joined, apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
+        restore_guide = 'source': the input picture guides the way back of all six outputs."""
+        from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
         tiles = (tile_height, tile_width, tile_overlap)
         rplan = None
         if fit != "off" and fit_restore:        # a crop that cut is refused before any GPU work, as the two nodes refuse it
             T, H, W = standardize_to_5d(image).shape[1:4]
             rplan = plan_restore(plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames))
+        guide = _source_guide(forward_pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide,
+                              restore_sigma)
         # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
                                         fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join)
@@ -392,11 +429,13 @@ class Cosmos1Relight:
         inputs = {k: inputs[k] for k in ("depth", "normal", "roughness", "metallic", "base_color")}
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
-                              restore_plan=rplan, tiles=tiles, tile_join=tile_join)
+                              restore_plan=rplan, tiles=tiles, tile_join=tile_join, restore_guide=guide)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:
-            if rplan is not None:
+            if guide is not None:
+                g = restore_frames_guided(g, guide.plan, guide.hi.to(g.device), guide.lo.to(g.device))
+            elif rplan is not None:
                 g = restore_frames(g, rplan)
             t = g.cpu().float() / 255.0
             b, tt, h, w, c = t.shape

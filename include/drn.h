@@ -2,7 +2,8 @@
  * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer),
  * the forward renderer's per-frame environment-light projection (drn_env_project), the
  * nodes' clip ingest with a fit to the model's grid (drn_fit_frames), its way back on the
- * uint8 outputs (drn_restore_frames_u8) and the join of spatial tiles on them (drn_tile_blend_u8).
+ * uint8 outputs (drn_restore_frames_u8, with the source as a guide drn_restore_guided_u8) and the join of spatial tiles on them
+ * (drn_tile_blend_u8).
  *
  * The reference (eggsbenedicto/DiffusionRenderer-ComfyUI) is pure Python/torch and has no FFI;
  * each entry point below names the reference code (file:line under /root/reference) whose
@@ -554,6 +555,28 @@ int drn_fit_frames_u8(const uint8_t* src, void* dst_bf16, int B, int Ts, int Hs,
  * B*Ts*Hs*Ws*3 >= 2^31, a table not 4-byte aligned. */
 int drn_restore_frames_u8(const uint8_t* src, uint8_t* dst, int B, int Ts, int Hs, int Ws, int Td, int Hd, int Wd,
                           const int* y_lo_n, const float* y_w, int Ky, const int* x_lo_n, const float* x_w, int Kx, void* stream);
+
+/* ---- the guided way back: the uint8 result of the post-process brought to the source's size with the source picture as a guide
+ * (no reference line: the reference has no fit; joint bilateral upsampling, Kopf et al. 2007; plan and torch specification:
+ * fit.py, plan_restore_guided / restore_frames_guided).
+ * ONE launch.  For output pixel (b, t, y, x), G = guide_hi[bg][t0 + t][y][x][:], q over the taps (y_lo + ky, x_lo + kx), ky
+ * outer and kx inner, g(q) = guide_lo[bg][t0 + t][q][:], bg = 0 where Bg == 1 and b otherwise:
+ *   r(q) = range_tab[|G_0 - g(q)_0|] * range_tab[|G_1 - g(q)_1|] * range_tab[|G_2 - g(q)_2|] + eps
+ *   w(q) = (y_w[y][ky] * x_w[x][kx]) * r(q)
+ *   dst[b][t][y][x][ch] = uint8(clamp(rint((sum_q w(q) * src[b][t][q][ch]) / (sum_q w(q))), 0, 255)),
+ * all in fp32 on the 0..255 scale (fma accumulation from 0 in tap order, one division), rint = round to nearest even.
+ *   src [B,Ts,Hs,Ws,3], guide_lo [Bg,Tg,Hs,Ws,3], guide_hi [Bg,Tg,Hd,Wd,3] and dst [B,Td,Hd,Wd,3] uint8, contiguous, at ANY
+ *   byte alignment; Bg is 1 (one guide for every clip) or B; Td <= Ts, 0 <= t0, t0 + Td <= Tg.  Tables on the device as for
+ *   drn_restore_frames_u8: per axis lo_n int32 [n_out][2] and w fp32 [n_out][K], zero-padded past n; range_tab fp32 [256] (the
+ *   plan's exp(-d^2 / (2 sigma^2)): no transcendental is evaluated on the device).
+ * lo and n are clamped into the source before use; what they should hold is checked on the host (native.restore_guided).
+ * Nothing outside dst is written, nothing outside src, guide_lo and guide_hi is read.
+ * DRN_EINVAL (nothing launched): a null pointer, a non-positive size, Bg not 1 or B, Td > Ts, t0 < 0, t0 + Td > Tg, Ky or Kx
+ * outside 1..8, any of the four tensors >= 2^31 bytes, a table not 4-byte aligned, eps <= 0. */
+int drn_restore_guided_u8(const uint8_t* src, const uint8_t* guide_lo, const uint8_t* guide_hi, uint8_t* dst,
+                          int B, int Bg, int Ts, int Hs, int Ws, int Tg, int t0, int Td, int Hd, int Wd,
+                          const int* y_lo_n, const float* y_w, int Ky, const int* x_lo_n, const float* x_w, int Kx,
+                          const float* range_tab, float eps, void* stream);
 
 /* ---- spatial tiles: one rendered tile cross-faded into the picture's canvas, in place (no reference line: the reference renders
  * a picture as one sequence; plan and torch specification: tiles.py, plan_tiles / blend_tile).
