@@ -23,6 +23,13 @@ int drn_gemm256s_dispatch(const void* A, const void* W, void* C, int64_t M, int6
                           void* stream, const int64_t* blk);
 int drn_gemm256s_partial(const void* A, const void* W, float* partial, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                          int splits, void* stream, bool wring_ok);
+// ---- gemm384.hip: 384x256x64 tile at one wave per SIMD (tile kernel 5): whole tiles, plain layouts, K >= 128, and for the gated
+// residual every tile inside one clip; drn_gemm384_ok is that test (ldmax: the largest row stride; blk == NULL: plain), the dispatch
+// returns DRN_EINVAL without it
+bool drn_gemm384_ok(int64_t M, int64_t N, int64_t K, int64_t ldmax, int epilogue, int64_t rpb, const int64_t* blk);
+int drn_gemm384_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                         int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,
+                         void* stream, const int64_t* blk);
 // ---- gemm144.hip: 144x256x64 kernel (token bands of sequence parallelism: M = 2304 k)
 int drn_gemm144_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                          int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,

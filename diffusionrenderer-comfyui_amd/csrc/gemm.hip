@@ -220,7 +220,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_kernel(const float* 
 // -> 0.79 vs 0.97 ms per DiT block; M = 18432 stays on 256^2).
 // Returns 0: 128^2, 1: 256^2, 2: 144x256.   DRN_GEMM256=0 / DRN_GEMM144=0 switch a kernel off, DRN_GEMM144=2 forces it (A/B runs).
 // drn_gemm_force_tile: -1 automatic, 0 / 1 / 2 as above; 3 = 1 (kept for callers of round 2); 4 = 1 with the split-K slices of
-// the small-M path on the 2 + 2 stage kernel instead of the weight-ring kernel (tests, A/B).
+// the small-M path on the 2 + 2 stage kernel instead of the weight-ring kernel (tests, A/B); 5 = the 384 x 256 kernel (gemm384.hip:
+// whole tiles only - a launch it cannot take returns DRN_EINVAL), which the automatic choice takes through gemm_plan_rows, not here.
 static int g_force_tile = -1;
 extern "C" void drn_gemm_force_tile(int tile) { g_force_tile = tile; }
 static int tall_choice(int64_t M, int64_t N, int64_t K);          // few-token kernel (gemm_tall.hip), defined with the split-K rules
@@ -263,6 +264,8 @@ static int gemm_launch_tile(int tile, const void* A, const void* W, void* C, int
         return drn_gemm256s_dispatch(A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, rows_per_batch, stream, blk);
     if (tile == 2)
         return drn_gemm144_dispatch(A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, rows_per_batch, stream, blk);
+    if (tile == 5)         // whole 384 x 256 tiles, plain layouts, every tile inside one clip: DRN_EINVAL otherwise, nothing launched
+        return drn_gemm384_dispatch(A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, rows_per_batch, stream, blk);
     const int64_t tiles = ((M + BM - 1) / BM) * (N / BN);
     DRN_CHECK_ARG(tiles < (1ll << 31));
     dim3 grid((unsigned)tiles), block(256);
@@ -283,10 +286,11 @@ static int gemm_launch_tile(int tile, const void* A, const void* W, void* C, int
 // workgroups, and - when the last round would be fractional (72 x 16 tiles = 4.5 rounds cost 5) - a second launch for the
 // remaining rows with the tile that suits them (DRN_GEMM_TAIL=0 switches the split off).  Returns the row count of the first
 // launch (M = no split) and its tile.
-static int64_t gemm_plan_rows(int64_t M, int64_t N, bool blocked, int* tile_out) {
+static int64_t gemm_plan_rows256(int64_t M, int64_t N, bool blocked, int* tile_out, double* cost_out) {
     double cost_all = 0.0;
     const int tile = pick_gemm_tile(M, N, &cost_all);
     *tile_out = tile;
+    *cost_out = cost_all;
     static int tail_mode = -1;
     if (tail_mode < 0) {
         const char* e = getenv("DRN_GEMM_TAIL");
@@ -302,7 +306,66 @@ static int64_t gemm_plan_rows(int64_t M, int64_t N, bool blocked, int* tile_out)
     const int tail_tile = pick_gemm_tile(M - M_main, N, &cost_tail);
     if (blocked && tail_tile == 0) cost_tail = 1e30;
     const double cost_split = (double)((tm_main * tn + 255) / 256) + cost_tail + 0.02;
-    return cost_split < cost_all - 0.05 ? M_main : M;
+    if (cost_split < cost_all - 0.05) {
+        *cost_out = cost_split;
+        return M_main;
+    }
+    return M;
+}
+
+// The 384 x 256 tile at one wave per SIMD (gemm384.hip, tile kernel 5): fewer operand pieces per FLOP, and 18 432 rows are 48 whole
+// tiles.  A workgroup does 1.5 units of work.  Chosen for ONE clip's rows, and only where all of these hold:
+//   * its preconditions (whole tiles, plain layouts, K >= 128 - drn_gemm384_ok);
+//   * the 384-row tiling fills whole rounds of the 256 CUs, or costs fewer round-equivalents than today's plan;
+//   * the shape is on the list of shapes where an interleaved A/B measured it faster than today's plan (profiles/gemm384.txt) -
+//     a shape that ties or loses, or that nobody measured, keeps today's plan.
+// DRN_GEMM384=0 switches it off; DRN_GEMM384=2 takes it for every shape that passes the first two rules (A/B runs).
+struct Gemm384Shape { int64_t M, N, K; };
+static const Gemm384Shape kGemm384Measured[] = {
+    {18432, 4096, 16384},                                  // MLP-down at 18 432 tokens: 1.737 -> 1.665 ms
+};
+static bool gemm384_choice(int64_t M, int64_t N, int64_t K, int64_t ldmax, bool blocked, double cost_today) {
+    static int mode = -1;
+    if (mode < 0) {
+        const char* e = getenv("DRN_GEMM384");
+        mode = e ? atoi(e) : 1;
+        if (mode < 0 || mode > 2) mode = 1;
+    }
+    if (!mode || g_force_tile >= 0 || blocked) return false;
+    if (!drn_gemm384_ok(M, N, K, ldmax, DRN_EPI_GATE_RES, M, nullptr)) return false;
+    const int64_t t384 = (M / 384) * (N / 256);
+    const double cost384 = 1.5 * (double)((t384 + 255) / 256);
+    if (t384 % 256 != 0 && !(cost384 < cost_today)) return false;
+    if (mode == 2) return true;
+    for (const Gemm384Shape& s : kGemm384Measured)
+        if (s.M == M && s.N == N && s.K == K) return true;
+    return false;
+}
+
+// (ldmax: the largest row stride among the operands - the 384-row kernel addresses a tile with 32-bit lane offsets)
+static int64_t gemm_plan_rows(int64_t M, int64_t N, int64_t K, int64_t ldmax, bool blocked, int* tile_out) {
+    double cost_today = 0.0;
+    const int64_t M_main = gemm_plan_rows256(M, N, blocked, tile_out, &cost_today);
+    if (gemm384_choice(M, N, K, ldmax, blocked, cost_today)) {
+        *tile_out = 5;
+        return M;
+    }
+    return M_main;
+}
+
+// what drn_gemm_bf16 does with a plain [M, K] x [N, K] product of clips of rows_per_batch rows (<= 0 or >= M: one clip), without
+// launching anything: returns the tile kernel of a clip's first launch (0 / 1 / 2 as drn_gemm_tile_choice, 5 = 384 x 256) and, in
+// *main_rows, how many of the clip's rows that launch covers (the rest go to a tail launch).  The few-token kernels (split-K,
+// gemm_tall.hip) are chosen before this plan and are not reported here.
+extern "C" int drn_gemm_plan_choice(int64_t M, int64_t N, int64_t K, int64_t rows_per_batch, int64_t* main_rows) {
+    if (main_rows) *main_rows = 0;
+    if (M <= 0 || N <= 0 || K <= 0 || N % BN != 0 || K % BK != 0) return DRN_EINVAL;
+    const bool batched = rows_per_batch > 0 && rows_per_batch < M && M % rows_per_batch == 0;
+    const int64_t Mb = batched ? rows_per_batch : M;
+    int tile = 0;
+    const int64_t rows = gemm_plan_rows(Mb, N, K, N > K ? N : K, false, &tile);
+    if (main_rows) *main_rows = rows;
+    return tile;
 }
 
 // one clip (or a plain problem): rows_per_batch >= M here
@@ -311,7 +374,10 @@ static int gemm_clip(const void* A, const void* W, void* C, int64_t M, int64_t N
                      const int64_t* blk) {
     const bool blocked = blk[0] != 62 || blk[2] != 62;
     int tile = 0;
-    const int64_t M_main = gemm_plan_rows(M, N, blocked, &tile);
+    int64_t ldmax = lda > ldw ? lda : ldw;
+    if (ldc > ldmax) ldmax = ldc;
+    if (residual && ldr > ldmax) ldmax = ldr;
+    const int64_t M_main = gemm_plan_rows(M, N, K, ldmax, blocked, &tile);
     if (blocked && tile == 0) return DRN_EINVAL;           // the 128x128 kernel has no blocked layouts (callers regroup instead)
     if (M_main == M)
         return gemm_launch_tile(tile, A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, M, stream, blk);
@@ -345,7 +411,8 @@ static int gemm_impl(const void* A, const void* W, void* C, int64_t M, int64_t N
             // ragged batches (the last one shorter): one launch with the tile of the whole problem, gates by row / rows_per_batch
             int tile = 0;
             const bool blocked = blk[0] != 62 || blk[2] != 62;
-            (void)gemm_plan_rows(M, N, blocked, &tile);
+            double cost = 0.0;                             // (today's plan: a 384-row tile must lie inside one clip)
+            (void)gemm_plan_rows256(M, N, blocked, &tile, &cost);
             if (blocked && tile == 0) return DRN_EINVAL;   // as in gemm_clip: the 128x128 kernel has no blocked layouts
             return gemm_launch_tile(tile, A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, rows_per_batch, stream, blk);
         }
@@ -353,7 +420,10 @@ static int gemm_impl(const void* A, const void* W, void* C, int64_t M, int64_t N
     }
     const int64_t Mb = rows_per_batch, nb = M / Mb;
     int tile = 0;
-    if (gemm_plan_rows(Mb, N, false, &tile) == Mb)          // one kernel covers a clip: one launch covers them all
+    int64_t ldmax = lda > ldw ? lda : ldw;
+    if (ldc > ldmax) ldmax = ldc;
+    if (residual && ldr > ldmax) ldmax = ldr;
+    if (gemm_plan_rows(Mb, N, K, ldmax, false, &tile) == Mb)   // one kernel covers a clip: one launch covers them all
         return gemm_launch_tile(tile, A, W, C, M, N, K, lda, ldw, ldc, epilogue, gate, residual, ldr, Mb, stream, blk);
     for (int64_t b = 0; b < nb; ++b) {
         const int rc = gemm_clip((const bf16_t*)A + b * Mb * lda, W, (bf16_t*)C + b * Mb * ldc, Mb, N, K, lda, ldw, ldc, epilogue,

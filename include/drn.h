@@ -101,6 +101,12 @@ int drn_gemm_splitk_choice(int64_t M, int64_t N, int64_t K);
  * A/B runs and tests (-1 = automatic). */
 int drn_gemm_tile_choice(int64_t M, int64_t N);
 void drn_gemm_force_tile(int tile);
+/* the plan of drn_gemm_bf16 for plain operands, nothing launched: the tile kernel that takes a clip's first launch (0 / 1 / 2 as
+ * above, 5: the 384x256 tile at one wave per SIMD - whole tiles only, taken only for shapes where it measured faster;
+ * DRN_GEMM384=0 in the environment switches it off) and, in *main_rows (may be NULL), how many of ONE clip's rows that launch covers
+ * (fewer than the clip has: a tail launch follows).  rows_per_batch: rows of one clip (<= 0: M).  drn_gemm_force_tile(5) selects
+ * the 384x256 kernel for every launch; one it cannot take returns DRN_EINVAL. */
+int drn_gemm_plan_choice(int64_t M, int64_t N, int64_t K, int64_t rows_per_batch, int64_t* main_rows);
 /* tuning hook (tests / A-B runs): the gated-residual epilogue of the 256x256 kernel takes its residual tile through LDS, requested
  * under the last two K steps, when the launch allows it (whole tiles inside one clip, an even number >= 4 of K steps, 16-byte
  * residual rows); 0 makes every launch load it after the loop as the other kernels do (same bits), 1 restores the default,

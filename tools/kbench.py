@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--S", type=int, default=18432)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--splits", type=int, default=1, help="attention: split-KV chunks (drn_attention_splitkv_bf16)")
-    ap.add_argument("--tiles", default="-1", help="gemm: comma list of forced tile kernels (-1 auto, 0 128^2, 1 256^2, 2 144x256)")
+    ap.add_argument("--tiles", default="-1", help="gemm: comma list of forced tile kernels (-1 auto, 0 128^2, 1 256^2, 2 144x256, 5 384x256), timed interleaved")
     ap.add_argument("--Sk", type=int, default=0, help="keys for attention (default: S); S is then the local query/token count")
     ap.add_argument("--cold", type=int, default=1, help="gemm: rotate over this many copies of the weights (and activations) so that "
                     "they come from HBM, not from the 256 MB Infinity Cache, as inside the model (4-6 copies)")
@@ -136,34 +136,47 @@ def main():
                   f"{(x[:, 5] / x[:, 6]).median().item() * 100:.0f} MHz")
             for i, nm in enumerate(names):
                 print(f"    {nm:18s} {x[:, i].median().item() / tiles:8.0f} cycles per tile  ({x[:, i].median().item() / tot * 100:5.1f} %)")
-    for name, fn, fl in cases:
-        times = [[] for _ in handles]
-        ref_out = None
-        for i, lib in enumerate(handles):
-            if name.startswith("attention"):
-                o.zero_()
-            fn(lib)
-            if name.startswith("attention") and len(handles) > 1:          # variants keep the summation order: same bits expected
-                torch.cuda.synchronize()
-                if ref_out is None:
-                    ref_out = o.clone()
-                else:
-                    print(f"    {os.path.basename(libs[i])}: identical to {os.path.basename(libs[0])}: {torch.equal(o, ref_out)}  "
-                          f"max|diff| {(o.float() - ref_out.float()).abs().max().item():.3e}", flush=True)
+    # cases of one group (a GEMM shape under several forced tiles) are timed round-robin inside every round, like the libraries:
+    # an A/B of two tile kernels is then interleaved in ONE process too
+    groups = []
+    for case in cases:
+        key = case[0].split(" tile ")[0]
+        if groups and groups[-1][0] == key:
+            groups[-1][1].append(case)
+        else:
+            groups.append((key, [case]))
+    for _, members in groups:
+        times = {(c, i): [] for c in range(len(members)) for i in range(len(handles))}
+        for c, (name, fn, fl) in enumerate(members):
+            ref_out = None
+            for i, lib in enumerate(handles):
+                if name.startswith("attention"):
+                    o.zero_()
+                fn(lib)
+                if name.startswith("attention") and len(handles) > 1:      # variants keep the summation order: same bits expected
+                    torch.cuda.synchronize()
+                    if ref_out is None:
+                        ref_out = o.clone()
+                    else:
+                        print(f"    {os.path.basename(libs[i])}: identical to {os.path.basename(libs[0])}: {torch.equal(o, ref_out)}  "
+                              f"max|diff| {(o.float() - ref_out.float()).abs().max().item():.3e}", flush=True)
         torch.cuda.synchronize()
         for _ in range(args.rounds):
-            for i, lib in enumerate(handles):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(3):
-                    fn(lib)
-                e1.record()
-                torch.cuda.synchronize()
-                times[i].append(e0.elapsed_time(e1) / 3)
-        for i, path in enumerate(libs):
-            t = sorted(times[i])
-            med, mn = t[len(t) // 2], t[0]
-            print(f"{name:46s} {os.path.basename(path):28s} median {med:8.3f} ms  {fl/med/1e9:8.1f} TF/s   min {mn:8.3f} ms {fl/mn/1e9:8.1f} TF/s", flush=True)
+            for c, (name, fn, fl) in enumerate(members):
+                for i, lib in enumerate(handles):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(3):
+                        fn(lib)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[(c, i)].append(e0.elapsed_time(e1) / 3)
+        for c, (name, fn, fl) in enumerate(members):
+            for i, path in enumerate(libs):
+                t = sorted(times[(c, i)])
+                med, mn = t[len(t) // 2], t[0]
+                print(f"{name:46s} {os.path.basename(path):28s} median {med:8.3f} ms  {fl/med/1e9:8.1f} TF/s   min {mn:8.3f} ms {fl/mn/1e9:8.1f} TF/s"
+                      f"   max {t[-1]:8.3f} ms", flush=True)
 
 
 if __name__ == "__main__":
