@@ -2,6 +2,7 @@
 // definer and caller alike, so a signature cannot drift between the two.  Arguments are validated by the public entry that calls.
 #pragma once
 #include "drn_common.h"
+#include "gemm_plan.h"
 
 struct ConvGeom;
 
@@ -16,17 +17,16 @@ void drn_attention16_launch(const void* q, const void* k, const void* v, void* o
                             float scale_log2e, int nqb, int64_t total, int nsplit, int64_t kv_chunk, float* opart, float* mlpart,
                             hipStream_t st, void* oq, void* os, int64_t mx_bs);
 
-// ---- gemm256s.hip: 256x256x64 tile, streamed schedule (tile kernel 1; 3 and 4 are accepted as aliases by drn_gemm_force_tile),
-// and its fp32 K slices
+// ---- gemm.hip: the process's GEMM settings (gemm_plan.h: the A/B switches, read once; .group = DRN_GEMM_GROUP for the tile launchers)
+const GemmSettings& drn_gemm_settings();
+// ---- gemm256s.hip: 256x256x64 tile, streamed schedule (tile kernel 1), and its fp32 K slices
 int drn_gemm256s_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                           int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,
                           void* stream, const int64_t* blk);
 int drn_gemm256s_partial(const void* A, const void* W, float* partial, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                          int splits, void* stream, bool wring_ok);
 // ---- gemm384.hip: 384x256x64 tile at one wave per SIMD (tile kernel 5): whole tiles, plain layouts, K >= 128, and for the gated
-// residual every tile inside one clip; drn_gemm384_ok is that test (ldmax: the largest row stride; blk == NULL: plain), the dispatch
-// returns DRN_EINVAL without it
-bool drn_gemm384_ok(int64_t M, int64_t N, int64_t K, int64_t ldmax, int epilogue, int64_t rpb, const int64_t* blk);
+// residual every tile inside one clip; drn_gemm384_ok (gemm_plan.h) is that test, the dispatch returns DRN_EINVAL without it
 int drn_gemm384_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                          int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,
                          void* stream, const int64_t* blk);

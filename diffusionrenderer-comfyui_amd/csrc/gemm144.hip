@@ -316,12 +316,7 @@ static int launch144(const void* A, const void* W, void* C, int64_t M, int64_t N
     const int64_t tiles = ((M + TM - 1) / TM) * ((N + TN - 1) / TN);
     if (tiles >= (1ll << 31) || M >= (1ll << 31)) return DRN_EINVAL;
     if (rpb > M || rpb <= 0) rpb = M;                      // (32-bit row / rows_per_batch arithmetic in the epilogue)
-    static int group = 0;
-    if (group == 0) {
-        const char* e = getenv("DRN_GEMM_GROUP");          // tile-rows per L2 band (A/B experiments)
-        group = e ? atoi(e) : 4;
-        if (group < 1) group = 4;
-    }
+    const int group = drn_gemm_settings().group;           // tile-rows per L2 band (DRN_GEMM_GROUP: A/B experiments)
     if constexpr (EPI == DRN_EPI_GATE_RES) {
         // every tile inside one clip and 32-bit residual offsets: the epilogue that requests the residual before the exchange
         if ((rpb == M || rpb % TM == 0) && residual && (int64_t)TM * ldr * 2 < (1ll << 31))

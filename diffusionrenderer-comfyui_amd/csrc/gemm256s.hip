@@ -404,12 +404,7 @@ static int launch256s(const void* A, const void* W, void* C, int64_t M, int64_t 
     const int64_t tiles = ((M + TB - 1) / TB) * ((N + TB - 1) / TB);
     if (tiles >= (1ll << 31) || M >= (1ll << 31)) return DRN_EINVAL;
     if (rpb > M || rpb <= 0) rpb = M;                      // (32-bit row / rows_per_batch arithmetic in the epilogue)
-    static int group = 0;
-    if (group == 0) {
-        const char* e = getenv("DRN_GEMM_GROUP");          // tile-rows per L2 band (A/B experiments)
-        group = e ? atoi(e) : 4;
-        if (group < 1) group = 4;
-    }
+    const int group = drn_gemm_settings().group;           // tile-rows per L2 band (DRN_GEMM_GROUP: A/B experiments)
     if constexpr (EPI == DRN_EPI_GATE_RES) {
         // whole tiles, each inside one clip, an even number (>= 4) of K steps, 16-byte residual rows: the residual tile comes in
         // through LDS under the last two K steps (same bits: only where the epilogue reads it from changes)

@@ -361,12 +361,7 @@ static int launch384(const void* A, const void* W, void* C, int64_t M, int64_t N
         if (e != hipSuccess) return (int)e;
         configured = true;
     }
-    static int group = 0;
-    if (group == 0) {
-        const char* e = getenv("DRN_GEMM_GROUP");          // tile-rows per L2 band (A/B experiments), as gemm256s
-        group = e ? atoi(e) : 4;
-        if (group < 1) group = 4;
-    }
+    const int group = drn_gemm_settings().group;           // tile-rows per L2 band (DRN_GEMM_GROUP: A/B experiments)
     const int64_t tiles = (M / G384_BM) * (N / G384_BN);
     gemm384_kernel<EPI><<<dim3((unsigned)tiles), dim3(256), G384_LDS, st>>>(
         (const bf16_t*)A, (const bf16_t*)W, (bf16_t*)C, M, N, K, lda, ldw, ldc, (const bf16_t*)gate, (const bf16_t*)residual, ldr,
@@ -374,28 +369,13 @@ static int launch384(const void* A, const void* W, void* C, int64_t M, int64_t N
     return drn_launch_status();
 }
 
-// what the kernel needs beyond gemm_impl's own checks: whole tiles, plain layouts, >= 2 K steps, 32-bit lane offsets inside a tile
-// (ldmax: the largest row stride of A, W, C and the residual); GATE_RES: every tile inside one clip
-bool drn_gemm384_ok(int64_t M, int64_t N, int64_t K, int64_t ldmax, int epilogue, int64_t rpb, const int64_t* blk) {
-    if (blk && (blk[0] != 62 || blk[2] != 62)) return false;
-    if (M < G384_BM || M % G384_BM != 0 || N % G384_BN != 0 || K % G384_BK != 0 || K < 2 * G384_BK) return false;
-    if (M >= (1ll << 31) || (M / G384_BM) * (N / G384_BN) >= (1ll << 31)) return false;
-    if (ldmax < K || (G384_BM * ldmax + 4096) * 2 >= (1ll << 31)) return false;
-    if (epilogue == DRN_EPI_GATE_RES) {
-        if (rpb <= 0 || rpb > M) rpb = M;
-        if (rpb % G384_BM != 0) return false;
-    }
-    return true;
-}
-
-// called from gemm.hip (tile kernel 5); pointer / alignment arguments already validated there
+// called from gemm.hip (tile kernel 5); pointer / alignment arguments already validated there.  drn_gemm384_ok (gemm_plan.h) is what
+// the kernel needs beyond those checks: the planner asks it before it names this kernel, and nothing is launched without it
+static_assert(G384_BM == 384 && G384_BN == 256 && G384_BK == 64, "drn_gemm384_ok (gemm_plan.h) spells the tile out");
 int drn_gemm384_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                          int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,
                          void* stream, const int64_t* blk) {
-    int64_t ldmax = lda > ldw ? lda : ldw;
-    if (ldc > ldmax) ldmax = ldc;
-    if (epilogue == DRN_EPI_GATE_RES && ldr > ldmax) ldmax = ldr;
-    if (lda < K || ldw < K || !drn_gemm384_ok(M, N, K, ldmax, epilogue, rpb, blk)) return DRN_EINVAL;
+    if (lda < K || ldw < K || !drn_gemm384_ok(M, N, K, gemm_ldmax(lda, ldw, ldc, ldr, epilogue), epilogue, rpb, blk)) return DRN_EINVAL;
     if (rpb > M || rpb <= 0) rpb = M;
     hipStream_t st = (hipStream_t)stream;
     switch (epilogue) {

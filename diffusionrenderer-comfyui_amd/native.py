@@ -71,6 +71,7 @@ SIGNATURES = {
     "drn_gemm_tile_choice": [_L, _L],
     "drn_gemm_force_tile": [_I],
     "drn_gemm_plan_choice": [_L, _L, _L, _L, _P],
+    "drn_gemm_plan_describe": [_L, _L, _L, _L, _L, _L, _L, _I, _L, _L, _L, _I, POINTER(c_int64), _I],
     "drn_gemm_force_res_prefetch": [_I],
     "drn_gemm_tall_force_shape": [_I],
     "drn_mx_quant_bf16": [_P, _L, _L, _L, _P, _P, _P],

@@ -107,6 +107,13 @@ void drn_gemm_force_tile(int tile);
  * (fewer than the clip has: a tail launch follows).  rows_per_batch: rows of one clip (<= 0: M).  drn_gemm_force_tile(5) selects
  * the 384x256 kernel for every launch; one it cannot take returns DRN_EINVAL. */
 int drn_gemm_plan_choice(int64_t M, int64_t N, int64_t K, int64_t rows_per_batch, int64_t* main_rows);
+/* every launch drn_gemm_bf16 / drn_gemm_bf16_blocked (block_cols as there, 0: plain) would make of these arguments, nothing launched:
+ * up to `cap` records of four int64 in `out` (may be NULL) - kernel, first row, rows, rows_per_batch passed on - in launch order;
+ * returns their number, -1 where the call would return DRN_EINVAL.  Kernels: 0 / 1 / 2 / 5 as above, 6 = the few-token kernel.  It
+ * is the planner the GEMM entries run, not a description of it.  splits > 1: the one slice launch of drn_gemm_bf16_splitk, its
+ * kernel 6, 1 (256-row slices) or 0 (128x128 slices).  ldr is read with DRN_EPI_GATE_RES only. */
+int drn_gemm_plan_describe(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int epilogue,
+                           int64_t rows_per_batch, int64_t a_block_cols, int64_t c_block_cols, int splits, int64_t* out, int cap);
 /* tuning hook (tests / A-B runs): the gated-residual epilogue of the 256x256 kernel takes its residual tile through LDS, requested
  * under the last two K steps, when the launch allows it (whole tiles inside one clip, an even number >= 4 of K steps, 16-byte
  * residual rows); 0 makes every launch load it after the loop as the other kernels do (same bits), 1 restores the default,

@@ -153,7 +153,7 @@ def store_standin(buffer, view, value, mutant=None):
 
 # ------------------------------------------------------------------------------------------------ GEMM
 GEMM_TILE_ROWS = {0: 128, 1: 256, 2: 144, -1: 128}     # csrc/gemm.hip BM, gemm256s.hip TB, gemm144.hip TM; automatic dispatch
-#                                                         takes the 128-row kernel at N = 256 (pick_gemm_tile: N / 256 tiles per
+#                                                         takes the 128-row kernel at N = 256 (gemm_pick_tile: N / 256 tiles per
 #                                                         tile row never fill 3/4 of a round at these M)
 # what ulp_diff_ok is given per epilogue: the bounds tests/test_kernels_gpu.py states (test_gemm_plain; test_gemm256_kernel)
 GEMM_BOUND = {EPI_NONE: dict(max_ulp=1, frac_exact=0.98), EPI_GELU: dict(max_ulp=2, frac_exact=0.97),
@@ -190,7 +190,7 @@ def _gemm_grid():
     cases.append(GemmCase("tall0", -1, 512, 12288, 64, EPI_GELU, True, False, 256, 1, 1630))
     # clips stacked along the rows.  4608 x 4096 per clip runs as ONE launch of the 144-row kernel over both clips
     # (drn_gemm_tile_choice(4608, 4096) == 2: no tail split); 9472 x 4096 per clip takes the 256^2 kernel with a tail split
-    # (37 x 16 tiles = 2 rounds + 80: 32 tile rows, then 1280 rows on the 128^2 kernel), so gemm_impl loops gemm_clip per clip
+    # (37 x 16 tiles = 2 rounds + 80: 32 tile rows, then 1280 rows on the 128^2 kernel), so every clip gets its own two launches
     cases.append(GemmCase("batched", -1, 2 * 4608, 4096, 128, EPI_GATE_RES, False, True, 4608, 1, 1640))
     cases.append(GemmCase("batched", -1, 2 * 9472, 4096, 128, EPI_GATE_RES, True, False, 9472, 1, 1641))
     return cases
@@ -658,7 +658,7 @@ def place_planes(P, M, cols, ld, gap, device, value=None, pad_rows=2):
 
 
 def gemm_cost_model(M, N):
-    """(tile, cost) of csrc/gemm.hip's pick_gemm_tile under its defaults (tests/test_dit_refs_cpu.py holds it to
+    """(tile, cost) of csrc/gemm_plan.h's gemm_pick_tile under its defaults (tests/test_sp_slab_refs_cpu.py holds it to
     drn_gemm_tile_choice): 0 = 128 x 128, 1 = 256 x 256, 2 = 144 x 256."""
     if N < 256 or N % 256:
         return 0, 1e30
@@ -671,9 +671,9 @@ def gemm_cost_model(M, N):
 
 
 def gemm_plan_rows(M, N, blocked=True):
-    """(rows of the first launch, its tile) as gemm_plan_rows of csrc/gemm.hip plans ONE clip: the rows that fill whole rounds of
-    256 x 256 workgroups, the rest left to a second launch (gemm_clip's recursion) when that is cheaper.  A blocked launch never
-    leaves a tail to the 128 x 128 kernel."""
+    """(rows of the first launch, its tile) as gemm_plan_clip of csrc/gemm_plan.h plans ONE clip without the 384-row tile: the rows
+    that fill whole rounds of 256 x 256 workgroups, the rest left to the launches after it when that is cheaper.  A blocked launch
+    never leaves a tail to the 128 x 128 kernel."""
     tile, cost_all = gemm_cost_model(M, N)
     if tile != 1:
         return M, tile
@@ -686,6 +686,53 @@ def gemm_plan_rows(M, N, blocked=True):
     if blocked and tail_tile == 0:
         cost_tail = 1e30
     return (tm_main * 256 if -(-tm_main * tn // 256) + cost_tail + 0.02 < cost_all - 0.05 else M), tile
+
+
+GEMM384_MEASURED = ((18432, 4096, 16384),)             # the shapes on which the dispatcher takes the 384 x 256 tile by default
+
+
+def gemm384_ok(M, N, K, ldmax, epi=EPI_NONE, rpb=0):
+    """The 384 x 256 kernel's preconditions on a plain launch (drn_gemm384_ok): whole tiles, >= 2 K steps, a tile within 32-bit lane
+    offsets, and with the gated residual every tile inside one clip."""
+    if M < 384 or M % 384 or N % 256 or K % 64 or K < 128 or ldmax < K or (384 * ldmax + 4096) * 2 >= 1 << 31:
+        return False
+    return epi != EPI_GATE_RES or (rpb if 0 < rpb <= M else M) % 384 == 0
+
+
+def gemm_tall_slices(M, N, K):
+    """gemm_tall.hip's rule for ONE clip of M rows: 1 = the few-token kernel unsplit, n > 1 = its n K slices, 0 = another kernel."""
+    if M != 256 or N % 64 or K % 64:
+        return 0
+    if N // 64 >= 192:
+        return 1
+    return next((s for s in (2, 4, 8) if 192 <= N // 64 * s <= 256 and K // 64 % s == 0 and 1024 <= K // s <= 2048), 0)
+
+
+def gemm_plan_launches(M, N, K, ld=None, epi=EPI_NONE, rpb=0, blocked=False):
+    """Every launch of a drn_gemm_bf16 / _blocked call under the default settings as [(kernel, first row, rows, rows_per_batch)],
+    None where the call is refused; kernel 5 = 384 x 256, 6 = the few-token kernel.  ld = (lda, ldw, ldc, ldr), contiguous when None.
+    An independent model of csrc/gemm_plan.h (tests/test_gemm_plan_cpu.py holds drn_gemm_plan_describe to it)."""
+    lda, ldw, ldc, ldr = ld or (K, K, N, N)
+    ldmax = max(lda, ldw, ldc, ldr if epi == EPI_GATE_RES else 0)
+    batched = not blocked and 0 < rpb < M and M % rpb == 0
+    Mb = rpb if batched else M
+    if not blocked and M % 256 == 0 and lda >= K and gemm_tall_slices(Mb, N, K) == 1:
+        return [(6, 0, M, rpb if rpb > 0 else M)]
+    if not batched and epi == EPI_GATE_RES and rpb < M:    # ragged clips, blocked clips: one launch, the tile of the whole problem
+        tile = gemm_cost_model(M, N)[0]
+        return None if blocked and tile == 0 else [(tile, 0, M, rpb)]
+    clip, row = [], 0
+    while row < Mb:
+        rows, tile = gemm_plan_rows(Mb - row, N, blocked)
+        if not blocked and (Mb - row, N, K) in GEMM384_MEASURED and gemm384_ok(Mb - row, N, K, ldmax):
+            rows, tile = Mb - row, 5
+        if blocked and tile == 0:
+            return None
+        clip.append((tile, row, rows, rows))
+        row += rows
+    if len(clip) == 1:
+        return [(clip[0][0], 0, M, Mb)]
+    return [(t, b * Mb + r, n, n) for b in range(M // Mb) for t, r, n, _ in clip]
 
 
 # tile: 1 / 2 = drn_gemm_force_tile, -1 = automatic dispatch.  layout: "a" = A in planes of abc columns, "c" = C in planes of cbc
@@ -741,7 +788,7 @@ def _gemm_blocked_grid():
     # the output projection: A in 8 planes of 128 columns, gated residual in place
     for r, rows in enumerate((2304, 9216)):
         cases.append(BlockedCase(-1, rows, 4096, 1024, EPI_GATE_RES, "a", 128, 0, r == 0, True, rows, False, 7450 + r))
-    # The tail split of gemm_clip (rows that fill whole rounds of 256 x 256 workgroups, the rest in a second launch that advances
+    # The tail split of gemm_plan_clip (rows that fill whole rounds of 256 x 256 workgroups, the rest in a second launch that advances
     # A by M_main * lda inside every plane).  drn_gemm_tile_choice / gemm_plan_rows over M < 20000: the band shape 9216 x 8192 above
     # is one (8192 rows on the 256-row kernel, 1024 on the 144-row one); the smallest is 4817 x 8192 (4096 rows, then a ragged 721
     # on the 144-row kernel).  The latter with A planes too, and with the gated residual in place.

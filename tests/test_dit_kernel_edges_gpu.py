@@ -12,6 +12,7 @@ import torch
 import dit_refs as R
 from conftest import rel_l2
 from oracle import dit_oracle as O
+from test_gemm_plan_cpu import describe
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +104,11 @@ def test_gemm_edges(pkg, gpu, c):
     assert ok, msg
     if c.path == "batched":
         if c.rpb == 9472:
-            assert pkg.native.load_library().drn_gemm_tile_choice(c.rpb, c.N) == 1, "one clip must take the 256^2 kernel (tail split)"
+            lib = pkg.native.load_library()
+            assert lib.drn_gemm_tile_choice(c.rpb, c.N) == 1, "one clip must take the 256^2 kernel (tail split)"
+            ld = (c.K + 64, c.K, c.N + 64, c.N + 128) if c.strided else None
+            assert describe(lib, c.M, c.N, c.K, ld=ld, epi=c.epi, rpb=c.rpb) == \
+                [(k, b * c.rpb + r0, n, n) for b in range(c.M // c.rpb) for k, r0, n in ((1, 0, 8192), (0, 8192, 1280))], "tail split"
         for b in range(c.M // c.rpb):
             one, g1 = _gemm_launch(pkg, gpu, c, a, w, gate, res, rows=(b * c.rpb, (b + 1) * c.rpb))
             R.assert_guard_intact(*g1[0])

@@ -12,7 +12,7 @@ TILE384 = 5
 S = 18432
 # the four block linears of the headline step (cfg 3, 18 432 tokens): (N, K), and whether the A/B enabled the tile for them
 HEADLINE = {"qkv": (12288, 4096), "out-proj": (4096, 4096), "mlp-up": (16384, 4096), "mlp-down": (4096, 16384)}
-ENABLED = ("mlp-down",)     # the HEADLINE shapes on csrc/gemm.hip's kGemm384Measured list (profiles/gemm384.txt: the others tie)
+ENABLED = ("mlp-down",)     # the HEADLINE shapes on csrc/gemm_plan.h's kGemm384Measured list (profiles/gemm384.txt: the others tie)
 
 
 def _plan(lib, M, N, K, rpb=0):

@@ -169,7 +169,7 @@ def test_gemm_blocked_refusals_write_nothing(pkg, gpu):
         "N = 384 (128 x 128 kernel)": call(M=2304, N=384, cbc=0, ldc=384, c_str=0, tile=-1),
         "forced tile 0, A planes": call(M=2304, N=4096, tile=0),
         "forced tile 0, C planes only": call(M=2304, N=4096, abc=0, lda=128, a_str=0, tile=0),
-        # gemm_impl's branch for several clips under one launch must refuse like gemm_clip does
+        # the plan's branch for several clips under one launch must refuse like the plan of one clip does
         "gated, two clips, 128 x 128 shape": call(M=300, N=256, epi=2, rpb=150, cbc=0, ldc=256, c_str=0, tile=-1, ldr=4096),
         "gated, ragged clips, 128 x 128 shape": call(M=301, N=256, epi=2, rpb=151, cbc=0, ldc=256, c_str=0, tile=-1, ldr=4096),
         "gated, two clips, forced tile 0": call(M=300, N=512, epi=2, rpb=150, tile=0, ldr=4096),
