@@ -117,6 +117,8 @@ SIGNATURES = {
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "drn_env_cubes": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
+    "drn_env_project_seq": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "drn_fit_frames": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_fit_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "drn_restore_frames_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P],
@@ -861,6 +863,46 @@ def env_project(cube, vec, rot, log_scale=10000.0, out=None):
         assert t.dtype == torch.float32 and t.shape == (3, T, H, W) and t.is_contiguous()
     _check(load_library().drn_env_project(_ptr(cube), R, _ptr(vec), _ptr(rot), _ptr(out[0]), _ptr(out[1]), T, H, W, log_scale,
                                           _stream()), "drn_env_project")
+    return out
+
+
+def env_cubes(latlong, grid, n0=0, n=None, brightness=1.0, flip=False, roll=0, out=None):
+    """The cube maps of panoramas n0 .. n0 + n - 1 of an env-map sequence in one launch (drn_env_cubes).  latlong [N, He, We, 3]
+    raw (preprocess_envmap.process_comfyui_sequence), grid [6, R, R, 2] (preprocess_envmap.cube_sample_grid), fp32 and
+    contiguous; roll in [0, We) -> [n, 6, R, R, 3] fp32.  out: such a tensor to write into."""
+    for t in (latlong, grid):
+        assert t.dtype == torch.float32 and t.is_contiguous(), "contiguous fp32 tensor required"
+    N, He, We = latlong.shape[:3]
+    R = grid.shape[1]
+    assert latlong.shape == (N, He, We, 3) and grid.shape == (6, R, R, 2)
+    n = N - n0 if n is None else n
+    if out is None:
+        out = torch.empty((n, 6, R, R, 3), dtype=torch.float32, device=latlong.device)
+    assert out.dtype == torch.float32 and out.shape == (n, 6, R, R, 3) and out.is_contiguous()
+    _check(load_library().drn_env_cubes(_ptr(latlong), _ptr(grid), _ptr(out), N, He, We, R, n0, n, float(brightness),
+                                        1 if flip else 0, int(roll), _stream()), "drn_env_cubes")
+    return out
+
+
+def env_project_seq(cubes, cube_of, vec, rot, log_scale=10000.0, out=None, t0=0):
+    """drn_env_project with a cube map per frame (drn_env_project_seq).  cubes [n_cubes, 6, R, R, 3], vec [H, W, 3], rot [T, 2] on
+    the device, fp32 and contiguous; cube_of int32 [T] on the HOST, every value checked to lie in [0, n_cubes) and then uploaded
+    -> (env_ldr, env_log).  out: a pair of [3, T_all, H, W] tensors of which frames t0 .. t0 + T - 1 are written."""
+    for t in (cubes, vec, rot):
+        assert t.dtype == torch.float32 and t.is_contiguous(), "contiguous fp32 tensor required"
+    n_cubes, R, (H, W), T = cubes.shape[0], cubes.shape[2], vec.shape[:2], rot.shape[0]
+    assert cubes.shape == (n_cubes, 6, R, R, 3) and vec.shape == (H, W, 3) and rot.shape == (T, 2)
+    assert not cube_of.is_cuda and cube_of.dtype == torch.int32 and cube_of.shape == (T,), "cube_of: int32 [T] on the host"
+    assert 0 <= int(cube_of.min()) and int(cube_of.max()) < n_cubes, "cube_of outside the cube maps"
+    if out is None:
+        out = (torch.empty((3, T, H, W), dtype=torch.float32, device=cubes.device),
+               torch.empty((3, T, H, W), dtype=torch.float32, device=cubes.device))
+    T_all = out[0].shape[1]
+    for t in out:
+        assert t.dtype == torch.float32 and t.shape == (3, T_all, H, W) and t.is_contiguous()
+    table = cube_of.contiguous().to(cubes.device)
+    _check(load_library().drn_env_project_seq(_ptr(cubes), n_cubes, _ptr(table), R, _ptr(vec), _ptr(rot), _ptr(out[0]),
+                                              _ptr(out[1]), T, t0, T_all, H, W, log_scale, _stream()), "drn_env_project_seq")
     return out
 
 

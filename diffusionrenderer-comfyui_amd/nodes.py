@@ -213,10 +213,11 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
                   env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
-                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None):
+                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None, env_sequence=False):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
     (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit);
-    restore_guide: its guide (a fit.RestoreGuide), or None for the plain way back."""
+    restore_guide: its guide (a fit.RestoreGuide), or None for the plain way back.  env_sequence: frame t is lit by frame t of
+    env_map, which then holds one frame per frame of the clip as handed in (or a single one)."""
     _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
@@ -236,10 +237,12 @@ def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_bri
     # env-map conditions (env_ldr / env_log / env_nrm): preprocessing outside the denoise loop (reference :283-304); env_spin
     # degrees turn the light about +Y over the clip (every frame projected on the GPU by drn_env_project), 0 = static.
     # Built for the WHOLE clip and the WHOLE picture also when it is rendered in windows or tiles: the pipeline cuts them per
-    # window and crops them per tile like the G-buffers (they are per-pixel view-direction images)
+    # window and crops them per tile like the G-buffers (they are per-pixel view-direction images).  A light sequence is checked
+    # against the clip's own frame count; over frames the fit padded, its last light repeats and is cut away with them
     from . import preprocess_envmap as pe
     env = pe.envmap_conditions(env_map, (H, W), T, env_format, env_brightness, env_flip_horizontal, env_rotation,
-                               device=getattr(pipeline, "device", "cuda"), env_spin=env_spin)
+                               device=getattr(pipeline, "device", "cuda"), env_spin=env_spin, env_sequence=env_sequence,
+                               clip_frames=T if keep is None else keep)
     data_batch["env_ldr"] = env["env_ldr"].expand(B, -1, -1, -1, -1)
     data_batch["env_log"] = env["env_log"].expand(B, -1, -1, -1, -1)
     data_batch["env_nrm"] = env["env_nrm"].expand(B, -1, T, -1, -1)
@@ -327,6 +330,10 @@ class Cosmos1InverseRenderer:
         return tuple(images)
 
 
+_ENV_SEQUENCE_TOOLTIP = ("env_map is a light that changes over the clip: frame t is lit by frame t of env_map, which must hold "
+                         "one frame per frame of the clip (or a single one). Off: only its first frame is used")
+
+
 class Cosmos1ForwardRenderer:
     @classmethod
     def INPUT_TYPES(s):
@@ -340,6 +347,7 @@ class Cosmos1ForwardRenderer:
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
+                         "env_sequence": ("BOOLEAN", {"default": False, "tooltip": _ENV_SEQUENCE_TOOLTIP}),
                          **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
         }
 
@@ -350,11 +358,11 @@ class Cosmos1ForwardRenderer:
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
-                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel"):
+                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", env_sequence=False):
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
                               env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                              tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join),)
+                              tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join, env_sequence=env_sequence),)
 
 
 class LoadHDRImage:
@@ -396,6 +404,7 @@ class Cosmos1Relight:
                          "env_flip_horizontal": ("BOOLEAN", {"default": False}),
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
+                         "env_sequence": ("BOOLEAN", {"default": False, "tooltip": _ENV_SEQUENCE_TOOLTIP}),
                          **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs()},
         }
 
@@ -407,7 +416,8 @@ class Cosmos1Relight:
     def run_relight(self, inverse_pipeline, forward_pipeline, image, env_map, guidance=0.0, forward_guidance=0.0, seed=42,
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
-                    tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0):
+                    tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
+                    env_sequence=False):
         """Tiles, and the way they are joined, apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
         restore_guide = 'source': the input picture guides the way back of all six outputs."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
@@ -429,7 +439,8 @@ class Cosmos1Relight:
         inputs = {k: inputs[k] for k in ("depth", "normal", "roughness", "metallic", "base_color")}
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
-                              restore_plan=rplan, tiles=tiles, tile_join=tile_join, restore_guide=guide)
+                              restore_plan=rplan, tiles=tiles, tile_join=tile_join, restore_guide=guide,
+                              env_sequence=env_sequence)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:

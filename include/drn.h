@@ -1,6 +1,7 @@
 /* drn.h - C ABI of libdrn.so: the MI355X (gfx950) kernels behind the DiffusionRenderer
  * denoising hot path (CleanGeneralDIT forward + EDM sampler steps + Cosmos CV8x8x8 tokenizer),
- * the forward renderer's per-frame environment-light projection (drn_env_project), the
+ * the forward renderer's per-frame environment-light projection (drn_env_project; with a light per frame drn_env_cubes and
+ * drn_env_project_seq), the
  * nodes' clip ingest with a fit to the model's grid (drn_fit_frames), its way back on the
  * uint8 outputs (drn_restore_frames_u8, with the source as a guide drn_restore_guided_u8) and the join of spatial tiles on them
  * (drn_tile_blend_u8).
@@ -517,6 +518,35 @@ int drn_postprocess_window_u8(const void* video, const void* prev_tail, const vo
  * or W < 1, T*H*W >= 2^31, a pointer not 4-byte aligned. */
 int drn_env_project(const float* cube, int R, const float* vec, const float* rot, float* env_ldr, float* env_log,
                     int T, int H, int W, float log_scale, void* stream);
+
+/* ---- environment light that changes over the clip: the cube maps of a run of panoramas (preprocess_envmap.py:263-286
+ * apply_hdr_preprocessing, then :161-206 latlong_to_cubemap_official, per frame of an env_map batch of which
+ * process_comfyui_tensor :247-261 keeps frame 0 only).  One launch over n*6*R*R cube texels, one thread per texel of one panorama
+ * (12 contiguous bytes out).  The sampling grid does not depend on the frame: the host computes it once with the torch
+ * expressions of :161-206 (preprocess_envmap.cube_sample_grid), so the kernel evaluates no transcendental.  Per texel and
+ * channel, grid_sample(mode="bilinear", padding_mode="border", align_corners=False) in drn_env_project's arithmetic and order
+ * (unnormalise and clamp each axis with its own size - the product and the `- 1` in ONE fused multiply-add, as torch's grid_sample
+ * builds contract them, where drn_env_project's cube lookup rounds twice - weights `(x0 + 1) - ix` .., nw + ne + sw + se, an
+ * out-of-range neighbour contributes 0 * w, no contraction anywhere else).  The clean-up of :263-286 is elementwise and is applied to every tap as it is read:
+ * `* brightness` only when brightness != 1.0, nan -> 0, +inf -> 65504, -inf -> 0, clamp to [0, 65504].  Flip and roll are index
+ * arithmetic on the source column, the flip before the roll: column c of the cleaned panorama is raw column
+ * j = (c - roll) mod We, or We - 1 - j with flip; roll = int(We * env_rot / 360) mod We comes from the host.
+ *   latlong [N,He,We,3] raw; grid [6,R,R,2] = (x, y) in [-1, 1]; cubes [n,6,R,R,3] = the cube maps of panoramas n0 .. n0+n-1.
+ *   All fp32 and contiguous.
+ * DRN_EINVAL (nothing launched): a null pointer, N, He, We or R < 1, n0 < 0, n < 1, n0 + n > N, roll outside [0, We), a pointer
+ * not 4-byte aligned, N*He*We*3 or n*6*R*R*3 >= 2^31. */
+int drn_env_cubes(const float* latlong, const float* grid, float* cubes, int N, int He, int We, int R, int n0, int n,
+                  float brightness, int flip, int roll, void* stream);
+
+/* ---- drn_env_project with a cube map per frame (the same lines, :440-450 / :119-140; the same kernel): frame t looks up cube map
+ * cube_of[t] of cubes [n_cubes,6,R,R,3] under rot[t], and is stored at frame t0 + t of outputs [3,T_all,H,W], of which no other
+ * frame is touched - so a clip is projected in chunks of frames whose cube maps are built chunk by chunk.  cube_of int32 [T] and
+ * rot [T,2] on the device.  cube_of is clamped into [0, n_cubes) before use; what it should hold is checked on the host
+ * (native.env_project_seq).  With every cube_of[t] = 0, t0 = 0 and T_all = T this is drn_env_project, bit for bit.
+ * DRN_EINVAL (nothing launched): what drn_env_project refuses, a null cube_of, n_cubes < 1, t0 < 0, t0 + T > T_all,
+ * T_all*H*W >= 2^31, cube_of not 4-byte aligned. */
+int drn_env_project_seq(const float* cubes, int n_cubes, const int32_t* cube_of, int R, const float* vec, const float* rot,
+                        float* env_ldr, float* env_log, int T, int t0, int T_all, int H, int W, float log_scale, void* stream);
 
 /* ---- clip ingest with a fit to the model's grid (the nodes' `image.permute(0, 4, 1, 2, 3) * 2.0 - 1.0`, nodes.py:156-190, with
  * a resize, a crop and a time padding in front that the reference does not have; plan and torch specification: fit.py).
