@@ -93,6 +93,47 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The uint8 post-process's two per-value pieces, shared by elementwise.hip (drn_postprocess_window_u8) and window_align.hip
+// (drn_postprocess_window_align_u8).  Both are bit-exact restatements of unfused torch fp32 ops, so contraction is switched off
+// inside them whatever the including file does.
+// One pixel's chain (diffusion_renderer_pipeline.py:299-318 with every bf16 rounding kept): c[] = the pixel's three bf16 channel
+// values (widened), o[] = its bytes.
+__device__ __forceinline__ void postprocess_pixel(float (&c)[3], int normalize, uint8_t (&o)[3]) {
+#pragma clang fp contract(off)
+    if (normalize) {
+        const float norm = rbf(sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
+        const float den = rbf(fmaxf(norm, 1e-12f));
+        // torch CPU rounds the Python scalar of a bf16 add/sub to bf16 first (0.2 -> 0.2001953125); div keeps fp32
+        float blend = rbf(rbf(norm - 0.2001953125f) / 0.2f);
+        blend = fminf(fmaxf(blend, 0.f), 1.f);
+        const float om = rbf(1.0f - blend);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float vn = rbf(c[ch] / den);
+            c[ch] = rbf(rbf(vn * blend) + rbf(c[ch] * om));
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float a = rbf(1.0f + c[ch]);
+        a = fminf(fmaxf(a, 0.f), 2.f);
+        const float u = rbf((a / 2.0f) * 255.0f);
+        o[ch] = (uint8_t)u;
+    }
+}
+
+// The cross-fade of a window's ramp frame with the carry (drn.h, drn_postprocess_window_u8).
+__device__ __forceinline__ float window_blend(float a, float b, float w) {
+#pragma clang fp contract(off)
+    // three separately rounded fp32 operations (torch's a + w * (b - a)), never an FMA; then the bf16 rounding of .to(bfloat16).
+    // Plain operators under `fp contract(off)`: hipcc lowers __fmul_rn / __fadd_rn through library code that the pragma does not
+    // reach and fuses the pair into v_pk_fma_f32 all the same (seen in the ISA).
+    const float d = b - a;
+    const float m = w * d;
+    return rbf(a + m);
+}
+
 #define DRN_CHECK_ARG(cond)            \
     do {                               \
         if (!(cond)) return DRN_EINVAL; \

@@ -781,29 +781,7 @@ extern "C" int drn_cfg_combine(const void* cond, const void* uncond, void* out, 
 
 // ------------------------------------------------------------------------------------------------
 // pipeline post-process -> uint8 (B,T,H,W,3); diffusion_renderer_pipeline.py:299-318 with every bf16 rounding kept.
-// One pixel's chain: c[] = the pixel's three bf16 channel values (widened), o[] = its bytes.
-__device__ __forceinline__ void postprocess_pixel(float (&c)[3], int normalize, uint8_t (&o)[3]) {
-    if (normalize) {
-        const float norm = rbf(sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
-        const float den = rbf(fmaxf(norm, 1e-12f));
-        // torch CPU rounds the Python scalar of a bf16 add/sub to bf16 first (0.2 -> 0.2001953125); div keeps fp32
-        float blend = rbf(rbf(norm - 0.2001953125f) / 0.2f);
-        blend = fminf(fmaxf(blend, 0.f), 1.f);
-        const float om = rbf(1.0f - blend);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float vn = rbf(c[ch] / den);
-            c[ch] = rbf(rbf(vn * blend) + rbf(c[ch] * om));
-        }
-    }
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        float a = rbf(1.0f + c[ch]);
-        a = fminf(fmaxf(a, 0.f), 2.f);
-        const float u = rbf((a / 2.0f) * 255.0f);
-        o[ch] = (uint8_t)u;
-    }
-}
+// One pixel's chain is postprocess_pixel, and the ramp's cross-fade window_blend, both in drn_common.h (window_align.hip shares them).
 
 // ------------------------------------------------------------------------------------------------
 // post-process of one WINDOW of a long clip (drn.h): frames [write_lo, write_hi) of the decoded window -> uint8, the O ramp frames
@@ -812,15 +790,6 @@ __device__ __forceinline__ void postprocess_pixel(float (&c)[3], int normalize, 
 // VEC: a lane owns 8 consecutive pixels of the frame - one 16-byte load per channel plane (two on a ramp frame) and 24 contiguous
 // output bytes as three 8-byte stores, a wave writes 1536 contiguous bytes.  Needs H * W % 8 == 0 (every plane of every frame then
 // starts 16-byte aligned, and a frame is whole groups: no partial group exists); any other shape takes the one-pixel-per-lane form.
-__device__ __forceinline__ float window_blend(float a, float b, float w) {
-    // three separately rounded fp32 operations (torch's a + w * (b - a)), never an FMA; then the bf16 rounding of .to(bfloat16).
-    // Plain operators under this file's `fp contract(off)`: hipcc lowers __fmul_rn / __fadd_rn through library code that the
-    // pragma does not reach and fuses the pair into v_pk_fma_f32 all the same (seen in the ISA).
-    const float d = b - a;
-    const float m = w * d;
-    return rbf(a + m);
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void postprocess_window_kernel(const bf16_t* __restrict__ v, const bf16_t* __restrict__ prev,
                                                                  const float* __restrict__ rw, uint8_t* __restrict__ o,

@@ -21,7 +21,7 @@ from .diffusion_renderer_config import get_config_from_tensor_shape, validate_co
 from .fit import restore_frames, restore_frames_guided
 from .model_diffusion_renderer import CleanDiffusionRendererModel
 from .tiles import blend_tile, latent_tile, plan_tiles
-from .windows import Window, plan_windows, ramp_weights
+from .windows import Window, check_window_align, plan_windows, ramp_weights
 
 _SHAPE_KEYS = ("rgb", "image", "basecolor", "normal", "depth", "roughness", "metallic")
 
@@ -46,6 +46,9 @@ class CleanDiffusionRendererPipeline:
         # become uint8
         self.window_frames = 0
         self.window_overlap = 8
+        # windows that agree (windows.align_affine): every window after the first is matched in gain and offset to the
+        # previous window's carry over the overlap, on the device, before the cross-fade; False = today's calls, today's bits
+        self.window_align = False
         # the fit's way back (fit.py): a RestorePlan -> the uint8 outputs are resampled to the source's size on the device, before
         # the D2H copy; None = the outputs keep the model's size (today's path, today's bits)
         self.restore_plan = None
@@ -255,6 +258,7 @@ class CleanDiffusionRendererPipeline:
         with each tile started from its crop of the canvas noise (`_tile_noises`)."""
         if self.tile_join not in ("pixel", "latent"):
             raise ValueError(f"tile_join must be 'pixel' or 'latent', got {self.tile_join!r}")
+        check_window_align(self.window_align, self.window_frames, self.window_overlap, self.tile_height, self.tile_width)
         if not batches:
             return []
         tiles = self._tile_plan(batches[0])
@@ -384,6 +388,9 @@ class CleanDiffusionRendererPipeline:
         shape), decode pass by pass, cross-fade with the carry of the previous window inside the uint8 post-process, resample to
         the source's size where a restore plan is set, and copy the written frames to the host.  The window's last `overlap`
         decoded frames become the next carry.  Device memory: one window's decode plus one carry per pass, whatever T is.
+        With `window_align`, a window that has a carry and is no normal pass (unit vectors have no gain or offset freedom) is first
+        matched to that carry (N.window_align_affine: the affine stays on the device), and one launch applies the affine, writes
+        the frames and hands on the ALIGNED last frames as the next carry, so every window lands in window 0's space.
 
         A clip that is one sequence is one window over the caller's own tensors (the upload cache knows them by identity) that
         writes every frame the tokenizer decoded, with no ramp and no carry.  clips: generate_video's contract for such a clip - the
@@ -424,8 +431,15 @@ class CleanDiffusionRendererPipeline:
                     if not whole and video.shape[2] != Wf:
                         raise ValueError(f"the tokenizer decoded {video.shape[2]} frames for a window of {Wf}")
                     prev = carry[c][p]                                                # None: window 0, or hard cuts
-                    u8 = N.postprocess_window_u8(video, prev, ramp if prev is not None else None, win.ramp_at, win.write_lo,
-                                                 win.write_hi or video.shape[2], flag)
+                    hand_on = O and i + 1 < len(plan)
+                    aligned = bool(self.window_align) and not whole and prev is not None and not flag
+                    if aligned:
+                        affine = N.window_align_affine(video, prev, win.ramp_at)
+                        u8, tail = N.postprocess_window_align_u8(video, prev, ramp, affine, win.ramp_at, win.write_lo, win.write_hi,
+                                                                 flag, carry_frames=O if hand_on else 0)
+                    else:
+                        u8 = N.postprocess_window_u8(video, prev, ramp if prev is not None else None, win.ramp_at, win.write_lo,
+                                                     win.write_hi or video.shape[2], flag)
                     # frames are independent: window by window = the whole clip.  Kept: those written, up to the restore plan's T
                     # (the time padding of a whole clip is cut; a windowed clip has none)
                     if self.restore_plan is not None:
@@ -434,7 +448,10 @@ class CleanDiffusionRendererPipeline:
                         outs[c][p] = torch.empty((u8.shape[0], u8.shape[1] if whole else T) + tuple(u8.shape[2:]), dtype=torch.uint8,
                                                  device="cpu" if to_host else u8.device)
                     outs[c][p][:, win.out_at:win.out_at + u8.shape[1]].copy_(u8)      # D2H straight into the clip's frames
-                    carry[c][p] = video[:, :, Wf - O:].contiguous() if O and i + 1 < len(plan) else None
+                    if aligned:
+                        carry[c][p] = tail
+                    else:
+                        carry[c][p] = video[:, :, Wf - O:].contiguous() if hand_on else None
         return [[o.numpy() if to_host else o for o in per_batch] for per_batch in outs]
 
     @staticmethod

@@ -116,6 +116,9 @@ SIGNATURES = {
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "drn_window_align_workspace_bytes": [_I, _I, _I, _I],
+    "drn_window_align_affine": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
+    "drn_postprocess_window_align_u8": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_env_project": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     "drn_env_cubes": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
     "drn_env_project_seq": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
@@ -131,6 +134,7 @@ _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_byte
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
              "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_mx_act_bytes": c_int64,
              "drn_dit_forward_mx_u_bytes": c_int64, "drn_mx_quant_calls": c_int64, "drn_dit_forward_mx_attn_bytes": c_int64,
+             "drn_window_align_workspace_bytes": c_int64,
              "drn_dit_forward_mx_gemm_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
              "drn_ln_force_kernel": None, "drn_attention_force_shape16": None}
 
@@ -846,6 +850,56 @@ def postprocess_window_u8(video, prev_tail, ramp_w, ramp_at: int, write_lo: int,
                                                     write_lo, write_hi, 1 if normalize_normal else 0, _stream()),
            "drn_postprocess_window_u8")
     return out
+
+
+def window_align_affine(video, prev_tail, ramp_at: int, moments: bool = False):
+    """The gain and offset that match one window to the previous window's carry over the overlap (drn_window_align_affine; the
+    specification: windows.align_affine).  video [B,3,Tw,H,W] bf16, prev_tail [B,3,O,H,W] bf16, O >= 1 -> affine [B,2] fp32 =
+    (g, o) on the device, never read by the host; with moments=True also the fp64 moments [B,6] behind it."""
+    _bf16(video, prev_tail)
+    B, C, Tw, H, W = video.shape
+    O = prev_tail.shape[2]
+    assert C == 3 and video.is_contiguous() and prev_tail.shape == (B, 3, O, H, W) and prev_tail.is_contiguous()
+    lib = load_library()
+    nbytes = lib.drn_window_align_workspace_bytes(B, H, W, O)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=video.device)
+    affine = torch.empty((B, 2), dtype=torch.float32, device=video.device)
+    mom = torch.empty((B, 6), dtype=torch.float64, device=video.device) if moments else None
+    _check(lib.drn_window_align_affine(_ptr(video), _ptr(prev_tail), _ptr(affine), _ptr(mom), _ptr(ws), nbytes, B, Tw, H, W, O,
+                                       ramp_at, _stream()), "drn_window_align_affine")
+    return (affine, mom) if moments else affine
+
+
+def postprocess_window_align_u8(video, prev_tail, ramp_w, affine, ramp_at: int, write_lo: int, write_hi: int,
+                                normalize_normal: bool, carry_frames: int = 0, out=None, carry_out=None):
+    """postprocess_window_u8 with the affine of window_align_affine ([B,2] fp32 on the device, or None) applied to every window
+    value in front of the cross-fade, and (carry_frames = O >= 1, or a carry_out given) the aligned last O frames written as the
+    next carry [B,3,O,H,W] bf16 by the same launch (drn_postprocess_window_align_u8) -> (uint8 frames, carry or None)."""
+    _bf16(video, prev_tail, carry_out)
+    B, C, Tw, H, W = video.shape
+    assert C == 3 and video.is_contiguous()
+    assert (prev_tail is None) == (ramp_w is None), "prev_tail and ramp_w come together"
+    O = int(carry_out.shape[2]) if carry_out is not None else int(carry_frames)
+    if prev_tail is not None:
+        assert not O or O == prev_tail.shape[2], "the carry written has the length of the carry read"
+        O = prev_tail.shape[2]
+        assert prev_tail.shape == (B, 3, O, H, W) and prev_tail.is_contiguous()
+        assert ramp_w.dtype == torch.float32 and ramp_w.shape == (O,) and ramp_w.is_contiguous()
+    if affine is not None:
+        assert affine.dtype == torch.float32 and affine.shape == (B, 2) and affine.is_contiguous()
+    if carry_out is None and carry_frames:
+        carry_out = torch.empty((B, 3, O, H, W), dtype=torch.bfloat16, device=video.device)
+    if carry_out is not None:
+        assert tuple(carry_out.shape) == (B, 3, O, H, W) and carry_out.is_contiguous()
+    shape = (B, max(write_hi - write_lo, 0), H, W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=video.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()
+    _check(load_library().drn_postprocess_window_align_u8(_ptr(video), _ptr(prev_tail), _ptr(ramp_w), _ptr(affine), _ptr(out),
+                                                          _ptr(carry_out), B, Tw, H, W, O, ramp_at, write_lo, write_hi,
+                                                          1 if normalize_normal else 0, _stream()),
+           "drn_postprocess_window_align_u8")
+    return out, carry_out
 
 
 def env_project(cube, vec, rot, log_scale=10000.0, out=None):

@@ -11,6 +11,7 @@ import torch
 from .diffusion_renderer_config import get_inverse_renderer_config
 from .diffusion_renderer_pipeline import CleanDiffusionRendererPipeline
 from .model_diffusion_renderer import CleanDiffusionRendererModel
+from .windows import check_window_align
 
 GBUFFER_INDEX_MAPPING = {"basecolor": 0, "metallic": 1, "roughness": 2, "normal": 3, "depth": 4}   # nodes.py:35-41
 INVERSE_PASSES = ["basecolor", "metallic", "roughness", "normal", "depth"]
@@ -35,7 +36,14 @@ def _window_inputs():
                                                  "length, cross-faded in pixel space"}),
             "window_overlap": ("INT", {"default": 8, "min": 0, "max": 512, "step": 1,
                                        "tooltip": "frames two neighbouring windows share (at most (window_frames - 1) / 2); "
-                                                  "0 = hard cuts"})}
+                                                  "0 = hard cuts"}),
+            "window_align": ("BOOLEAN", {"default": False,
+                                         "tooltip": "windows are independent samples: level and contrast step from one window to "
+                                                    "the next and the cross-fade only smears the step.  On: every window after the "
+                                                    "first is matched in gain and offset (one pair for the three channels) to its "
+                                                    "predecessor over the frames they share, on the GPU, before the cross-fade; "
+                                                    "normal maps are never changed.  Needs window_overlap >= 1 and no tiles; "
+                                                    "ignored where the clip fits one window"})}
 
 
 def _tile_inputs():
@@ -115,14 +123,18 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
     raise TypeError(f"Unsupported input type for '{name}': {type(image)}. Expected torch.Tensor or list of Tensors.")
 
 
-def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel"):
+def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel",
+               window_align=False):
     """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
-    (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent")."""
+    (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent"); window_align: windows matched
+    in gain and offset over the overlap (refused here, before any upload, without an overlap or with tiles)."""
+    check_window_align(window_align, window_frames, window_overlap, tiles[0], tiles[1])
     pipeline.set_model_type(model_type)
     pipeline.guidance = guidance
     pipeline.seed = seed
     pipeline.window_frames = window_frames
     pipeline.window_overlap = window_overlap
+    pipeline.window_align = bool(window_align)
     pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
     pipeline.tile_join = tile_join
     pipeline.restore_plan = None
@@ -177,11 +189,12 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                    to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0):
+                    to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0,
+                    window_align=False):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
-    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join)
+    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     guide = _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma)
     if guide is not None:
@@ -213,12 +226,12 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
                   env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
-                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None, env_sequence=False):
+                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None, env_sequence=False, window_align=False):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
     (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit);
     restore_guide: its guide (a fit.RestoreGuide), or None for the plain way back.  env_sequence: frame t is lit by frame t of
     env_map, which then holds one frame per frame of the clip as handed in (or a single one)."""
-    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join)
+    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
     # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
@@ -316,10 +329,10 @@ class Cosmos1InverseRenderer:
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
-                         tile_join="pixel", restore_guide="off", restore_sigma=12.0):
+                         tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
                                         fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join,
-                                        restore_guide=restore_guide, restore_sigma=restore_sigma)
+                                        restore_guide=restore_guide, restore_sigma=restore_sigma, window_align=window_align)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -358,11 +371,13 @@ class Cosmos1ForwardRenderer:
     def run_forward_pass(self, pipeline, depth, normal, roughness, metallic, base_color, env_map, guidance=0.0, seed=42,
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
-                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", env_sequence=False):
+                         fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", env_sequence=False,
+                         window_align=False):
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
                               env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
-                              tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join, env_sequence=env_sequence),)
+                              tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join, env_sequence=env_sequence,
+                              window_align=window_align),)
 
 
 class LoadHDRImage:
@@ -417,8 +432,8 @@ class Cosmos1Relight:
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
                     tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    env_sequence=False):
-        """Tiles, and the way they are joined, apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
+                    env_sequence=False, window_align=False):
+        """Tiles, and the way they are joined, and window_align apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
         restore_guide = 'source': the input picture guides the way back of all six outputs."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
         tiles = (tile_height, tile_width, tile_overlap)
@@ -430,7 +445,8 @@ class Cosmos1Relight:
                               restore_sigma)
         # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
-                                        fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join)
+                                        fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join,
+                                        window_align=window_align)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's
@@ -440,7 +456,7 @@ class Cosmos1Relight:
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
                               restore_plan=rplan, tiles=tiles, tile_join=tile_join, restore_guide=guide,
-                              env_sequence=env_sequence)
+                              env_sequence=env_sequence, window_align=window_align)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:

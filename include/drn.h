@@ -506,6 +506,36 @@ int drn_postprocess_window_u8(const void* video, const void* prev_tail, const vo
                               int B, int Tw, int H, int W, int O, int ramp_at, int write_lo, int write_hi,
                               int normalize_normal, void* stream);
 
+/* ---- windows that agree (windows.py align_affine / apply_affine; extends the window walk of diffusion_renderer_pipeline.py
+ * `_walk`, which is the reference's one decode + post-process, :299-318, run per window).  Two windows are independent samples
+ * and describe the same frames only over the overlap: the carry a = prev_tail [B,3,O,H,W] and the new window's frames
+ * v = video[:, :, ramp_at : ramp_at + O], both bf16.  Per pass b, over all 3*O*H*W values and in fp64: the population moments
+ * n, mean_a, mean_v, var_a, var_v, cov; the gain g = sqrt(var_a / var_v) (moment matching, not the regression slope), g = 1 where
+ * var_a or var_v < 2^-20 or cov <= 0, clamped to [0.5, 2]; the offset o = mean_a - g * mean_v; any non-finite moment gives (1, 0).
+ *   affine [B,2] fp32 = (g, o), each rounded to fp32 once; moments [B,6] fp64 = (n, mean_a, mean_v, var_a, var_v, cov) or NULL.
+ * Store-and-sum, no atomics, identical bits run to run: blocks reduce fixed 8192-value chunks of one pass and channel to five fp64
+ * partials (sum a, v, a^2, v^2, a v; products exact in fp32) in `workspace`, then one small launch adds them in index order (64
+ * contiguous runs, then the runs in order) and evaluates the rules.  Two launches, no host read, no synchronisation.  H * W % 8 == 0 with 16-byte aligned inputs reads 16 bytes
+ * per lane; anything else one value per lane.  workspace: at least drn_window_align_workspace_bytes(B, H, W, O) bytes (host
+ * arithmetic only; 0 for a non-positive size), 8-byte aligned, not initialised by the caller.
+ * DRN_EINVAL (nothing launched): a null video / prev_tail / affine / workspace, O < 1, ramp_at < 0, ramp_at + O > Tw, a short
+ * workspace, video / prev_tail off 2 bytes, affine off 4, moments / workspace off 8, a non-positive size, B > 65535. */
+int64_t drn_window_align_workspace_bytes(int B, int H, int W, int O);
+int drn_window_align_affine(const void* video, const void* prev_tail, void* affine, void* moments, void* workspace,
+                            int64_t workspace_bytes, int B, int Tw, int H, int W, int O, int ramp_at, void* stream);
+
+/* ---- drn_postprocess_window_u8 with two more pointers (the same `_walk` lines, and the carry copy `video[:, :, Tw - O:]` behind
+ * them).  affine [B,2] fp32 on the device or NULL: every window value the kernel reads becomes bf16(fp32(g * x) + o) with pass
+ * b's (g, o) - two separately rounded fp32 operations, no FMA - before the cross-fade, the normal blend and the clamp chain.
+ * carry_out [B,3,O,H,W] bf16 or NULL: receives frames [Tw - O, Tw) of the window, aligned and not cross-faded, in the same launch
+ * (blocks stride over the written frames, then the carry frames); it must not be prev_tail or video.  affine = NULL skips the
+ * arithmetic: out_u8 holds drn_postprocess_window_u8's bytes and carry_out the raw tail.  Bit-exact.
+ * The 8-pixels-per-lane form additionally needs carry_out 16-byte aligned.  DRN_EINVAL (nothing launched): every refusal of
+ * drn_postprocess_window_u8, affine off 4 bytes, carry_out off 2, carry_out with O < 1, carry_out == prev_tail or video. */
+int drn_postprocess_window_align_u8(const void* video, const void* prev_tail, const void* ramp_w, const void* affine,
+                                    void* out_u8, void* carry_out, int B, int Tw, int H, int W, int O, int ramp_at,
+                                    int write_lo, int write_hi, int normalize_normal, void* stream);
+
 /* ---- environment light of the forward renderer, turning about +Y over the clip (preprocess_envmap.py:440-450 with the unused
  * per-frame hook `y_rot = rotate_y(0.0)` (:340-348, :442) filled in, then hdr_mapping_official :119-140 and the `* 2 - 1` /
  * permute of nodes.py:283-304).  One launch over T*H*W pixels, one thread per output pixel of one frame: the direction
