@@ -16,5 +16,8 @@ rc=$?
 # the slab GEMM and the regroup kernel at plane, tile and clip edges (tests/test_sp_slab_kernels_gpu.py), one line per case
 # -> sp_slab_parity.txt in the output directory (copied to profiles/sp_slab_parity.txt under that file's header)
 grep -o "sp-slab-edge .*" "$out/parity_full.log" | cut -c1-260 > "$out/sp_slab_parity.txt"
+# every finite bf16 value through the GELU, gated-residual and SiLU arithmetic (tests/test_value_sweep_gpu.py), one line per case
+# -> value_sweep_parity.txt in the output directory (copied to profiles/value_sweep_parity.txt under that file's header)
+grep -o "value-sweep .*" "$out/parity_full.log" | cut -c1-260 > "$out/value_sweep_parity.txt"
 tail -5 gpurun_out/parity.txt
 exit $rc
