@@ -20,6 +20,7 @@ from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
 from .fit import restore_frames, restore_frames_guided
 from .model_diffusion_renderer import CleanDiffusionRendererModel
+from .sampler import check_sampler
 from .tiles import blend_tile, latent_tile, plan_tiles
 from .windows import Window, check_window_align, plan_windows, ramp_weights
 
@@ -66,7 +67,11 @@ class CleanDiffusionRendererPipeline:
         # sampling: ONE noisy latent canvas for the picture, every tile's Euler step cross-faded into it at every step, so that
         # neighbours agree; needs tile_overlap on the tokenizer's 8-grid and a canvas-shaped init_noise
         self.tile_join = "pixel"
-        self.device = torch.device("cuda")     # torch "cuda" == HIP on ROCm (reference :81)
+        # the sampler of the denoising loop (sampler.py): "euler" = the reference's first-order EDM Euler (today's
+        # calls, today's bits); "dpmpp_2m" = DPM-Solver++(2M), second order at the same cost per step, so `num_steps` can be lower;
+        # not with tile_join = "latent"
+        self.sampler = "euler"
+        self.device = torch.device("cuda")    # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
         self.model = None
@@ -258,6 +263,7 @@ class CleanDiffusionRendererPipeline:
         with each tile started from its crop of the canvas noise (`_tile_noises`)."""
         if self.tile_join not in ("pixel", "latent"):
             raise ValueError(f"tile_join must be 'pixel' or 'latent', got {self.tile_join!r}")
+        check_sampler(self.sampler, self.tile_join)
         check_window_align(self.window_align, self.window_frames, self.window_overlap, self.tile_height, self.tile_width)
         if not batches:
             return []
@@ -469,6 +475,8 @@ class CleanDiffusionRendererPipeline:
         C = self.config["latent_shape"][0]
         _, _, T, H, W = video_tensor.shape
         state_shape = [C, (T - 1) // 8 + 1, H // 8, W // 8]
+        # (under "euler" the call is the reference's, argument for argument)
+        other = {} if self.sampler == "euler" else {"sampler": self.sampler}
         return self.model.generate_samples_from_batch(data_batch, guidance=self.guidance, state_shape=state_shape,
                                                       num_steps=self.num_steps, is_negative_prompt=False,
-                                                      seed=effective_seed, init_noise=init_noise)
+                                                      seed=effective_seed, init_noise=init_noise, **other)

@@ -7,7 +7,9 @@ CleanDiffusionRendererModel :98-234), so the pipeline above it is unchanged.  Di
     load_state_dict() with the reference's strict parameter names and are repacked once;
   * scheduler scalars are evaluated on the host with the reference's own fp32 torch expressions and the
     latent update runs in fused elementwise kernels (bit-exact with the unfused fp32 reference ops);
-  * sigma values never leave the host, so the denoising loop has no device->host synchronisation.
+  * sigma values never leave the host, so the denoising loop has no device->host synchronisation;
+  * an opt-in second-order sampler, `sampler="dpmpp_2m"` (sampler.py): same schedule and model calls, fewer steps for the same
+    answer; the default "euler" is the reference's loop, call for call.
 """
 from typing import Any, Dict, Optional, Tuple
 
@@ -16,6 +18,7 @@ import torch
 from torch import Tensor
 
 from . import native as N
+from . import sampler as S
 from .diffusion_renderer_config import get_inverse_renderer_config
 from .dit_engine import HipDiT
 from .synthetic_weights import dit_param_shapes
@@ -242,9 +245,12 @@ class CleanDiffusionRendererModel:
 
     def generate_samples_from_batch(self, data_batch: Dict, guidance: float = 0.0, seed: int = 1000,
                                     state_shape: Tuple = None, num_steps: int = 15, init_noise: Tensor = None,
-                                    **kwargs) -> Tensor:
+                                    sampler: str = "euler", **kwargs) -> Tensor:
         """The denoising loop (reference :211-234).  `init_noise` (already scaled by sigma_0) replaces the
-        device-side randn for parity runs; without it the reference's seeding convention is kept."""
+        device-side randn for parity runs; without it the reference's seeding convention is kept.
+        sampler: "euler" = the reference's first-order loop; "dpmpp_2m" = DPM-Solver++(2M) (sampler.py): the same
+        schedule, noise, passes and CFG halves, one fused launch per step between two DiT calls."""
+        S.check_sampler(sampler)
         if self.net is None:
             raise RuntimeError("weights not loaded: call load_state_dict() first")
         with torch.no_grad():
@@ -281,6 +287,8 @@ class CleanDiffusionRendererModel:
                 idx = cis + [0] * P
             else:
                 lat, idx = lat_c, cis
+            if sampler != "euler":
+                return self._sample_multistep(xt, lat, idx, P, guidance, sampler)
             for t in self.scheduler.timesteps:
                 xt_scaled = self.scheduler.scale_model_input(xt, timestep=t)
                 if guidance > 0:
@@ -292,8 +300,26 @@ class CleanDiffusionRendererModel:
                 xt = self.scheduler.step(net_output, t, xt).prev_sample
             return xt
 
+    def _sample_multistep(self, xt: Tensor, lat: Tensor, idx: list, P: int, guidance: float, sampler: str) -> Tensor:
+        """generate_samples_from_batch's loop under sampler = "dpmpp_2m", from the start noise on (the scheduler's table is set).
+        The first model input is scaled as the Euler loop scales it; from then on ONE fused step per iteration (sampler.
+        step_reference: drn_sampler_step_2m on a GPU) combines the CFG halves, updates the latent from the denoised estimate and
+        the fp32 history - one tensor of the latent's shape, rewritten in place - and writes the next DiT input, both CFG halves."""
+        plan = S.plan_steps(self.scheduler.sigmas, self.scheduler.sigma_data, sampler)
+        hist = torch.empty(xt.shape, dtype=torch.float32, device=xt.device)
+        copies = 2 if guidance > 0 else 1
+        xs = self.scheduler.scale_model_input(xt, timestep=self.scheduler.timesteps[0])
+        if guidance > 0:
+            xs = torch.cat([xs, xs], 0)
+        for t, coef in zip(self.scheduler.timesteps, plan):
+            out = self.net(x=xs, timesteps=t, latent_condition=lat, context_index=idx)
+            c, u = (out[:P], out[P:]) if guidance > 0 else (out, None)
+            xt, _, xs = S.step_reference(c, u, float(guidance), xt, hist if coef.has_hist else None, coef, copies, hist_out=hist)
+            self.scheduler.current_step += 1
+        return xt
+
     def generate_samples_joint(self, tile_batches, tiles_lat, canvas_shape: Tuple, guidance: float = 0.0, seed: int = 1000,
-                               num_steps: int = 15, init_noise: Tensor = None) -> Tensor:
+                               num_steps: int = 15, init_noise: Tensor = None, sampler: str = "euler") -> Tensor:
         """The denoising loop over the spatial tiles of ONE picture, joined in latent space at every step (tiles.py, DESIGN.md
         4i): one noisy canvas [P, *canvas_shape] exists for the whole picture; per Euler step every tile, in raster order, takes
         its crop of the current canvas through the DiT exactly as generate_samples_from_batch would, and its step result is
@@ -302,8 +328,10 @@ class CleanDiffusionRendererModel:
         tile_batches: per tile the data batch of its crop (a batch that already holds its `latent_condition` is taken as it is;
         only the condition latents and the context indices are kept).  tiles_lat: the tiles in latent units (tiles.latent_tile),
         whose written rectangles must cover the canvas.  canvas_shape: (C, F, Hc, Wc).  init_noise (already scaled by sigma_0)
-        must be canvas-shaped.  Seed, P passes stepped together, CFG and the errors are generate_samples_from_batch's."""
+        must be canvas-shaped.  Seed, P passes stepped together, CFG and the errors are generate_samples_from_batch's.  sampler:
+        only "euler" - a multistep sampler would need a history per tile, which is not built (ValueError)."""
         from . import tiles as T
+        S.check_sampler(sampler, tile_join="latent")
         if self.net is None:
             raise RuntimeError("weights not loaded: call load_state_dict() first")
         tile_batches, tiles_lat, canvas_shape = list(tile_batches), list(tiles_lat), tuple(int(v) for v in canvas_shape)

@@ -114,6 +114,7 @@ SIGNATURES = {
     "drn_edm_scale_input": [_P, _P, _L, _F, _P],
     "drn_edm_step": [_P, _P, _P, _L, _F, _F, _F, _F, _P],
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
+    "drn_sampler_step_2m": [_P, _P, _F, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _F, _P],
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_window_align_workspace_bytes": [_I, _I, _I, _I],
@@ -816,6 +817,31 @@ def cfg_combine(cond, uncond, guidance: float):
     _check(load_library().drn_cfg_combine(_ptr(cond), _ptr(uncond), _ptr(out), cond.numel(), guidance, _stream()),
            "drn_cfg_combine")
     return out
+
+
+def sampler_step_2m(cond, uncond, guidance: float, x, hist_in, hist_out, c_skip: float, c_out: float, a: float, b1: float,
+                    b0: float, c_in_next=None, copies: int = 1):
+    """One DPM-Solver++(2M) step in one launch (drn_sampler_step_2m; the plan and the specification: sampler.plan_steps /
+    step_reference).  cond (and uncond, or None for no CFG) and x bf16 of one shape [P, ...]; hist_in fp32 of that shape, or None
+    where the step reads no history; hist_out fp32 of that shape, written with the denoised estimate (it may be hist_in).  All on
+    one device, contiguous.  -> (the new latent, bf16 like x; the next step's model input bf16 [copies * P, ...] = the new latent
+    times c_in_next, `copies` (1, or 2 under CFG) times along the batch - or None where c_in_next is None, the last step)."""
+    _bf16(cond, uncond, x)
+    for name, t in (("cond", cond), ("uncond", uncond), ("x", x), ("hist_in", hist_in), ("hist_out", hist_out)):
+        if t is not None:
+            assert t.is_contiguous() and t.numel() == x.numel() and t.device == x.device, \
+                f"{name}: a contiguous tensor of x's size on x's device required"
+    for name, t in (("hist_in", hist_in), ("hist_out", hist_out)):
+        assert t is None or t.dtype == torch.float32, f"{name}: the history is fp32"
+    assert hist_out is not None, "hist_out: the step always writes its denoised estimate"
+    x_out = torch.empty_like(x)
+    scaled = None
+    if c_in_next is not None:
+        scaled = torch.empty((copies * x.shape[0], *x.shape[1:]), dtype=torch.bfloat16, device=x.device)
+    _check(load_library().drn_sampler_step_2m(_ptr(cond), _ptr(uncond), guidance, _ptr(x), _ptr(hist_in), _ptr(hist_out),
+                                              _ptr(x_out), _ptr(scaled), copies, x.numel(), c_skip, c_out, a, b1, b0,
+                                              0.0 if c_in_next is None else c_in_next, _stream()), "drn_sampler_step_2m")
+    return x_out, scaled
 
 
 def postprocess_u8(video, normalize_normal: bool):

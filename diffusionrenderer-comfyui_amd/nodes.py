@@ -11,6 +11,7 @@ import torch
 from .diffusion_renderer_config import get_inverse_renderer_config
 from .diffusion_renderer_pipeline import CleanDiffusionRendererPipeline
 from .model_diffusion_renderer import CleanDiffusionRendererModel
+from .sampler import SAMPLERS, check_sampler
 from .windows import check_window_align
 
 GBUFFER_INDEX_MAPPING = {"basecolor": 0, "metallic": 1, "roughness": 2, "normal": 3, "depth": 4}   # nodes.py:35-41
@@ -72,6 +73,19 @@ def _tile_inputs():
                                       "tile_overlap must be a multiple of 8 (the tokenizer's grid; the default 64 is)"})}
 
 
+def _sampler_inputs():
+    """Optional inputs of the renderers for the denoising loop's sampler (sampler.py)."""
+    return {"sampler": (list(SAMPLERS),
+                        {"default": "euler",
+                         "tooltip": "euler: the first-order EDM Euler loop (the default, unchanged).  dpmpp_2m: DPM-Solver++(2M), a "
+                                    "second-order multistep sampler at the same cost per step - one model call -, so fewer steps "
+                                    "reach the same answer (set `steps`); it keeps one fp32 copy of the latent as history.  Not "
+                                    "with tile_join = latent"}),
+            "steps": ("INT", {"default": 0, "min": 0, "max": 1000, "step": 1,
+                              "tooltip": "denoising steps; 0 = leave the loaded pipeline's own number (15 from the loader node) as "
+                                         "it is"})}
+
+
 def _fit_inputs():
     """Optional inputs of both renderers for clips off the model's grid (fit.py)."""
     return {"fit": (["off", "crop", "stretch"],
@@ -124,11 +138,16 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
 
 
 def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel",
-               window_align=False):
+               window_align=False, sampler="euler", steps=0):
     """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
     (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent"); window_align: windows matched
-    in gain and offset over the overlap (refused here, before any upload, without an overlap or with tiles)."""
+    in gain and offset over the overlap (refused here, before any upload, without an overlap or with tiles); sampler: the
+    denoising loop's (refused here where it is unknown, or not "euler" with tile_join = "latent"); steps: the pipeline's
+    num_steps, 0 = left as it is."""
     check_window_align(window_align, window_frames, window_overlap, tiles[0], tiles[1])
+    check_sampler(sampler, tile_join)
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
+        raise ValueError(f"steps must be a non-negative integer (0 = the pipeline's own), got {steps!r}")
     pipeline.set_model_type(model_type)
     pipeline.guidance = guidance
     pipeline.seed = seed
@@ -137,6 +156,9 @@ def _configure(pipeline, model_type, guidance, seed, window_frames, window_overl
     pipeline.window_align = bool(window_align)
     pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
     pipeline.tile_join = tile_join
+    pipeline.sampler = sampler
+    if steps:
+        pipeline.num_steps = int(steps)
     pipeline.restore_plan = None
     pipeline.restore_guide = None
 
@@ -190,11 +212,11 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
                     to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    window_align=False):
+                    window_align=False, sampler="euler", steps=0):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
-    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align)
+    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     guide = _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma)
     if guide is not None:
@@ -226,12 +248,13 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
                   env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
-                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None, env_sequence=False, window_align=False):
+                  tiles=(0, 0, 64), tile_join="pixel", restore_guide=None, env_sequence=False, window_align=False,
+                  sampler="euler", steps=0):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
     (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit);
     restore_guide: its guide (a fit.RestoreGuide), or None for the plain way back.  env_sequence: frame t is lit by frame t of
     env_map, which then holds one frame per frame of the clip as handed in (or a single one)."""
-    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align)
+    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
     # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
@@ -319,7 +342,7 @@ class Cosmos1InverseRenderer:
             "required": {"pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "image": ("IMAGE",)},
             "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1}),
                          "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -329,10 +352,11 @@ class Cosmos1InverseRenderer:
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
-                         tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False):
+                         tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False, sampler="euler", steps=0):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
                                         fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join,
-                                        restore_guide=restore_guide, restore_sigma=restore_sigma, window_align=window_align)
+                                        restore_guide=restore_guide, restore_sigma=restore_sigma, window_align=window_align,
+                                        sampler=sampler, steps=steps)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -361,7 +385,7 @@ class Cosmos1ForwardRenderer:
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
                          "env_sequence": ("BOOLEAN", {"default": False, "tooltip": _ENV_SEQUENCE_TOOLTIP}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_sampler_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE",)
@@ -372,12 +396,12 @@ class Cosmos1ForwardRenderer:
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
                          fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", env_sequence=False,
-                         window_align=False):
+                         window_align=False, sampler="euler", steps=0):
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
                               env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
                               tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join, env_sequence=env_sequence,
-                              window_align=window_align),)
+                              window_align=window_align, sampler=sampler, steps=steps),)
 
 
 class LoadHDRImage:
@@ -420,7 +444,7 @@ class Cosmos1Relight:
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
                          "env_sequence": ("BOOLEAN", {"default": False, "tooltip": _ENV_SEQUENCE_TOOLTIP}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -432,8 +456,8 @@ class Cosmos1Relight:
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
                     tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    env_sequence=False, window_align=False):
-        """Tiles, and the way they are joined, and window_align apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
+                    env_sequence=False, window_align=False, sampler="euler", steps=0):
+        """Tiles, and the way they are joined, window_align, the sampler and its steps apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
         restore_guide = 'source': the input picture guides the way back of all six outputs."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
         tiles = (tile_height, tile_width, tile_overlap)
@@ -446,7 +470,7 @@ class Cosmos1Relight:
         # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
                                         fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join,
-                                        window_align=window_align)
+                                        window_align=window_align, sampler=sampler, steps=steps)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's
@@ -456,7 +480,7 @@ class Cosmos1Relight:
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
                               restore_plan=rplan, tiles=tiles, tile_join=tile_join, restore_guide=guide,
-                              env_sequence=env_sequence, window_align=window_align)
+                              env_sequence=env_sequence, window_align=window_align, sampler=sampler, steps=steps)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:

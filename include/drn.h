@@ -706,6 +706,31 @@ int drn_latent_tile_step_join(const void* model_out, const void* uncond, float g
                               int y_at, int x_at, int ry, int rx, int Oy, int Ox, float c_skip, float c_out, float sigma, float dt,
                               void* stream);
 
+/* ---- DPM-Solver++(2M) sampler step (no reference line for the solver: the reference samples with first-order EDM Euler; it
+ * stands beside model_diffusion_renderer.py:30-82 (scale_model_input, step: the preconditioning c_in / c_skip / c_out is theirs)
+ * and :224-234 (the loop and its CFG combine); plan and torch specification: sampler.py, plan_steps / step_reference;
+ * DESIGN.md 4l).  ONE launch per step; under CFG it stands for drn_cfg_combine + drn_edm_step + the NEXT step's
+ * drn_edm_scale_input + torch.cat([xs, xs]).  Per element i < n, with c = cond, u = uncond, x and h = hist_in as fp32, every
+ * fp32 operation rounded on its own (never an FMA):
+ *   m        = uncond ? bf16(c + bf16(guidance * bf16(c - u))) : c                  (drn_cfg_combine; uncond == NULL: no CFG)
+ *   D        = c_skip * x + c_out * m                                               (drn_edm_step's `denoised`)
+ *   s        = b1 * D;  hist_in ? s = s + b0 * h                                    (hist_in == NULL: the history is not read)
+ *   x_out    = bf16(a * x + s)
+ *   hist_out = D                                                                    (fp32)
+ *   scaled_out[k * n + i] = bf16(fp32(x_out) * c_in_next)   for k < copies          (scaled_out == NULL, the last step: not written)
+ * cond, uncond, x, x_out: bf16 [n]; hist_in, hist_out: fp32 [n]; scaled_out: bf16 [copies * n], the batch the DiT takes next
+ * (copies = 2 under CFG: both halves are the same values).  hist_out may be hist_in; no other two tensors may overlap.  The
+ * coefficients (a, b1, b0) come from sampler.plan_steps: (sigma_next / sigma, e, 0) on the first step, (sigma_next / sigma,
+ * e (1 + 1 / 2r), -e / 2r) on a middle one, (0, 1, 0) on the step to sigma = 0, with e = 1 - sigma_next / sigma and
+ * r = log(sigma_prev / sigma) / log(sigma / sigma_next).  Any alignment on the element's grid; 8 elements per lane where every
+ * base pointer (scaled_out + n for the second copy included) is 16-byte aligned, one per lane otherwise: the same bits.
+ * DRN_EINVAL (nothing launched): a null cond, x, hist_out or x_out; copies outside 1..2 with scaled_out set; n < 0;
+ * hist_in == NULL with b0 != 0; a bf16 pointer off the 2-byte grid or a history pointer off the 4-byte grid.  n == 0: DRN_OK,
+ * nothing launched. */
+int drn_sampler_step_2m(const void* cond, const void* uncond, float guidance, const void* x, const float* hist_in,
+                        float* hist_out, void* x_out, void* scaled_out, int copies, int64_t n, float c_skip, float c_out,
+                        float a, float b1, float b0, float c_in_next, void* stream);
+
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
  * Activations are channels-last bf16, X[t][h][w][c], stored with an optional 1-pixel zero halo in H and W
