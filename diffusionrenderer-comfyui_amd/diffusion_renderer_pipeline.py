@@ -18,6 +18,7 @@ import torch
 
 from . import native as N
 from .diffusion_renderer_config import get_config_from_tensor_shape, validate_config
+from .ensemble import check_ensemble, member_seed, reduce_results
 from .fit import restore_frames, restore_frames_guided
 from .model_diffusion_renderer import CleanDiffusionRendererModel
 from .sampler import check_sampler
@@ -71,6 +72,12 @@ class CleanDiffusionRendererPipeline:
         # calls, today's bits); "dpmpp_2m" = DPM-Solver++(2M), second order at the same cost per step, so `num_steps` can be lower;
         # not with tile_join = "latent"
         self.sampler = "euler"
+        # seed ensembles (ensemble.py): `ensemble` = N > 1 renders every call N times, under the seeds seed, seed + 1,
+        # ... (wrapped at 2^64), and reduces the N uint8 results per pixel on the device: normal passes by the renormalised vector
+        # sum, every other pass by `ensemble_reduce` ("median" / "mean"); 1 = off (today's calls, today's bits); not with an
+        # init_noise
+        self.ensemble = 1
+        self.ensemble_reduce = "median"
         self.device = torch.device("cuda")    # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
@@ -246,6 +253,14 @@ class CleanDiffusionRendererPipeline:
             return None
         return plan_tiles(ref.shape[3], ref.shape[4], self.tile_height, self.tile_width, self.tile_overlap)   # ValueError on a bad size
 
+    def _check_settings(self, init_noise=None):
+        """ValueError for settings that cannot be rendered, before any GPU work."""
+        if self.tile_join not in ("pixel", "latent"):
+            raise ValueError(f"tile_join must be 'pixel' or 'latent', got {self.tile_join!r}")
+        check_sampler(self.sampler, self.tile_join)
+        check_window_align(self.window_align, self.window_frames, self.window_overlap, self.tile_height, self.tile_width)
+        check_ensemble(self.ensemble, self.ensemble_reduce, init_noise)
+
     def _render(self, batches, flags, seed, init_noise, clips=False, to_host=True):
         """Per batch, per pass: uint8 [B, T, H, W, 3] (numpy on the host, or with to_host=False torch tensors on the pipeline's
         device).  A picture of one tile is `_walk`, untouched.  A larger one is rendered tile by tile in raster order around that
@@ -261,12 +276,61 @@ class CleanDiffusionRendererPipeline:
         the final canvases instead of sampling - post-process, carries and the pixel cross-fade as above, because the decoder
         sees each tile's own context.  At tile_overlap = 0 there is nothing to join: "latent" is then the hard-cut tiling above
         with each tile started from its crop of the canvas noise (`_tile_noises`)."""
-        if self.tile_join not in ("pixel", "latent"):
-            raise ValueError(f"tile_join must be 'pixel' or 'latent', got {self.tile_join!r}")
-        check_sampler(self.sampler, self.tile_join)
-        check_window_align(self.window_align, self.window_frames, self.window_overlap, self.tile_height, self.tile_width)
+        self._check_settings(init_noise)
         if not batches:
             return []
+        if self.ensemble > 1:
+            return self._render_ensemble(batches, flags, seed, clips, to_host)[0]
+        return self._render_member(batches, flags, seed, init_noise, clips, to_host)
+
+    def _render_ensemble(self, batches, flags, seed, clips=False, to_host=True, spread=False):
+        """`ensemble` = N members of one call -> (results, spreads or None), per batch and pass as `_render`
+        returns them.  Member k is the one render below - windows, tiles, sampler and passes as they are inside it - under the
+        seed (seed + k) mod 2^64, its results left on the device at the model's size: the restore plan and guide are taken
+        away for the members and put back whatever happens.  Per batch and pass the N results are reduced per pixel
+        (ensemble.reduce_members: 'normal' where the pass's flag is set, `ensemble_reduce` elsewhere), each member's tensor freed
+        as soon as its pass is reduced; the way back then runs ONCE, on the reduced result (guided where a guide is set; the
+        spreads take the plain way back), which also cuts the time padding; the copy to the host comes last.  Device memory: N
+        results of one call at the model's size."""
+        base = seed if seed is not None else self.seed
+        rplan, rguide = self.restore_plan, self.restore_guide
+        self.restore_plan = self.restore_guide = None
+        try:
+            members = [self._render_member(batches, flags, member_seed(base, k), None, clips, False)
+                       for k in range(int(self.ensemble))]
+        finally:
+            self.restore_plan, self.restore_guide = rplan, rguide
+        results, spreads = reduce_results(members, flags, self.ensemble_reduce, spread=spread)
+        del members
+        results = [[self._restored(r) for r in rs] for rs in results]
+        host = (lambda t: t.cpu().numpy()) if to_host else (lambda t: t)
+        if not spread:
+            return [[host(r) for r in rs] for rs in results], None
+        try:
+            self.restore_guide = None                              # a spread is no picture of the source: the plain way back
+            spreads = [[self._restored(s) for s in ss] for ss in spreads]
+        finally:
+            self.restore_guide = rguide
+        return [[host(r) for r in rs] for rs in results], [[host(s) for s in ss] for ss in spreads]
+
+    def generate_video_ensemble(self, data_batches, normalize_normal, seed: int = None, to_host: bool = True):
+        """generate_video_each under `self.ensemble` members, with the members' spread: -> (results, spreads), two lists of uint8
+        [B, T, H, W, 3] in the batches' order.  A spread is the median (mean) absolute deviation of the members per byte, or for a
+        normal pass 255 * (1 - the mean resultant length) in all three channels; it comes back through the plain restore also
+        where a guide is set.  At ensemble = 1 the reduce still runs on the one member: a normal pass is renormalised, every
+        other result is the member and its spread 0."""
+        batches = list(data_batches)
+        flags = [bool(f) for f in normalize_normal]
+        if len(flags) != len(batches):
+            raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
+        self._check_settings()
+        if not batches:
+            return [], []
+        results, spreads = self._render_ensemble(batches, [[f] for f in flags], seed, clips=True, to_host=to_host, spread=True)
+        return [r[0] for r in results], [s[0] for s in spreads]
+
+    def _render_member(self, batches, flags, seed, init_noise, clips=False, to_host=True):
+        """One sample of `_render`'s call: everything `_render`'s text says, behind its checks."""
         tiles = self._tile_plan(batches[0])
         if tiles is None:
             return self._walk(batches, flags, seed, init_noise, clips, to_host)

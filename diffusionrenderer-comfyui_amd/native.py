@@ -115,6 +115,7 @@ SIGNATURES = {
     "drn_edm_step": [_P, _P, _P, _L, _F, _F, _F, _F, _P],
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
     "drn_sampler_step_2m": [_P, _P, _F, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _F, _P],
+    "drn_ensemble_reduce_u8": [POINTER(c_void_p), _I, _P, _P, _L, _I, _P],
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_window_align_workspace_bytes": [_I, _I, _I, _I],
@@ -1099,6 +1100,28 @@ def tile_blend_u8(canvas, tile, wy, wx, y_at: int, x_at: int, ry: int, rx: int):
     _check(load_library().drn_tile_blend_u8(_ptr(canvas), _ptr(tile), _ptr(wy), _ptr(wx), B * T, H, W, h, w, y_at, x_at, ry, rx,
                                             O[0], O[1], _stream()), "drn_tile_blend_u8")
     return canvas
+
+
+ENSEMBLE_MODES = {"median": 0, "mean": 1, "normal": 2}
+
+
+def ensemble_reduce_u8(members, mode: str, spread: bool = False):
+    """N uint8 results of one shape reduced per pixel in one launch (drn_ensemble_reduce_u8; the specification:
+    ensemble.reduce_members).  members: 1..16 uint8 tensors of one shape [..., 3] on one device, each contiguous (they need not
+    lie in one allocation: their pointers go to the kernel by value, no stack is built); mode: 'median' / 'mean' / 'normal'.
+    -> (the result, the spread or None), both of the members' shape."""
+    N = len(members)
+    first = members[0]
+    for m in members:
+        assert m.dtype == torch.uint8 and m.is_contiguous() and m.shape == first.shape and m.device == first.device, \
+            "contiguous uint8 tensors of one shape on one device required"
+    assert first.ndim >= 1 and first.shape[-1] == 3, "[..., 3] pixels required"
+    out = torch.empty_like(first)
+    sp = torch.empty_like(first) if spread else None
+    table = (c_void_p * N)(*[_ptr(m) for m in members])
+    _check(load_library().drn_ensemble_reduce_u8(table, N, _ptr(out), _ptr(sp), first.numel(), ENSEMBLE_MODES[mode], _stream()),
+           "drn_ensemble_reduce_u8")
+    return out, sp
 
 
 def _latent_canvas(name, t):

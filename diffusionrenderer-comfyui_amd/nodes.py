@@ -11,6 +11,7 @@ import torch
 from .diffusion_renderer_config import get_inverse_renderer_config
 from .diffusion_renderer_pipeline import CleanDiffusionRendererPipeline
 from .model_diffusion_renderer import CleanDiffusionRendererModel
+from .ensemble import MAX_MEMBERS, REDUCES, check_ensemble
 from .sampler import SAMPLERS, check_sampler
 from .windows import check_window_align
 
@@ -86,6 +87,20 @@ def _sampler_inputs():
                                          "it is"})}
 
 
+def _ensemble_inputs():
+    """Optional inputs of the nodes that run the inverse renderer, for seed ensembles (ensemble.py)."""
+    return {"ensemble": ("INT", {"default": 1, "min": 1, "max": MAX_MEMBERS, "step": 1,
+                                 "tooltip": "1 = off: one sample (the default, unchanged).  N > 1: the clip is rendered N times, "
+                                            "under the seeds seed, seed + 1, ..., and the N results are reduced per pixel on the "
+                                            "GPU - normal maps by the renormalised sum of the members' vectors, every other output "
+                                            "by ensemble_reduce.  Costs N times the run time and N results held on the GPU; with "
+                                            "sampler = dpmpp_2m at 8 steps a member costs about a quarter of a 35-step Euler pass"}),
+            "ensemble_reduce": (list(REDUCES),
+                                {"default": "median",
+                                 "tooltip": "how the members of an ensemble become one picture, per byte: median (robust against "
+                                            "a member that went wrong; the two middle values averaged at even N) or mean"})}
+
+
 def _fit_inputs():
     """Optional inputs of both renderers for clips off the model's grid (fit.py)."""
     return {"fit": (["off", "crop", "stretch"],
@@ -138,14 +153,18 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
 
 
 def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel",
-               window_align=False, sampler="euler", steps=0):
+               window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median"):
     """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
     (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent"); window_align: windows matched
     in gain and offset over the overlap (refused here, before any upload, without an overlap or with tiles); sampler: the
     denoising loop's (refused here where it is unknown, or not "euler" with tile_join = "latent"); steps: the pipeline's
-    num_steps, 0 = left as it is."""
+    num_steps, 0 = left as it is; ensemble, ensemble_reduce: the seed ensemble (refused here where it is no integer in 1..16 or the
+    reduce is unknown; the forward renderer is always handed 1: averaged renders blur)."""
     check_window_align(window_align, window_frames, window_overlap, tiles[0], tiles[1])
     check_sampler(sampler, tile_join)
+    if isinstance(ensemble, np.integer):
+        ensemble = int(ensemble)
+    check_ensemble(ensemble, ensemble_reduce)
     if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
         raise ValueError(f"steps must be a non-negative integer (0 = the pipeline's own), got {steps!r}")
     pipeline.set_model_type(model_type)
@@ -157,6 +176,8 @@ def _configure(pipeline, model_type, guidance, seed, window_frames, window_overl
     pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
     pipeline.tile_join = tile_join
     pipeline.sampler = sampler
+    pipeline.ensemble = ensemble
+    pipeline.ensemble_reduce = ensemble_reduce
     if steps:
         pipeline.num_steps = int(steps)
     pipeline.restore_plan = None
@@ -212,11 +233,12 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
                     to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    window_align=False, sampler="euler", steps=0):
+                    window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median"):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
-    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps)
+    _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps,
+               ensemble, ensemble_reduce)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     guide = _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma)
     if guide is not None:
@@ -342,7 +364,8 @@ class Cosmos1InverseRenderer:
             "required": {"pipeline": ("DIFFUSION_RENDERER_PIPELINE",), "image": ("IMAGE",)},
             "optional": {"guidance": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 10.0, "step": 0.1}),
                          "seed": ("INT", {"default": 42, "min": 0, "max": 0xffffffffffffffff}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs(),
+                         **_ensemble_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -352,11 +375,12 @@ class Cosmos1InverseRenderer:
 
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
-                         tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False, sampler="euler", steps=0):
+                         tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False, sampler="euler", steps=0,
+                         ensemble=1, ensemble_reduce="median"):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
                                         fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join,
                                         restore_guide=restore_guide, restore_sigma=restore_sigma, window_align=window_align,
-                                        sampler=sampler, steps=steps)
+                                        sampler=sampler, steps=steps, ensemble=ensemble, ensemble_reduce=ensemble_reduce)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -444,7 +468,8 @@ class Cosmos1Relight:
                          "env_rotation": ("FLOAT", {"default": 180.0, "min": 0, "max": 360, "step": 1.0}),
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
                          "env_sequence": ("BOOLEAN", {"default": False, "tooltip": _ENV_SEQUENCE_TOOLTIP}),
-                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs()},
+                         **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs(),
+                         **_ensemble_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -456,8 +481,9 @@ class Cosmos1Relight:
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
                     tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    env_sequence=False, window_align=False, sampler="euler", steps=0):
-        """Tiles, and the way they are joined, window_align, the sampler and its steps apply to both stages.  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
+                    env_sequence=False, window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median"):
+        """Tiles, and the way they are joined, window_align, the sampler and its steps apply to both stages; ensemble and
+        ensemble_reduce to the inverse stage only (the forward stage always renders one sample: averaged renders blur).  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
         restore_guide = 'source': the input picture guides the way back of all six outputs."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
         tiles = (tile_height, tile_width, tile_overlap)
@@ -470,7 +496,8 @@ class Cosmos1Relight:
         # 1. the inverse stage as the inverse node runs it, its outputs left at the model's size on the device, cut to the clip's T
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
                                         fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join,
-                                        window_align=window_align, sampler=sampler, steps=steps)
+                                        window_align=window_align, sampler=sampler, steps=steps, ensemble=ensemble,
+                                        ensemble_reduce=ensemble_reduce)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's

@@ -731,6 +731,27 @@ int drn_sampler_step_2m(const void* cond, const void* uncond, float guidance, co
                         float* hist_out, void* x_out, void* scaled_out, int copies, int64_t n, float c_skip, float c_out,
                         float a, float b1, float b0, float c_in_next, void* stream);
 
+/* ---- seed ensembles: N uint8 results of one shape, rendered under N seeds, reduced per pixel (no reference line: the reference
+ * renders one sample; the torch specification: ensemble.py, reduce_members).  ONE launch.  members: a HOST array
+ * of N device pointers, uint8 [n_bytes] each (they travel to the kernel by value: no device table, no copy); dst: uint8
+ * [n_bytes]; spread: uint8 [n_bytes] or NULL (then neither computed nor written).  m_k = member k's byte.
+ *   mode 0, median, per byte, in integers: s = the N bytes sorted ascending, lo = s[(N-1)/2], hi = s[N/2], t = lo + hi,
+ *     r = t >> 1, and r += r & 1 where t is odd (the two middle values averaged, half to even; odd N: the middle value).
+ *     spread = the same rule on d_k = |m_k - r| (the median absolute deviation).
+ *   mode 1, mean, per byte, in integers: S = sum m_k, q = S / N, rem = S % N, r = q + 1 where 2 rem > N or (2 rem == N and q is
+ *     odd), else q.  spread = the same rule on d_k = |m_k - r|.
+ *   mode 2, normal, per pixel of three bytes (n_bytes % 3 == 0), in fp32, every operation rounded on its own (never an FMA):
+ *     v_k,c = unit(m_k,c) * 2 - 1, unit(i) = fp32(i) / 255.0f correctly rounded (fit.u8_unit); s_c = v_0,c, then s_c = s_c + v_k,c
+ *     for k = 1..N-1 in member order; l2 = (s_x s_x + s_y s_y) + s_z s_z, l = sqrt(l2), d = max(l, 1e-6f), n_c = s_c / d, sqrt and
+ *     / correctly rounded; dst = uint8(rint(clamp((n_c + 1) * 127.5f, 0, 255))), rint half to even (a zero sum: 128, 128, 128);
+ *     spread = uint8(rint(255 * clamp(1 - l / fp32(N), 0, 1))), one minus the mean resultant length, in all three channels.
+ * N = 1: modes 0 and 1 copy (spread 0); mode 2 still renormalises.  Every pointer at any byte alignment: 16 bytes (mode 2: 48
+ * bytes, 16 whole pixels) per lane where every base is 16-byte aligned, one byte (one pixel) per lane otherwise - the same bits;
+ * 64-bit offsets.  dst and spread may overlap nothing else.
+ * DRN_EINVAL (nothing launched): a null members, member or dst; N outside 1..16; mode outside 0..2; n_bytes < 0;
+ * n_bytes % 3 != 0 in mode 2; dst == spread; dst or spread equal to a member.  n_bytes == 0: DRN_OK, nothing launched. */
+int drn_ensemble_reduce_u8(const void* const* members, int N, void* dst, void* spread, int64_t n_bytes, int mode, void* stream);
+
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
  * Activations are channels-last bf16, X[t][h][w][c], stored with an optional 1-pixel zero halo in H and W
