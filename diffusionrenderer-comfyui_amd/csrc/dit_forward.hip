@@ -416,9 +416,17 @@ int validate(const drn_dit_forward_args* a, int64_t al[8]) {
 }
 }  // namespace
 
-extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
+// A forward in parts (drn.h): patch embed (DRN_DIT_EMBED), the sub-blocks [sub_lo, sub_hi), the final layer (DRN_DIT_FINAL) - the
+// launches drn_dit_forward makes for them.  A part that does not end in the final layer leaves X complete: its last
+// gated-residual linear does not defer its split-K sum (the same bits: drn_splitk_gate_res_ln_modulate), and it may not end on a
+// cross-attention sub-block, whose add would still be pending.
+extern "C" int drn_dit_forward_range(const drn_dit_forward_args* a, int sub_lo, int sub_hi, int flags, void* stream) {
     Forward f = {};
     DRN_TRY(validate(a, f.al));
+    DRN_CHECK_ARG((flags & ~(DRN_DIT_EMBED | DRN_DIT_FINAL)) == 0);
+    DRN_CHECK_ARG(0 <= sub_lo && sub_lo <= sub_hi && sub_hi <= a->n_sub);
+    const bool embed = (flags & DRN_DIT_EMBED) != 0, final_layer = (flags & DRN_DIT_FINAL) != 0;
+    DRN_CHECK_ARG(final_layer || sub_lo == sub_hi || a->subs[sub_hi - 1].kind != DRN_SUB_CA);
     f.a = a;
     f.stream = stream;
     const int64_t D = a->D, M = f.M = a->B * a->S;
@@ -427,10 +435,11 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
     const MxPtr h_mx = mxf ? act : none;                 // the MX operand ln_next leaves for q|k|v / MLP-up
 
     // patch embedding (CleanGeneralDIT.py:386/:417): X = P . w_patch^T
-    DRN_TRY(f.linear_bf16({.a = a->P, .w = a->w_patch, .c = a->X, .M = M, .N = D, .K = a->kpad, .epi = DRN_EPI_NONE}));
+    if (embed) DRN_TRY(f.linear_bf16({.a = a->P, .w = a->w_patch, .c = a->X, .M = M, .N = D, .K = a->kpad, .epi = DRN_EPI_NONE}));
 
-    for (int i = 0; i < a->n_sub; ++i) {
+    for (int i = sub_lo; i < sub_hi; ++i) {
         const drn_dit_sub* sb = &a->subs[i];
+        const bool may_defer = final_layer || i + 1 < sub_hi;      // the part's last linear completes X unless the final LN follows
         const bf16_t* sh = (const bf16_t*)a->shift + (int64_t)sb->site * a->shift_site_stride;
         const bf16_t* sc = (const bf16_t*)a->scale + (int64_t)sb->site * a->scale_site_stride;
         const bf16_t* gt = (const bf16_t*)a->gate + (int64_t)sb->site * a->gate_site_stride;
@@ -456,7 +465,7 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
             const bool o_mx = mxf && (mx_ops || drn_attention_mx_available());
             DRN_TRY(f.self_attention(sb, mx_ops, o_mx));
             DRN_TRY(f.linear({.a = a->O, .a_mx = o_mx ? act : none, .w = sb->w_b, .sw = sb->s_b, .c = a->X, .M = M, .N = D, .K = D,
-                              .epi = DRN_EPI_GATE_RES, .gate = gt, .residual = a->X, .may_defer = true}));
+                              .epi = DRN_EPI_GATE_RES, .gate = gt, .residual = a->X, .may_defer = may_defer}));
         } else {
             // mx_fused: MLP-up reads AQ | AS and writes U as MX into UQ | US (a second buffer: written while AQ is read) where the
             // GELU -> MX epilogue exists; a sliced MLP-up writes bf16 U and MLP-down quantises it by launch
@@ -464,10 +473,16 @@ extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
             DRN_TRY(f.linear({.a = a->H, .a_mx = h_mx, .w = sb->w_a, .sw = sb->s_a, .c = a->U, .c_mx = mxf ? uact : none, .M = M,
                               .N = a->hidden, .K = D, .epi = DRN_EPI_GELU}, &u_mx));
             DRN_TRY(f.linear({.a = a->U, .a_mx = u_mx ? uact : none, .w = sb->w_b, .sw = sb->s_b, .c = a->X, .M = M, .N = D,
-                              .K = a->hidden, .epi = DRN_EPI_GATE_RES, .gate = gt, .residual = a->X, .may_defer = true}));
+                              .K = a->hidden, .epi = DRN_EPI_GATE_RES, .gate = gt, .residual = a->X, .may_defer = may_defer}));
         }
     }
     // final layer (CleanGeneralDIT.py:583-590): LN + modulate with the first 2D of the LoRA vector, Linear(D -> n_final)
+    if (!final_layer) return DRN_OK;
     DRN_TRY(f.ln_next((const bf16_t*)a->final_shift, (const bf16_t*)a->final_scale, false));
     return f.linear_bf16({.a = a->H, .w = a->w_final, .c = a->Y, .M = M, .N = a->n_final, .K = D, .epi = DRN_EPI_NONE});
+}
+
+extern "C" int drn_dit_forward(const drn_dit_forward_args* a, void* stream) {
+    if (!a) return DRN_EINVAL;
+    return drn_dit_forward_range(a, 0, a->n_sub, DRN_DIT_EMBED | DRN_DIT_FINAL, stream);
 }

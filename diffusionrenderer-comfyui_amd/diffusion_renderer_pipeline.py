@@ -22,6 +22,7 @@ from .ensemble import check_ensemble, member_seed, reduce_results
 from .fit import restore_frames, restore_frames_guided
 from .model_diffusion_renderer import CleanDiffusionRendererModel
 from .sampler import check_sampler
+from .step_cache import MAX_RUN, check_step_cache
 from .tiles import blend_tile, latent_tile, plan_tiles
 from .windows import Window, check_window_align, plan_windows, ramp_weights
 
@@ -78,6 +79,14 @@ class CleanDiffusionRendererPipeline:
         # init_noise
         self.ensemble = 1
         self.ensemble_reduce = "median"
+        # step cache (step_cache.py): a threshold in (0, 1] lets every sample loop skip the DiT blocks behind the first
+        # on steps where the first block's output moved by less than that (relative L1) since the last computed step, at most
+        # `step_cache_max_run` steps in a row; 0 = off (today's calls, today's bits); not with tile_join = "latent".  Windows, pixel
+        # tiles and ensemble members each run their own loop and so their own cache.  `last_step_cache`: per sample loop of the
+        # last call its log, per step (computed, delta or None)
+        self.step_cache = 0.0
+        self.step_cache_max_run = MAX_RUN
+        self.last_step_cache = []
         self.device = torch.device("cuda")    # torch "cuda" == HIP on ROCm (reference :81)
         self.dtype = dtype
         self.config = None
@@ -260,6 +269,7 @@ class CleanDiffusionRendererPipeline:
         check_sampler(self.sampler, self.tile_join)
         check_window_align(self.window_align, self.window_frames, self.window_overlap, self.tile_height, self.tile_width)
         check_ensemble(self.ensemble, self.ensemble_reduce, init_noise)
+        check_step_cache(self.step_cache, self.step_cache_max_run, self.tile_join)
 
     def _render(self, batches, flags, seed, init_noise, clips=False, to_host=True):
         """Per batch, per pass: uint8 [B, T, H, W, 3] (numpy on the host, or with to_host=False torch tensors on the pipeline's
@@ -277,6 +287,7 @@ class CleanDiffusionRendererPipeline:
         sees each tile's own context.  At tile_overlap = 0 there is nothing to join: "latent" is then the hard-cut tiling above
         with each tile started from its crop of the canvas noise (`_tile_noises`)."""
         self._check_settings(init_noise)
+        self.last_step_cache = []
         if not batches:
             return []
         if self.ensemble > 1:
@@ -324,6 +335,7 @@ class CleanDiffusionRendererPipeline:
         if len(flags) != len(batches):
             raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
         self._check_settings()
+        self.last_step_cache = []
         if not batches:
             return [], []
         results, spreads = self._render_ensemble(batches, [[f] for f in flags], seed, clips=True, to_host=to_host, spread=True)
@@ -541,6 +553,11 @@ class CleanDiffusionRendererPipeline:
         state_shape = [C, (T - 1) // 8 + 1, H // 8, W // 8]
         # (under "euler" the call is the reference's, argument for argument)
         other = {} if self.sampler == "euler" else {"sampler": self.sampler}
-        return self.model.generate_samples_from_batch(data_batch, guidance=self.guidance, state_shape=state_shape,
-                                                      num_steps=self.num_steps, is_negative_prompt=False,
-                                                      seed=effective_seed, init_noise=init_noise, **other)
+        if self.step_cache:
+            other.update(step_cache=float(self.step_cache), step_cache_max_run=int(self.step_cache_max_run))
+        sample = self.model.generate_samples_from_batch(data_batch, guidance=self.guidance, state_shape=state_shape,
+                                                        num_steps=self.num_steps, is_negative_prompt=False,
+                                                        seed=effective_seed, init_noise=init_noise, **other)
+        if self.step_cache:
+            self.last_step_cache.append(list(getattr(self.model.net, "step_cache_log", None) or []))
+        return sample

@@ -30,6 +30,7 @@ from typing import Dict, NamedTuple, Optional
 import torch
 
 from . import native as N
+from . import step_cache as SC
 from .host_tables import rope_cos_sin, timestep_sinusoid
 from .parallel import ShardPlan, allgather_rows_, alltoall_bands_, alltoall_rows_, group_info, is_process_group, wait_exchange
 
@@ -99,6 +100,32 @@ def sp_route(D, heads, S, world, exchange, mx, amx_on, fused_mx, mx_return, spli
     launches = tuple(N.attention_plan(1, hpr, S, S))
     nb = launches[0][1] // rows if len(launches) == 2 and split_return else 0
     return SpRoute("slabs" if slabs else "regroup", amx, mxret, launches, nb)
+
+
+class _HipCacheBackend:
+    """step_cache.Controller's tensor operations on the residual stream [B S, D] (csrc/step_cache.hip); cur["B"]: its clips."""
+
+    def __init__(self, cur):
+        self.cur = cur
+        self.stats = self.ws = None
+
+    def copy(self, x, into=None):
+        return x.clone() if into is None else into.copy_(x)
+
+    def probe(self, x, ref):
+        B = self.cur["B"]
+        if self.stats is None:
+            self.stats = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+            nb = N.load_library().drn_step_cache_workspace_bytes(B, x.numel() // B)
+            self.ws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+        N.step_cache_probe(x.view(B, -1), ref.view(B, -1), self.stats, self.ws)
+        return self.stats.tolist()                # the step's one synchronisation: B x 2 doubles
+
+    def residual(self, x, ref, into=None):
+        return N.step_cache_residual(x, ref, out=into)
+
+    def apply(self, x, r):
+        return N.step_cache_apply(x, r)
 
 
 class HipDiT:
@@ -181,6 +208,10 @@ class HipDiT:
         self.sp_path = None        # sharded forwards: which layout / return exchange the last one took (tests, tools)
         # DRN_SP_SPLIT_RETURN=0: the return all-to-all as ONE collective after the whole attention (A/B runs)
         self._split_return = os.environ.get("DRN_SP_SPLIT_RETURN", "1") != "0"
+        # step cache (step_cache.py): the controller of the sample loop between cache_begin and cache_end, and the
+        # log of the last loop: per step (computed, delta or None)
+        self._cache = None
+        self.step_cache_log = []
 
     # ------------------------------------------------------------------ weights
     def _load(self, sd, p):
@@ -485,6 +516,46 @@ class HipDiT:
                 addvec = (gates.unsqueeze(1) * cv).contiguous()
         return self._run(x, cond, mod, modf, addvec, (Tp, Hp, Wp), plan)
 
+    # ------------------------------------------------------------------ step cache
+    def _cache_refusals(self):
+        if self.trace is not None or self._per_launch:
+            raise ValueError("the step cache cuts the one-call forward (drn_dit_forward_range): not with a trace or DRN_PER_LAUNCH=1")
+
+    def cache_begin(self, thr: float, max_run: int, n_steps: int) -> None:
+        """Open a sample loop of `n_steps` forwards under the step cache (step_cache.Controller): until cache_end every forward is
+        one step of it - the head (patch embed + block 0) always runs, the other blocks only where the probe behind block 0 moved
+        by `thr` or more since the last computed step, or the rule forces them.  Two [B S, D] bf16 buffers live from the loop's first
+        forward to cache_end; a candidate step reads B x 2 doubles back (its one synchronisation).  A net of fewer than 2 blocks
+        ignores the setting."""
+        if self.pg is not None:
+            raise NotImplementedError("the step cache under sequence parallelism is not implemented: set step_cache = 0")
+        self._cache_refusals()
+        if self._cache is not None:
+            raise RuntimeError("cache_begin inside an open sample loop: call cache_end first")
+        self.step_cache_log = []
+        if self.L < 2:
+            SC.check_step_cache(thr, max_run)
+            return
+        n_head, n_sub = len(self.kinds), len(self._subs_c)
+        cur = {}                                  # what the step in hand works on: args (the sequencer's block), x [B S, D], B
+
+        def part(lo, hi, flags):
+            N.dit_forward_range(cur["args"], lo, hi, flags)
+            return cur["x"]
+
+        self._cache = SC.Controller(thr, max_run, n_steps, head=lambda _: part(0, n_head, N.DIT_EMBED),
+                                    tail=lambda x: part(n_head, n_sub, 0), final=lambda x: part(n_sub, n_sub, N.DIT_FINAL),
+                                    backend=_HipCacheBackend(cur))
+        self._cache.cur, self._cache.shape = cur, None
+        self.step_cache_log = self._cache.log
+
+    def cache_end(self) -> None:
+        """Close the sample loop: the two buffers are freed, the log stays in `step_cache_log`."""
+        c, self._cache = self._cache, None
+        if c is not None:
+            c.cur.clear()
+            c.end()
+
     def _lin(self, a, w, out, epilogue=N.EPI_NONE, gate=None, residual=None, rows_per_batch=None):
         """A block linear (q|k|v, out-proj, MLP-up, MLP-down): the bf16 GEMM, or with precision 'mxfp8' the quantisation of
         `a` followed by the MXFP8 GEMM against the weights quantised at load (native.gemm_mxfp8 picks the few-token kernel and its
@@ -744,6 +815,12 @@ class HipDiT:
     def _run(self, x, cond, mod, modf, addvec, grid, plan):
         """The kernel sequence of one forward (all shapes / pointers fixed for a given input shape).  grid: (Tp, Hp, Wp) patches."""
         D, S, rows, B = self.D, plan.S, plan.rows, x.shape[0]    # (a sharded batch: row = b * band + r)
+        if self._cache is not None:
+            # a step of a cached sample loop: refused before anything is allocated or launched
+            self._cache_refusals()
+            if self._cache.shape not in (None, tuple(x.shape)):
+                raise ValueError(f"the input shape changed inside a cached sample loop: {self._cache.shape} -> {tuple(x.shape)}")
+            self._cache.shape = tuple(x.shape)
         rope = self.rope(*grid)
         ws = self._workspace(S, rows, B)
         X, Hb, Y = ws["x"], ws["h"], ws["y"]
@@ -770,7 +847,13 @@ class HipDiT:
         if not sharded and self.trace is None and not self._per_launch:
             # one GPU: the whole launch sequence below is enqueued by ONE C call (csrc/dit_forward.hip: same kernels, same
             # arguments, same order -> same bits; ~570 ctypes round trips less per forward)
-            N.dit_forward(self._sequencer_args(ws, P, S, B, mod=mod, modf=modf, batched=batched, addvec=addvec, rope=rope))
+            args = self._sequencer_args(ws, P, S, B, mod=mod, modf=modf, batched=batched, addvec=addvec, rope=rope)
+            if self._cache is None:
+                N.dit_forward(args)
+            else:
+                # one step of the cached loop: the same launches in parts (drn_dit_forward_range), the tail only where it must
+                self._cache.cur.update(args=args, x=X, B=B)
+                self._cache.step(None)
             return N.unpatchify(Y, B, self.out_ch, *grid, self.pt, self.ps)
         if sharded:
             for b in range(B):                                   # this rank's band of every clip (P holds whole clips)

@@ -19,6 +19,7 @@ from torch import Tensor
 
 from . import native as N
 from . import sampler as S
+from . import step_cache as SC
 from .diffusion_renderer_config import get_inverse_renderer_config
 from .dit_engine import HipDiT
 from .synthetic_weights import dit_param_shapes
@@ -245,12 +246,17 @@ class CleanDiffusionRendererModel:
 
     def generate_samples_from_batch(self, data_batch: Dict, guidance: float = 0.0, seed: int = 1000,
                                     state_shape: Tuple = None, num_steps: int = 15, init_noise: Tensor = None,
-                                    sampler: str = "euler", **kwargs) -> Tensor:
+                                    sampler: str = "euler", step_cache: float = 0.0, step_cache_max_run: int = SC.MAX_RUN,
+                                    **kwargs) -> Tensor:
         """The denoising loop (reference :211-234).  `init_noise` (already scaled by sigma_0) replaces the
         device-side randn for parity runs; without it the reference's seeding convention is kept.
         sampler: "euler" = the reference's first-order loop; "dpmpp_2m" = DPM-Solver++(2M) (sampler.py): the same
-        schedule, noise, passes and CFG halves, one fused launch per step between two DiT calls."""
+        schedule, noise, passes and CFG halves, one fused launch per step between two DiT calls.
+        step_cache > 0 (step_cache.py): the step loop of either sampler runs between net.cache_begin(step_cache,
+        step_cache_max_run, steps) and net.cache_end() (also when a step raises): the net may then reuse what its blocks behind the
+        first added at the last computed step where the first block's output moved by less than the threshold.  0 = no such call."""
         S.check_sampler(sampler)
+        SC.check_step_cache(step_cache, step_cache_max_run)
         if self.net is None:
             raise RuntimeError("weights not loaded: call load_state_dict() first")
         with torch.no_grad():
@@ -287,18 +293,28 @@ class CleanDiffusionRendererModel:
                 idx = cis + [0] * P
             else:
                 lat, idx = lat_c, cis
-            if sampler != "euler":
-                return self._sample_multistep(xt, lat, idx, P, guidance, sampler)
-            for t in self.scheduler.timesteps:
-                xt_scaled = self.scheduler.scale_model_input(xt, timestep=t)
-                if guidance > 0:
-                    both = self.net(x=torch.cat([xt_scaled, xt_scaled], 0), timesteps=t, latent_condition=lat,
-                                    context_index=idx)
-                    net_output = N.cfg_combine(both[:P].contiguous(), both[P:].contiguous(), float(guidance))
-                else:
-                    net_output = self.net(x=xt_scaled, timesteps=t, latent_condition=lat, context_index=idx)
-                xt = self.scheduler.step(net_output, t, xt).prev_sample
-            return xt
+            if step_cache > 0:
+                self.net.cache_begin(float(step_cache), int(step_cache_max_run), len(self.scheduler.timesteps))
+                try:
+                    return self._sample_loop(xt, lat, idx, P, guidance, sampler)
+                finally:
+                    self.net.cache_end()
+            return self._sample_loop(xt, lat, idx, P, guidance, sampler)
+
+    def _sample_loop(self, xt: Tensor, lat: Tensor, idx: list, P: int, guidance: float, sampler: str) -> Tensor:
+        """generate_samples_from_batch's step loop, from the start noise on (the scheduler's table is set)."""
+        if sampler != "euler":
+            return self._sample_multistep(xt, lat, idx, P, guidance, sampler)
+        for t in self.scheduler.timesteps:
+            xt_scaled = self.scheduler.scale_model_input(xt, timestep=t)
+            if guidance > 0:
+                both = self.net(x=torch.cat([xt_scaled, xt_scaled], 0), timesteps=t, latent_condition=lat,
+                                context_index=idx)
+                net_output = N.cfg_combine(both[:P].contiguous(), both[P:].contiguous(), float(guidance))
+            else:
+                net_output = self.net(x=xt_scaled, timesteps=t, latent_condition=lat, context_index=idx)
+            xt = self.scheduler.step(net_output, t, xt).prev_sample
+        return xt
 
     def _sample_multistep(self, xt: Tensor, lat: Tensor, idx: list, P: int, guidance: float, sampler: str) -> Tensor:
         """generate_samples_from_batch's loop under sampler = "dpmpp_2m", from the start noise on (the scheduler's table is set).
@@ -319,7 +335,8 @@ class CleanDiffusionRendererModel:
         return xt
 
     def generate_samples_joint(self, tile_batches, tiles_lat, canvas_shape: Tuple, guidance: float = 0.0, seed: int = 1000,
-                               num_steps: int = 15, init_noise: Tensor = None, sampler: str = "euler") -> Tensor:
+                               num_steps: int = 15, init_noise: Tensor = None, sampler: str = "euler",
+                               step_cache: float = 0.0) -> Tensor:
         """The denoising loop over the spatial tiles of ONE picture, joined in latent space at every step (tiles.py, DESIGN.md
         4i): one noisy canvas [P, *canvas_shape] exists for the whole picture; per Euler step every tile, in raster order, takes
         its crop of the current canvas through the DiT exactly as generate_samples_from_batch would, and its step result is
@@ -329,9 +346,11 @@ class CleanDiffusionRendererModel:
         only the condition latents and the context indices are kept).  tiles_lat: the tiles in latent units (tiles.latent_tile),
         whose written rectangles must cover the canvas.  canvas_shape: (C, F, Hc, Wc).  init_noise (already scaled by sigma_0)
         must be canvas-shaped.  Seed, P passes stepped together, CFG and the errors are generate_samples_from_batch's.  sampler:
-        only "euler" - a multistep sampler would need a history per tile, which is not built (ValueError)."""
+        only "euler" - a multistep sampler would need a history per tile, which is not built (ValueError).  step_cache: only 0 -
+        every tile is a DiT call of its own per step and would need a cache of its own, which is not built (ValueError)."""
         from . import tiles as T
         S.check_sampler(sampler, tile_join="latent")
+        SC.check_step_cache(step_cache, tile_join="latent")
         if self.net is None:
             raise RuntimeError("weights not loaded: call load_state_dict() first")
         tile_batches, tiles_lat, canvas_shape = list(tile_batches), list(tiles_lat), tuple(int(v) for v in canvas_shape)

@@ -46,6 +46,7 @@ class DitForwardArgs(Structure):              # drn_dit_forward_args (include/dr
 SIGNATURES = {
     "drn_attention_plan": [_I, _L, _L, POINTER(c_int64)],
     "drn_dit_forward": [POINTER(DitForwardArgs), _P],
+    "drn_dit_forward_range": [POINTER(DitForwardArgs), _I, _I, _I, _P],
     "drn_dit_forward_args_bytes": [],
     "drn_dit_sub_bytes": [],
     "drn_dit_forward_gemm_workspace_bytes": [_L, _L, _L, _L, _L, _L],
@@ -116,6 +117,10 @@ SIGNATURES = {
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
     "drn_sampler_step_2m": [_P, _P, _F, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _F, _P],
     "drn_ensemble_reduce_u8": [POINTER(c_void_p), _I, _P, _P, _L, _I, _P],
+    "drn_step_cache_workspace_bytes": [_I, _L],
+    "drn_step_cache_probe": [_P, _P, _P, _P, _L, _I, _L, _P],
+    "drn_step_cache_residual": [_P, _P, _P, _L, _P],
+    "drn_step_cache_apply": [_P, _P, _L, _P],
     "drn_postprocess_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "drn_postprocess_window_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "drn_window_align_workspace_bytes": [_I, _I, _I, _I],
@@ -136,7 +141,7 @@ _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_byte
              "drn_gemm_splitk_workspace_bytes": c_int64, "drn_dit_forward_gemm_workspace_bytes": c_int64,
              "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_mx_act_bytes": c_int64,
              "drn_dit_forward_mx_u_bytes": c_int64, "drn_mx_quant_calls": c_int64, "drn_dit_forward_mx_attn_bytes": c_int64,
-             "drn_window_align_workspace_bytes": c_int64,
+             "drn_window_align_workspace_bytes": c_int64, "drn_step_cache_workspace_bytes": c_int64,
              "drn_dit_forward_mx_gemm_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
              "drn_ln_force_kernel": None, "drn_attention_force_shape16": None}
 
@@ -1166,12 +1171,70 @@ def latent_tile_step_join(model_out, uncond, guidance: float, canvas_cur, canvas
     return canvas_next
 
 
-def dit_forward(args: "DitForwardArgs"):
-    """Enqueue one whole DiT forward (drn_dit_forward).  `args` holds raw pointers: the caller keeps every tensor alive."""
+def _stamp(args: "DitForwardArgs"):
+    """The two fields of the argument block the binding owns: its size (the ABI check) and the timer handle."""
     args.struct_bytes = ctypes.sizeof(DitForwardArgs)
     if _TIMER is not None:
         h = _TIMER.native_handle()
         args.timer = h.value if h is not None else None
     else:
         args.timer = None
+
+
+def dit_forward(args: "DitForwardArgs"):
+    """Enqueue one whole DiT forward (drn_dit_forward).  `args` holds raw pointers: the caller keeps every tensor alive."""
+    _stamp(args)
     _check(load_library().drn_dit_forward(ctypes.byref(args), _stream()), "drn_dit_forward")
+
+
+DIT_EMBED, DIT_FINAL = 1, 2
+
+
+def dit_forward_range(args: "DitForwardArgs", sub_lo: int, sub_hi: int, flags: int):
+    """Enqueue a part of a DiT forward (drn_dit_forward_range): the patch embed (DIT_EMBED), the sub-blocks [sub_lo, sub_hi), the
+    final layer (DIT_FINAL).  `args` as for dit_forward; parts that tile the forward give its bits."""
+    _stamp(args)
+    _check(load_library().drn_dit_forward_range(ctypes.byref(args), int(sub_lo), int(sub_hi), int(flags), _stream()),
+           "drn_dit_forward_range")
+
+
+def _clips(t):
+    _bf16(t)
+    assert t.is_contiguous() and t.ndim >= 2 and t.numel() > 0
+    return t.shape[0], t.numel() // t.shape[0]
+
+
+def step_cache_probe(x, ref, stats=None, workspace=None):
+    """How far `x` [B, ...] bf16 lies from `ref` of the same shape, per clip of the leading dimension (drn_step_cache_probe; the
+    specification: step_cache.probe_reference) -> stats [B, 2] fp64 = (sum |x - ref|, sum |ref|) on the device, never read here."""
+    B, n = _clips(x)
+    assert _clips(ref) == (B, n)
+    lib = load_library()
+    nbytes = lib.drn_step_cache_workspace_bytes(B, n)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    assert workspace.dtype == torch.float64 and workspace.numel() * 8 >= nbytes
+    if stats is None:
+        stats = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    assert stats.dtype == torch.float64 and tuple(stats.shape) == (B, 2) and stats.is_contiguous()
+    _check(lib.drn_step_cache_probe(_ptr(x), _ptr(ref), _ptr(stats), _ptr(workspace), workspace.numel() * 8, B, n, _stream()),
+           "drn_step_cache_probe")
+    return stats
+
+
+def step_cache_residual(x, ref, out=None):
+    """bf16(fp32(x) - fp32(ref)) (drn_step_cache_residual), into `out` or a new tensor."""
+    _bf16(x, ref, out)
+    if out is None:
+        out = torch.empty_like(x)
+    assert x.is_contiguous() and ref.is_contiguous() and out.is_contiguous() and x.numel() == ref.numel() == out.numel()
+    _check(load_library().drn_step_cache_residual(_ptr(x), _ptr(ref), _ptr(out), x.numel(), _stream()), "drn_step_cache_residual")
+    return out
+
+
+def step_cache_apply(x, r):
+    """x <- bf16(fp32(x) + fp32(r)) in place (drn_step_cache_apply)."""
+    _bf16(x, r)
+    assert x.is_contiguous() and r.is_contiguous() and x.numel() == r.numel()
+    _check(load_library().drn_step_cache_apply(_ptr(x), _ptr(r), x.numel(), _stream()), "drn_step_cache_apply")
+    return x

@@ -13,6 +13,7 @@ from .diffusion_renderer_pipeline import CleanDiffusionRendererPipeline
 from .model_diffusion_renderer import CleanDiffusionRendererModel
 from .ensemble import MAX_MEMBERS, REDUCES, check_ensemble
 from .sampler import SAMPLERS, check_sampler
+from .step_cache import check_step_cache
 from .windows import check_window_align
 
 GBUFFER_INDEX_MAPPING = {"basecolor": 0, "metallic": 1, "roughness": 2, "normal": 3, "depth": 4}   # nodes.py:35-41
@@ -84,7 +85,16 @@ def _sampler_inputs():
                                     "with tile_join = latent"}),
             "steps": ("INT", {"default": 0, "min": 0, "max": 1000, "step": 1,
                               "tooltip": "denoising steps; 0 = leave the loaded pipeline's own number (15 from the loader node) as "
-                                         "it is"})}
+                                         "it is"}),
+            "step_cache": ("FLOAT", {"default": 0.0, "min": 0.0, "max": 1.0, "step": 0.01,
+                                     "tooltip": "0 = off (the default, unchanged).  > 0: a step cache (first-block cache) - every "
+                                                "denoising step runs the first DiT block, and where its output moved by less than "
+                                                "this (relative L1) since the last fully computed step, the other 27 blocks are "
+                                                "not run and their last contribution is added instead; the first and the last step "
+                                                "are always computed, and at most 3 steps in a row are skipped.  Faster, and the "
+                                                "result changes; which threshold keeps a picture intact has not been measured on "
+                                                "real weights.  Holds two copies of the hidden state on the GPU (302 MB per clip at "
+                                                "57 x 576 x 1024).  Not with tile_join = latent"})}
 
 
 def _ensemble_inputs():
@@ -153,15 +163,17 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
 
 
 def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel",
-               window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median"):
+               window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median", step_cache=0.0):
     """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
     (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent"); window_align: windows matched
     in gain and offset over the overlap (refused here, before any upload, without an overlap or with tiles); sampler: the
     denoising loop's (refused here where it is unknown, or not "euler" with tile_join = "latent"); steps: the pipeline's
     num_steps, 0 = left as it is; ensemble, ensemble_reduce: the seed ensemble (refused here where it is no integer in 1..16 or the
-    reduce is unknown; the forward renderer is always handed 1: averaged renders blur)."""
+    reduce is unknown; the forward renderer is always handed 1: averaged renders blur); step_cache: the step cache's threshold,
+    0 = off (refused here outside [0, 1], or > 0 with tile_join = "latent")."""
     check_window_align(window_align, window_frames, window_overlap, tiles[0], tiles[1])
     check_sampler(sampler, tile_join)
+    check_step_cache(step_cache, tile_join=tile_join)
     if isinstance(ensemble, np.integer):
         ensemble = int(ensemble)
     check_ensemble(ensemble, ensemble_reduce)
@@ -176,6 +188,7 @@ def _configure(pipeline, model_type, guidance, seed, window_frames, window_overl
     pipeline.tile_height, pipeline.tile_width, pipeline.tile_overlap = tiles
     pipeline.tile_join = tile_join
     pipeline.sampler = sampler
+    pipeline.step_cache = float(step_cache)
     pipeline.ensemble = ensemble
     pipeline.ensemble_reduce = ensemble_reduce
     if steps:
@@ -233,12 +246,12 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
                     to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median"):
+                    window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median", step_cache=0.0):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
     _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps,
-               ensemble, ensemble_reduce)
+               ensemble, ensemble_reduce, step_cache)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     guide = _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma)
     if guide is not None:
@@ -271,12 +284,13 @@ def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overl
 def _forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal, env_rotation,
                   env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore, restore_plan=None,
                   tiles=(0, 0, 64), tile_join="pixel", restore_guide=None, env_sequence=False, window_align=False,
-                  sampler="euler", steps=0):
+                  sampler="euler", steps=0, step_cache=0.0):
     """The forward renderer on the five G-buffers `inputs` (depth, normal, roughness, metallic, base_color) -> the image
     (B,T,H,W,C) in [0, 1].  restore_plan: a way back that is not this fit's own (the relight node: the inverse stage's fit);
     restore_guide: its guide (a fit.RestoreGuide), or None for the plain way back.  env_sequence: frame t is lit by frame t of
     env_map, which then holds one frame per frame of the clip as handed in (or a single one)."""
-    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps)
+    _configure(pipeline, "forward", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps,
+               step_cache=step_cache)
     key_mapping = {"base_color": "basecolor", "depth": "depth", "normal": "normal", "roughness": "roughness",
                    "metallic": "metallic"}
     # with a fit, all five G-buffers go through ONE plan: they must be the same clip geometry
@@ -376,11 +390,12 @@ class Cosmos1InverseRenderer:
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
                          tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False, sampler="euler", steps=0,
-                         ensemble=1, ensemble_reduce="median"):
+                         ensemble=1, ensemble_reduce="median", step_cache=0.0):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
                                         fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join,
                                         restore_guide=restore_guide, restore_sigma=restore_sigma, window_align=window_align,
-                                        sampler=sampler, steps=steps, ensemble=ensemble, ensemble_reduce=ensemble_reduce)
+                                        sampler=sampler, steps=steps, ensemble=ensemble, ensemble_reduce=ensemble_reduce,
+                                        step_cache=step_cache)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -420,12 +435,12 @@ class Cosmos1ForwardRenderer:
                          env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0,
                          env_spin=0.0, window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0,
                          fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", env_sequence=False,
-                         window_align=False, sampler="euler", steps=0):
+                         window_align=False, sampler="euler", steps=0, step_cache=0.0):
         inputs = {"depth": depth, "normal": normal, "roughness": roughness, "metallic": metallic, "base_color": base_color}
         return (_forward_pass(pipeline, inputs, env_map, guidance, seed, env_format, env_brightness, env_flip_horizontal,
                               env_rotation, env_spin, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
                               tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join, env_sequence=env_sequence,
-                              window_align=window_align, sampler=sampler, steps=steps),)
+                              window_align=window_align, sampler=sampler, steps=steps, step_cache=step_cache),)
 
 
 class LoadHDRImage:
@@ -481,8 +496,9 @@ class Cosmos1Relight:
                     env_format="proj", env_brightness=1.0, env_flip_horizontal=False, env_rotation=0.0, env_spin=0.0,
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
                     tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    env_sequence=False, window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median"):
-        """Tiles, and the way they are joined, window_align, the sampler and its steps apply to both stages; ensemble and
+                    env_sequence=False, window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median",
+                    step_cache=0.0):
+        """Tiles, and the way they are joined, window_align, the sampler, its steps and step_cache apply to both stages; ensemble and
         ensemble_reduce to the inverse stage only (the forward stage always renders one sample: averaged renders blur).  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
         restore_guide = 'source': the input picture guides the way back of all six outputs."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
@@ -497,7 +513,7 @@ class Cosmos1Relight:
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
                                         fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join,
                                         window_align=window_align, sampler=sampler, steps=steps, ensemble=ensemble,
-                                        ensemble_reduce=ensemble_reduce)
+                                        ensemble_reduce=ensemble_reduce, step_cache=step_cache)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's
@@ -507,7 +523,8 @@ class Cosmos1Relight:
         relit = _forward_pass(forward_pipeline, inputs, env_map, forward_guidance, seed, env_format, env_brightness,
                               env_flip_horizontal, env_rotation, env_spin, window_frames, window_overlap, "crop", 0, 0, False,
                               restore_plan=rplan, tiles=tiles, tile_join=tile_join, restore_guide=guide,
-                              env_sequence=env_sequence, window_align=window_align, sampler=sampler, steps=steps)
+                              env_sequence=env_sequence, window_align=window_align, sampler=sampler, steps=steps,
+                              step_cache=step_cache)
         # 4. the G-buffers as the inverse node returns them
         images = []
         for g in gbuffers:

@@ -424,7 +424,19 @@ typedef struct drn_dit_forward_args {
  * drn_dit_forward_mx_gemm_workspace_bytes), attn_ws drn_dit_forward_attn_workspace_bytes when a FA sub-block is present - whatever
  * sub-blocks the forward holds.  DRN_EINVAL therefore always means that nothing was launched. */
 int drn_dit_forward(const drn_dit_forward_args* args, void* stream);
-int64_t drn_dit_forward_args_bytes(void);     /* sizeof the two structs as this library was compiled (binding self-check) */
+/* The same forward in parts (the step cache cuts it behind block 0: step_cache.py): the patch embed if `flags` has
+ * DRN_DIT_EMBED, then the sub-blocks [sub_lo, sub_hi) of args->subs, then the final layer if `flags` has DRN_DIT_FINAL - each with
+ * the launches drn_dit_forward makes for it, on the same buffers; drn_dit_forward IS the part (0, n_sub, EMBED | FINAL).  Between two
+ * parts only X carries state, and a part without FINAL leaves X complete: its last gated-residual linear does not defer its
+ * split-K sum to a LayerNorm pass that this call will not make (the same bits as deferring: drn_splitk_gate_res_ln_modulate), so
+ * parts that tile [0, n_sub) give drn_dit_forward's Y bit for bit.  (sub_lo == sub_hi is allowed: (n_sub, n_sub, FINAL) is the
+ * final layer alone.)  DRN_EINVAL (nothing launched): everything drn_dit_forward refuses (the whole argument block is checked,
+ * whatever the part), sub_lo > sub_hi, a range outside [0, n_sub], an unknown flag, and a part without FINAL whose last sub-block
+ * is a cross-attention (its add would still be pending in the next LayerNorm pass). */
+#define DRN_DIT_EMBED 1
+#define DRN_DIT_FINAL 2
+int drn_dit_forward_range(const drn_dit_forward_args* args, int sub_lo, int sub_hi, int flags, void* stream);
+int64_t drn_dit_forward_args_bytes(void);    /* sizeof the two structs as this library was compiled (binding self-check) */
 int64_t drn_dit_sub_bytes(void);
 int64_t drn_dit_forward_gemm_workspace_bytes(int64_t B, int64_t S, int64_t D, int64_t hidden, int64_t n_final, int64_t kpad);
 int64_t drn_dit_forward_attn_workspace_bytes(int64_t B, int heads, int64_t S);
@@ -751,6 +763,37 @@ int drn_sampler_step_2m(const void* cond, const void* uncond, float guidance, co
  * DRN_EINVAL (nothing launched): a null members, member or dst; N outside 1..16; mode outside 0..2; n_bytes < 0;
  * n_bytes % 3 != 0 in mode 2; dst == spread; dst or spread equal to a member.  n_bytes == 0: DRN_OK, nothing launched. */
 int drn_ensemble_reduce_u8(const void* const* members, int N, void* dst, void* spread, int64_t n_bytes, int mode, void* stream);
+
+/* ---- step cache (step_cache.py: the rule, the controller and the torch / numpy specification; no reference
+ * counterpart).  A cached denoising loop runs block 0 on every step, asks how far the residual stream behind it moved since the
+ * last computed step, and where it hardly moved adds that step's contribution of blocks 1 .. L-1 instead of running them.
+ * Three streaming passes over [B][n] bf16 (n = S * D values per clip, contiguous), csrc/step_cache.hip:
+ *
+ * drn_step_cache_probe: stats [B][2] fp64 on the device = (num_b, den_b), num_b = sum_i |x_i - ref_i| with the subtraction ONE
+ * rounded fp32 operation, den_b = sum_i |ref_i|, both summed in fp64 over clip b's n values.  Store-and-sum in the manner of
+ * drn_window_align_affine, no atomics, no host read, the same bits run to run and at any alignment:
+ *   chunk k of clip b = its values [8192 k, min(8192 (k + 1), n)); value j of a chunk (0 <= j < 8192) belongs to lane
+ *   (j / 8) % 256; a lane adds its values in increasing j from 0.0; the 64 lanes of a wave are joined by the butterfly
+ *   s_l <- s_l + s_(l ^ d) for d = 32, 16, 8, 4, 2, 1; the chunk's partial is ((w0 + w1) + w2) + w3 over its four waves (lanes
+ *   0-63, 64-127, ...).  A second launch adds clip b's ceil(n / 8192) partials in index order: 64 contiguous runs of
+ *   ceil(chunks / 64) partials, each from 0.0, then the runs in order from 0.0.  A NaN sum is stored as 0x7FF8000000000000.
+ * Both bases 16-byte aligned and n % 8 == 0: 16-byte loads; otherwise 2-byte loads, in the SAME order (the same bits).  64-bit
+ * offsets; the grid is capped at 2048 blocks that stride over the B * ceil(n / 8192) chunks.  workspace: at least
+ * drn_step_cache_workspace_bytes(B, n) bytes (host arithmetic only; 0 for a non-positive size), 8-byte aligned, not initialised
+ * by the caller.  DRN_EINVAL (nothing launched): a null x / ref / stats / workspace, a short workspace, B < 1, n < 1, x / ref off
+ * 2 bytes, stats / workspace off 8.
+ *
+ * drn_step_cache_residual: r_i = bf16(fp32(x_i) - fp32(ref_i)); drn_step_cache_apply: x_i = bf16(fp32(x_i) + fp32(r_i)) in place.
+ * Over n_total values, bit for bit torch's (a.float() -/+ b.float()).bfloat16(): one rounded fp32 operation, round to nearest
+ * even, +-inf kept, every NaN result 0x7FC0 (c10's scalar conversion; torch's vectorised CPU loop writes 0xFFFF for the same
+ * NaN, so against torch a NaN compares as a NaN).  Every base 16-byte aligned: 8 values per lane and the n_total % 8 tail one per lane;
+ * otherwise one value per lane; 64-bit offsets, a capped grid that strides.  r may be x or ref.  DRN_EINVAL (nothing launched):
+ * a null pointer, n_total < 1, a pointer off 2 bytes. */
+int64_t drn_step_cache_workspace_bytes(int B, int64_t n);
+int drn_step_cache_probe(const void* x, const void* ref, void* stats, void* workspace, int64_t workspace_bytes, int B, int64_t n,
+                         void* stream);
+int drn_step_cache_residual(const void* x, const void* ref, void* r, int64_t n_total, void* stream);
+int drn_step_cache_apply(void* x, const void* r, int64_t n_total, void* stream);
 
 /* =====================================================================================================
  * Cosmos-1.0 CV8x8x8 tokenizer (CleanVAE.py:45-60 -> diffusers.AutoencoderKLCosmos, un-vendored: parity unpinned).
