@@ -262,6 +262,83 @@ void en_launch(int mode, dim3 grid, hipStream_t stream, const EnMembers& mem, ui
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the reduce behind an affine
+// Ensembles that agree (ensemble.py; the solve: ensemble_align.hip): member k's byte x of clip b is read as
+// u8(rint(clamp(fp32(g * fp32(x)) + o, 0, 255))) with (g, o) = affine[k][b] - torch's m.float() * g + o, two separately rounded
+// operations under this file's `fp contract(off)`, then the clamp, then half to even - and the median / mean and the spread are
+// the rules above on those bytes.  (1, 0) gives the byte back.  blockIdx.y strides the clips, so the 2 N values of a clip's
+// affines are uniform and a lane's 16 bytes never cross from one clip into the next: the wide path needs every clip's base on
+// the 16-byte grid (the host's finding, `vec`).
+__device__ __forceinline__ uint32_t en_affine(uint32_t x, float g, float o) {
+    const float m = g * (float)x;
+    const float a = m + o;
+    return (uint32_t)__builtin_rintf(__builtin_amdgcn_fmed3f(a, 0.0f, 255.0f));
+}
+
+template <int N, int MODE, bool SPREAD>
+__global__ void __launch_bounds__(EN_THREADS) ensemble_reduce_affine_kernel(EnMembers mem, const float* __restrict__ affine, int B,
+                                                                            int64_t clip_bytes, uint8_t* __restrict__ dst,
+                                                                            uint8_t* __restrict__ spread, int vec) {
+    const int64_t lane = (int64_t)blockIdx.x * EN_THREADS + threadIdx.x;
+    const int64_t lanes = (int64_t)gridDim.x * EN_THREADS;
+    const int64_t n = clip_bytes;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        float ag[N], ao[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            ag[k] = affine[((int64_t)k * B + b) * 2];
+            ao[k] = affine[((int64_t)k * B + b) * 2 + 1];
+        }
+        const int64_t base = (int64_t)b * n;
+        const int64_t nv = vec ? n >> 4 : 0;
+        for (int64_t g = lane; g < nv; g += lanes) {
+            const int64_t e = base + (g << 4);
+            uint32_t w[N][4];
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                const uint4 q = ld16_nt(mem.p[k] + e);
+                w[k][0] = q.x; w[k][1] = q.y; w[k][2] = q.z; w[k][3] = q.w;
+            }
+            uint32_t o[4], s[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = 0;
+                s[j] = 0;
+#pragma unroll
+                for (int bb = 0; bb < 4; ++bb) {
+                    uint32_t v[N], sp = 0;
+#pragma unroll
+                    for (int k = 0; k < N; ++k) v[k] = en_affine((w[k][j] >> (8 * bb)) & 255u, ag[k], ao[k]);
+                    o[j] |= en_byte<N, MODE, SPREAD>(v, sp) << (8 * bb);
+                    s[j] |= sp << (8 * bb);
+                }
+            }
+            *reinterpret_cast<uint4*>(dst + e) = make_uint4(o[0], o[1], o[2], o[3]);
+            if (SPREAD) *reinterpret_cast<uint4*>(spread + e) = make_uint4(s[0], s[1], s[2], s[3]);
+        }
+        for (int64_t i = (nv << 4) + lane; i < n; i += lanes) {
+            uint32_t v[N], sp = 0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k] = en_affine(mem.p[k][base + i], ag[k], ao[k]);
+            dst[base + i] = (uint8_t)en_byte<N, MODE, SPREAD>(v, sp);
+            if (SPREAD) spread[base + i] = (uint8_t)sp;
+        }
+    }
+}
+
+template <int N>
+void en_launch_affine(int mode, dim3 grid, hipStream_t stream, const EnMembers& mem, const float* affine, int B, int64_t clip_bytes,
+                      uint8_t* dst, uint8_t* spread, int vec) {
+    const dim3 block(EN_THREADS);
+    if (spread) {
+        if (mode == 0) ensemble_reduce_affine_kernel<N, 0, true><<<grid, block, 0, stream>>>(mem, affine, B, clip_bytes, dst, spread, vec);
+        else ensemble_reduce_affine_kernel<N, 1, true><<<grid, block, 0, stream>>>(mem, affine, B, clip_bytes, dst, spread, vec);
+    } else {
+        if (mode == 0) ensemble_reduce_affine_kernel<N, 0, false><<<grid, block, 0, stream>>>(mem, affine, B, clip_bytes, dst, nullptr, vec);
+        else ensemble_reduce_affine_kernel<N, 1, false><<<grid, block, 0, stream>>>(mem, affine, B, clip_bytes, dst, nullptr, vec);
+    }
+}
+
 }  // namespace
 
 extern "C" int drn_ensemble_reduce_u8(const void* const* members, int N, void* dst, void* spread, int64_t n_bytes, int mode,
@@ -292,6 +369,41 @@ extern "C" int drn_ensemble_reduce_u8(const void* const* members, int N, void* d
     uint8_t *pd = (uint8_t*)dst, *ps = (uint8_t*)spread;
     switch (N) {
 #define EN_CASE(n_) case n_: en_launch<n_>(mode, grid, st, mem, pd, ps, n_bytes, vec); break;
+        EN_CASE(1) EN_CASE(2) EN_CASE(3) EN_CASE(4) EN_CASE(5) EN_CASE(6) EN_CASE(7) EN_CASE(8)
+        EN_CASE(9) EN_CASE(10) EN_CASE(11) EN_CASE(12) EN_CASE(13) EN_CASE(14) EN_CASE(15) EN_CASE(16)
+#undef EN_CASE
+    }
+    return drn_launch_status();
+}
+
+extern "C" int drn_ensemble_reduce_affine_u8(const void* const* members, int N, const void* affine, int B, int64_t clip_bytes,
+                                             void* dst, void* spread, int mode, void* stream) {
+    DRN_CHECK_ARG(mode >= 0 && mode <= 1);
+    DRN_CHECK_ARG(B >= 1 && clip_bytes >= 0 && clip_bytes <= INT64_MAX / B);
+    DRN_CHECK_ARG(((uintptr_t)affine & 3) == 0);
+    if (!affine) return drn_ensemble_reduce_u8(members, N, dst, spread, (int64_t)B * clip_bytes, mode, stream);
+    DRN_CHECK_ARG(members && dst);
+    DRN_CHECK_ARG(N >= 1 && N <= EN_MAX_N);
+    DRN_CHECK_ARG(dst != spread);
+    EnMembers mem = {};
+    uintptr_t all = (uintptr_t)dst | (uintptr_t)spread;
+    for (int k = 0; k < N; ++k) {
+        DRN_CHECK_ARG(members[k] && members[k] != dst && members[k] != spread);
+        mem.p[k] = (const uint8_t*)members[k];
+        all |= (uintptr_t)members[k];
+    }
+    if (clip_bytes == 0) return DRN_OK;
+    if (B > 1) all |= (uintptr_t)clip_bytes;                          // every clip's base on the 16-byte grid, or one byte per lane
+    const int vec = (all & 15) == 0;
+    const int64_t pieces = clip_bytes / 16, tail = clip_bytes - pieces * 16;
+    const int64_t work = vec ? (pieces > tail ? pieces : tail) : clip_bytes;
+    int64_t blocks = (work + EN_THREADS - 1) / EN_THREADS;
+    if (blocks > EN_MAX_BLOCKS) blocks = EN_MAX_BLOCKS;
+    const dim3 grid((unsigned)blocks, (unsigned)(B < 65535 ? B : 65535));
+    hipStream_t st = (hipStream_t)stream;
+    switch (N) {
+#define EN_CASE(n_) \
+    case n_: en_launch_affine<n_>(mode, grid, st, mem, (const float*)affine, B, clip_bytes, (uint8_t*)dst, (uint8_t*)spread, vec); break;
         EN_CASE(1) EN_CASE(2) EN_CASE(3) EN_CASE(4) EN_CASE(5) EN_CASE(6) EN_CASE(7) EN_CASE(8)
         EN_CASE(9) EN_CASE(10) EN_CASE(11) EN_CASE(12) EN_CASE(13) EN_CASE(14) EN_CASE(15) EN_CASE(16)
 #undef EN_CASE

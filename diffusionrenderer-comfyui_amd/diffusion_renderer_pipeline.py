@@ -79,6 +79,13 @@ class CleanDiffusionRendererPipeline:
         # init_noise
         self.ensemble = 1
         self.ensemble_reduce = "median"
+        # ensembles that agree (ensemble.py): with `ensemble` > 1, every non-normal pass's members are first matched
+        # to member 0 in gain and offset - one (g, o) per member and clip, solved on the device from the members' Gram matrix - and
+        # the reduce reads every byte through its member's pair; False = off (today's calls, today's bits); ignored at ensemble = 1.
+        # `last_ensemble_align`: per batch and pass of the last call the fp32 [N, B, 2] affines on the device, None for a normal
+        # pass; empty where the switch was off
+        self.ensemble_align = False
+        self.last_ensemble_align = []
         # step cache (step_cache.py): a threshold in (0, 1] lets every sample loop skip the DiT blocks behind the first
         # on steps where the first block's output moved by less than that (relative L1) since the last computed step, at most
         # `step_cache_max_run` steps in a row; 0 = off (today's calls, today's bits); not with tile_join = "latent".  Windows, pixel
@@ -268,7 +275,7 @@ class CleanDiffusionRendererPipeline:
             raise ValueError(f"tile_join must be 'pixel' or 'latent', got {self.tile_join!r}")
         check_sampler(self.sampler, self.tile_join)
         check_window_align(self.window_align, self.window_frames, self.window_overlap, self.tile_height, self.tile_width)
-        check_ensemble(self.ensemble, self.ensemble_reduce, init_noise)
+        check_ensemble(self.ensemble, self.ensemble_reduce, init_noise, self.ensemble_align)
         check_step_cache(self.step_cache, self.step_cache_max_run, self.tile_join)
 
     def _render(self, batches, flags, seed, init_noise, clips=False, to_host=True):
@@ -288,6 +295,7 @@ class CleanDiffusionRendererPipeline:
         with each tile started from its crop of the canvas noise (`_tile_noises`)."""
         self._check_settings(init_noise)
         self.last_step_cache = []
+        self.last_ensemble_align = []
         if not batches:
             return []
         if self.ensemble > 1:
@@ -302,7 +310,9 @@ class CleanDiffusionRendererPipeline:
         (ensemble.reduce_members: 'normal' where the pass's flag is set, `ensemble_reduce` elsewhere), each member's tensor freed
         as soon as its pass is reduced; the way back then runs ONCE, on the reduced result (guided where a guide is set; the
         spreads take the plain way back), which also cuts the time padding; the copy to the host comes last.  Device memory: N
-        results of one call at the model's size."""
+        results of one call at the model's size.  With `ensemble_align` (ignored at ensemble = 1) the members of
+        every non-normal pass are solved and reduced through their affines, still per batch and pass, still at the model's size
+        in front of the one way back; the affines stay on the device in `last_ensemble_align`."""
         base = seed if seed is not None else self.seed
         rplan, rguide = self.restore_plan, self.restore_guide
         self.restore_plan = self.restore_guide = None
@@ -311,7 +321,11 @@ class CleanDiffusionRendererPipeline:
                        for k in range(int(self.ensemble))]
         finally:
             self.restore_plan, self.restore_guide = rplan, rguide
-        results, spreads = reduce_results(members, flags, self.ensemble_reduce, spread=spread)
+        if self.ensemble_align and int(self.ensemble) > 1:
+            results, spreads, self.last_ensemble_align = reduce_results(members, flags, self.ensemble_reduce, spread=spread,
+                                                                        align=True)
+        else:
+            results, spreads = reduce_results(members, flags, self.ensemble_reduce, spread=spread)
         del members
         results = [[self._restored(r) for r in rs] for rs in results]
         host = (lambda t: t.cpu().numpy()) if to_host else (lambda t: t)
@@ -336,6 +350,7 @@ class CleanDiffusionRendererPipeline:
             raise ValueError(f"{len(flags)} normalize_normal flags for {len(batches)} batches")
         self._check_settings()
         self.last_step_cache = []
+        self.last_ensemble_align = []
         if not batches:
             return [], []
         results, spreads = self._render_ensemble(batches, [[f] for f in flags], seed, clips=True, to_host=to_host, spread=True)

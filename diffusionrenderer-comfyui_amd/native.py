@@ -117,6 +117,9 @@ SIGNATURES = {
     "drn_cfg_combine": [_P, _P, _P, _L, _F, _P],
     "drn_sampler_step_2m": [_P, _P, _F, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _F, _P],
     "drn_ensemble_reduce_u8": [POINTER(c_void_p), _I, _P, _P, _L, _I, _P],
+    "drn_ensemble_align_workspace_bytes": [_I, _I, _L],
+    "drn_ensemble_align_affine": [POINTER(c_void_p), _I, _I, _L, _P, _P, _P, _L, _P],
+    "drn_ensemble_reduce_affine_u8": [POINTER(c_void_p), _I, _P, _I, _L, _P, _P, _I, _P],
     "drn_step_cache_workspace_bytes": [_I, _L],
     "drn_step_cache_probe": [_P, _P, _P, _P, _L, _I, _L, _P],
     "drn_step_cache_residual": [_P, _P, _P, _L, _P],
@@ -142,6 +145,7 @@ _RESTYPES = {"drn_error_string": c_char_p, "drn_attention_splitkv_workspace_byte
              "drn_dit_forward_attn_workspace_bytes": c_int64, "drn_dit_forward_mx_act_bytes": c_int64,
              "drn_dit_forward_mx_u_bytes": c_int64, "drn_mx_quant_calls": c_int64, "drn_dit_forward_mx_attn_bytes": c_int64,
              "drn_window_align_workspace_bytes": c_int64, "drn_step_cache_workspace_bytes": c_int64,
+             "drn_ensemble_align_workspace_bytes": c_int64,
              "drn_dit_forward_mx_gemm_workspace_bytes": c_int64, "drn_dit_forward_args_bytes": c_int64, "drn_dit_sub_bytes": c_int64, "drn_timer_create": c_void_p, "drn_timer_destroy": None,
              "drn_ln_force_kernel": None, "drn_attention_force_shape16": None}
 
@@ -1126,6 +1130,51 @@ def ensemble_reduce_u8(members, mode: str, spread: bool = False):
     table = (c_void_p * N)(*[_ptr(m) for m in members])
     _check(load_library().drn_ensemble_reduce_u8(table, N, _ptr(out), _ptr(sp), first.numel(), ENSEMBLE_MODES[mode], _stream()),
            "drn_ensemble_reduce_u8")
+    return out, sp
+
+
+def _ensemble_clips(members):
+    """The checks the two aligned entries share -> (N, B, clip_bytes): contiguous uint8 [B, ..., 3] tensors of one shape."""
+    first = members[0]
+    for m in members:
+        assert m.dtype == torch.uint8 and m.is_contiguous() and m.shape == first.shape and m.device == first.device, \
+            "contiguous uint8 tensors of one shape on one device required"
+    assert first.ndim >= 2 and first.shape[-1] == 3 and first.shape[0] >= 1, "[B, ..., 3] pixels required"
+    return len(members), int(first.shape[0]), first.numel() // int(first.shape[0])
+
+
+def ensemble_align_affine(members, stats: bool = False):
+    """One gain and offset per member and clip, from the members' Gram matrix over the whole clip, solved on the device in two
+    launches (drn_ensemble_align_affine; the specification: ensemble.align_members).  members: 1..16 contiguous uint8 tensors
+    [B, ..., 3] of one shape on one device, clip b = member[b] -> affine [N, B, 2] fp32 = (g, o) on the device, never read by the
+    host; with stats=True also the fp64 [B, N + N * N] means and covariances behind it."""
+    N, B, clip_bytes = _ensemble_clips(members)
+    first = members[0]
+    lib = load_library()
+    nbytes = lib.drn_ensemble_align_workspace_bytes(N, B, clip_bytes)
+    ws = torch.empty(max(nbytes, 8) // 8 + 1, dtype=torch.int64, device=first.device)
+    affine = torch.empty((N, B, 2), dtype=torch.float32, device=first.device)
+    st = torch.empty((B, N + N * N), dtype=torch.float64, device=first.device) if stats else None
+    table = (c_void_p * N)(*[_ptr(m) for m in members])
+    _check(lib.drn_ensemble_align_affine(table, N, B, clip_bytes, _ptr(affine), _ptr(st), _ptr(ws), ws.numel() * 8, _stream()),
+           "drn_ensemble_align_affine")
+    return (affine, st) if stats else affine
+
+
+def ensemble_reduce_affine_u8(members, affine, mode: str, spread: bool = False):
+    """ensemble_reduce_u8 in the modes 'median' / 'mean' with every member's byte read through its clip's affine
+    (drn_ensemble_reduce_affine_u8; the specification: ensemble.reduce_members with an affine).  members: as in
+    ensemble_align_affine; affine: fp32 [N, B, 2] on their device, finite.  -> (the result, the spread or None)."""
+    N, B, clip_bytes = _ensemble_clips(members)
+    first = members[0]
+    assert mode in ("median", "mean"), "normal maps are never aligned"
+    assert affine.dtype == torch.float32 and tuple(affine.shape) == (N, B, 2) and affine.is_contiguous() and \
+        affine.device == first.device, "affine: contiguous fp32 [N, B, 2] on the members' device"
+    out = torch.empty_like(first)
+    sp = torch.empty_like(first) if spread else None
+    table = (c_void_p * N)(*[_ptr(m) for m in members])
+    _check(load_library().drn_ensemble_reduce_affine_u8(table, N, _ptr(affine), B, clip_bytes, _ptr(out), _ptr(sp),
+                                                        ENSEMBLE_MODES[mode], _stream()), "drn_ensemble_reduce_affine_u8")
     return out, sp
 
 

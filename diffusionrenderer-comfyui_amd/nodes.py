@@ -108,7 +108,15 @@ def _ensemble_inputs():
             "ensemble_reduce": (list(REDUCES),
                                 {"default": "median",
                                  "tooltip": "how the members of an ensemble become one picture, per byte: median (robust against "
-                                            "a member that went wrong; the two middle values averaged at even N) or mean"})}
+                                            "a member that went wrong; the two middle values averaged at even N) or mean"}),
+            "ensemble_align": ("BOOLEAN", {"default": False,
+                                           "tooltip": "match every member of an ensemble to the first in gain and offset before "
+                                                      "the members are reduced: relative depth and base colour come out of every "
+                                                      "seed at a scale and shift of their own, and a median of members on "
+                                                      "different scales blurs edges.  One gain and offset per member, output and "
+                                                      "clip, solved on the GPU from all members together; normal maps are never "
+                                                      "aligned; the result keeps the first member's scale.  Off: the members are "
+                                                      "reduced as they are.  Ignored at ensemble = 1"})}
 
 
 def _fit_inputs():
@@ -163,20 +171,24 @@ def standardize_to_5d(image, name="image") -> torch.Tensor:
 
 
 def _configure(pipeline, model_type, guidance, seed, window_frames, window_overlap, tiles=(0, 0, 64), tile_join="pixel",
-               window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median", step_cache=0.0):
+               window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median", step_cache=0.0,
+               ensemble_align=False):
     """What both renderers set on the pipeline before a run; the restore plan of an earlier run is cleared.  tiles:
     (tile_height, tile_width, tile_overlap); tile_join: how they are joined ("pixel" / "latent"); window_align: windows matched
     in gain and offset over the overlap (refused here, before any upload, without an overlap or with tiles); sampler: the
     denoising loop's (refused here where it is unknown, or not "euler" with tile_join = "latent"); steps: the pipeline's
     num_steps, 0 = left as it is; ensemble, ensemble_reduce: the seed ensemble (refused here where it is no integer in 1..16 or the
     reduce is unknown; the forward renderer is always handed 1: averaged renders blur); step_cache: the step cache's threshold,
-    0 = off (refused here outside [0, 1], or > 0 with tile_join = "latent")."""
+    0 = off (refused here outside [0, 1], or > 0 with tile_join = "latent"); ensemble_align: the ensemble's members matched in gain
+    and offset before the reduce (refused here where it is no bool; the forward renderer is always handed False)."""
     check_window_align(window_align, window_frames, window_overlap, tiles[0], tiles[1])
     check_sampler(sampler, tile_join)
     check_step_cache(step_cache, tile_join=tile_join)
     if isinstance(ensemble, np.integer):
         ensemble = int(ensemble)
-    check_ensemble(ensemble, ensemble_reduce)
+    if isinstance(ensemble_align, np.bool_):
+        ensemble_align = bool(ensemble_align)
+    check_ensemble(ensemble, ensemble_reduce, ensemble_align=ensemble_align)
     if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
         raise ValueError(f"steps must be a non-negative integer (0 = the pipeline's own), got {steps!r}")
     pipeline.set_model_type(model_type)
@@ -191,6 +203,7 @@ def _configure(pipeline, model_type, guidance, seed, window_frames, window_overl
     pipeline.step_cache = float(step_cache)
     pipeline.ensemble = ensemble
     pipeline.ensemble_reduce = ensemble_reduce
+    pipeline.ensemble_align = ensemble_align
     if steps:
         pipeline.num_steps = int(steps)
     pipeline.restore_plan = None
@@ -246,12 +259,13 @@ def _ingest(pipeline, clips, fit, fit_height, fit_width, fit_restore, window_fra
 
 def _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width, fit_restore,
                     to_host=True, tiles=(0, 0, 64), tile_join="pixel", restore_guide="off", restore_sigma=12.0,
-                    window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median", step_cache=0.0):
+                    window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median", step_cache=0.0,
+                    ensemble_align=False):
     """The inverse renderer up to the pipeline's outputs -> (the five uint8 results in INVERSE_PASSES order - an iterable, rendered
     as it is walked where the passes run one by one -, the frames to keep or None, the fit's plan or None).  to_host=False: the
     results are device tensors (the pipeline's `to_host`)."""
     _configure(pipeline, "inverse", guidance, seed, window_frames, window_overlap, tiles, tile_join, window_align, sampler, steps,
-               ensemble, ensemble_reduce, step_cache)
+               ensemble, ensemble_reduce, step_cache, ensemble_align)
     clips, plan = _ingest(pipeline, {"image": image}, fit, fit_height, fit_width, fit_restore, window_frames)
     guide = _source_guide(pipeline, image, fit, fit_height, fit_width, fit_restore, window_frames, restore_guide, restore_sigma)
     if guide is not None:
@@ -390,12 +404,12 @@ class Cosmos1InverseRenderer:
     def run_inverse_pass(self, pipeline, image, guidance=0.0, seed=42, window_frames=0, window_overlap=8,
                          fit="off", fit_height=0, fit_width=0, fit_restore=False, tile_height=0, tile_width=0, tile_overlap=64,
                          tile_join="pixel", restore_guide="off", restore_sigma=12.0, window_align=False, sampler="euler", steps=0,
-                         ensemble=1, ensemble_reduce="median", step_cache=0.0):
+                         ensemble=1, ensemble_reduce="median", step_cache=0.0, ensemble_align=False):
         outs, keep, _ = _inverse_passes(pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height, fit_width,
                                         fit_restore, tiles=(tile_height, tile_width, tile_overlap), tile_join=tile_join,
                                         restore_guide=restore_guide, restore_sigma=restore_sigma, window_align=window_align,
                                         sampler=sampler, steps=steps, ensemble=ensemble, ensemble_reduce=ensemble_reduce,
-                                        step_cache=step_cache)
+                                        step_cache=step_cache, ensemble_align=ensemble_align)
         images = []
         pbar = _progress_bar(len(INVERSE_PASSES))
         for out in outs:                                                      # in INVERSE_PASSES order = RETURN_NAMES order
@@ -497,9 +511,9 @@ class Cosmos1Relight:
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
                     tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
                     env_sequence=False, window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median",
-                    step_cache=0.0):
-        """Tiles, and the way they are joined, window_align, the sampler, its steps and step_cache apply to both stages; ensemble and
-        ensemble_reduce to the inverse stage only (the forward stage always renders one sample: averaged renders blur).  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
+                    step_cache=0.0, ensemble_align=False):
+        """Tiles, and the way they are joined, window_align, the sampler, its steps and step_cache apply to both stages; ensemble,
+        ensemble_reduce and ensemble_align to the inverse stage only (the forward stage always renders one sample: averaged renders blur).  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
         restore_guide = 'source': the input picture guides the way back of all six outputs."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
         tiles = (tile_height, tile_width, tile_overlap)
@@ -513,7 +527,7 @@ class Cosmos1Relight:
         outs, keep, _ = _inverse_passes(inverse_pipeline, image, guidance, seed, window_frames, window_overlap, fit, fit_height,
                                         fit_width, False, to_host=False, tiles=tiles, tile_join=tile_join,
                                         window_align=window_align, sampler=sampler, steps=steps, ensemble=ensemble,
-                                        ensemble_reduce=ensemble_reduce, step_cache=step_cache)
+                                        ensemble_reduce=ensemble_reduce, step_cache=step_cache, ensemble_align=ensemble_align)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's

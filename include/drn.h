@@ -764,6 +764,46 @@ int drn_sampler_step_2m(const void* cond, const void* uncond, float guidance, co
  * n_bytes % 3 != 0 in mode 2; dst == spread; dst or spread equal to a member.  n_bytes == 0: DRN_OK, nothing launched. */
 int drn_ensemble_reduce_u8(const void* const* members, int N, void* dst, void* spread, int64_t n_bytes, int mode, void* stream);
 
+/* ---- ensembles that agree: one gain and offset per member and clip, solved on the device in front of the reduce (no reference
+ * line; the rule and the torch / numpy specification: ensemble.py, align_solve_members / align_members).  The
+ * members are B clips of clip_bytes bytes each (all of T x H x W x 3); member 0 is the space the result lives in.
+ *
+ * drn_ensemble_align_affine: members: a HOST array of N device pointers, uint8 [B * clip_bytes] each (by value, as in the
+ * reduce); affine: fp32 [N][B][2] = (g, o); stats: fp64 [B][N + N * N] = the means, then C row by row, or NULL; workspace: at
+ * least drn_ensemble_align_workspace_bytes(N, B, clip_bytes) bytes, not initialised by the caller.  Per clip, with n = clip_bytes:
+ *   S_k = sum m_k, S_jk = sum m_j m_k (j <= k), exact integers; mean_k = f64(S_k) / n; C_jk = f64(S_jk) / n - mean_j * mean_k
+ *   (population moments; every fp64 operation rounded on its own, never an FMA); FLAT = 2^-6.
+ *   k = 0: (1, 0).  k >= 1: with N >= 3, num = sum_j C_0j and den = sum_j C_kj over j not in {0, k}, ascending, from 0.0; where
+ *   both are finite and >= FLAT, g = num / den (the cross rule: a third member's noise is independent of both).  Otherwise
+ *   g = sqrt(C_00 / C_kk), or 1 where C_00 < FLAT, C_kk < FLAT or C_0k <= 0 (windows.align_solve's rule on the byte scale).
+ *   g is clamped to [0.5, 2]; o = mean_0 - g * mean_k with the clamped g; anything non-finite: (1, 0); each rounded to fp32 once.
+ * TWO launches, store-and-sum: every wave of a workgroup reduces fixed 8192-byte chunks of one clip to N + N (N + 1) / 2 unsigned
+ * 32-bit partials (8192 * 255^2 < 2^32; byte products through v_dot4_u32_u8; 16 bytes per lane and member where every base and
+ * clip_bytes are on the 16-byte grid, byte loads otherwise), at most 1024 workgroups of four waves per clip, further chunks a grid
+ * stride on;
+ * then one workgroup per clip adds the partials in 64-bit integers and evaluates the rule in fp64.  No atomics, no memset; all
+ * sums are integers, so the bits do not depend on any order.  N = 1 writes (1, 0).
+ * DRN_EINVAL (nothing launched): a null members, member, affine or workspace; N outside 1..16; B < 1 or > 65535; clip_bytes < 1 or
+ * > 2^36 (every sum stays below 2^53 and converts to fp64 exactly); workspace_bytes too small; affine off the 4-byte grid; stats or
+ * workspace off the 8-byte grid.  drn_ensemble_align_workspace_bytes: host arithmetic only; 0 for sizes the entry refuses. */
+int64_t drn_ensemble_align_workspace_bytes(int N, int B, int64_t clip_bytes);
+int drn_ensemble_align_affine(const void* const* members, int N, int B, int64_t clip_bytes, void* affine, void* stats,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
+/* drn_ensemble_reduce_affine_u8: drn_ensemble_reduce_u8 in modes 0 and 1 with an affine in front: member k's byte x of clip b is
+ * read as u8(rint(clamp(fp32(g * fp32(x)) + o, 0, 255))), (g, o) = affine[k][b] - two separately rounded fp32 operations (never
+ * an FMA), the clamp, then half to even: torch's m.float() * g + o on the CPU -, and the median / mean and the spread are the
+ * rules above on those bytes (the spread around the aligned members).  members: as above, uint8 [B * clip_bytes] each; affine:
+ * fp32 [N][B][2] on the device, finite (every member's pair is applied, member 0's too); dst, spread: uint8 [B * clip_bytes],
+ * spread or NULL.  (1, 0) gives the byte back: an all-identity affine gives drn_ensemble_reduce_u8's bits, and affine == NULL is
+ * that entry on B * clip_bytes bytes.  ONE launch, one grid row per clip (a lane's 16 bytes never mix two clips' affines): 16 bytes
+ * per lane where every base is 16-byte aligned and (B > 1) clip_bytes is a multiple of 16, one byte per lane otherwise - the same
+ * bits; 64-bit offsets; the grid capped as in drn_ensemble_reduce_u8.
+ * DRN_EINVAL (nothing launched): mode outside 0..1 (normal maps are never aligned); B < 1; clip_bytes < 0; affine off the 4-byte
+ * grid; and the refusals of drn_ensemble_reduce_u8.  clip_bytes == 0: DRN_OK, nothing launched. */
+int drn_ensemble_reduce_affine_u8(const void* const* members, int N, const void* affine, int B, int64_t clip_bytes, void* dst,
+                                  void* spread, int mode, void* stream);
+
 /* ---- step cache (step_cache.py: the rule, the controller and the torch / numpy specification; no reference
  * counterpart).  A cached denoising loop runs block 0 on every step, asks how far the residual stream behind it moved since the
  * last computed step, and where it hardly moved adds that step's contribution of blocks 1 .. L-1 instead of running them.

@@ -4,6 +4,8 @@ costs, measured in one process with the arms alternating.  Nothing was set in ad
 
     python tools/ensemblebench.py [--kernels-only] [--steps K] [--out profiles/ensemble.txt]
     python tools/ensemblebench.py --parity [--out profiles/ensemble_parity.txt]          (CPU: needs no GPU)
+    python tools/ensemblebench.py --align [--out profiles/ensemble_align.txt]
+    python tools/ensemblebench.py --align --parity [--out profiles/ensemble_align_parity.txt]   (CPU: needs no GPU)
 
 (a) Reduce leg (device events around the wrappers, median of `--reps` runs after a warm-up, arms alternating inside every
     repetition): one pass's reduce at uint8 57 x 576 x 1024 x 3 with N = 3, 5, 8 members, in every mode, without and with the
@@ -15,6 +17,11 @@ costs, measured in one process with the arms alternating.  Nothing was set in ad
     - the full 28-block network with synthetic weights, the HIP tokenizer, `--steps` steps.
 --parity: the robustness figures of tests/ensemble_refs.py's synthetic scene (numpy reference, no GPU) and the count of bytes by
     which every wrong stand-in differs from the reference at its named case.
+--align: ensembles that agree at the same size with N = 3, 5, 8 members that differ in gain and offset: the solve
+    (drn_ensemble_align_affine, its two launches together) against ensemble.align_members' torch path on the device, and the
+    reduce through the affines (drn_ensemble_reduce_affine_u8) against today's reduce (drn_ensemble_reduce_u8, the parent's cost)
+    and against the torch path with the affines.  With --parity: the robustness figures of tests/ensemble_align_refs.py's scene
+    and the stand-in counts, on the CPU.
 """
 import argparse
 import importlib
@@ -61,6 +68,111 @@ def parity():
         say(f"  {kind:28s} {case:18s} {int((gr != wr).sum()):6d} / {int((gsp != wsp).sum()):6d} of {wr.size}")
     n = sum(1 for _ in R.cases())
     say(f"grid: {n} cases; the torch specification equals the numpy reference on all of them (tests/test_ensemble_cpu.py)")
+
+
+def align_parity():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ensemble_align_refs as A
+    import numpy as np
+    fmt = lambda v: ", ".join(f"{x:.3f}" for x in v)
+    say("# tools/ensemblebench.py --align --parity (numpy reference of tests/ensemble_align_refs.py, CPU)")
+    say("robustness: one picture with structure, 96 x 128 x 3, N = 5, member k = g_k truth + o_k + Gaussian noise (sigma 6 of 255) "
+        "with 20 % of its bytes replaced by salt; mean |byte error| of the per-byte median against member 0's space")
+    for title, kw in (("members at gains 1 / 0.7 / 1.3 / 0.85 / 1.15", {}), ("all gains 1 (nothing to align)",
+                                                                            dict(gains=(1.0,) * 5, offsets=(0.0,) * 5))):
+        f = A.robustness_figures(**kw)
+        say(f"  {title}: today's median {f['unaligned']:.3f}; aligned by moment matching alone {f['moment']:.3f}; aligned by the "
+            f"cross rule {f['cross']:.3f}")
+        say(f"    gains: true {fmt(f['true_gains'])}; moment matching {fmt(f['moment_gains'])}; cross rule {fmt(f['cross_gains'])}")
+    f = A.robustness_figures()
+    say(f"  cross rule < moment matching < unaligned on the scene with gains: {f['cross'] < f['moment'] < f['unaligned']}  (the test "
+        "asserts this inequality and fixes no number; the scene with all gains 1 is recorded, not judged)")
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    cases = {name: mem for name, mem in A.solve_cases()}
+    say("wrong stand-ins of the solve against the reference at their named case (affine values / moments that differ):")
+    for kind, case in A.SOLVE_WRONG.items():
+        wa, ws = A.align_ref(cases[case])
+        ga, gs = A.align_ref(cases[case], kind)
+        say(f"  {kind:30s} {case:18s} {int((bits(ga) != bits(wa)).sum()):5d} / {int((gs != ws).sum()):5d}")
+    rcases = {name: (mode, mem, aff) for name, mode, mem, aff in A.reduce_cases(big=False)}
+    say("wrong stand-ins of the reduce behind an affine at their named case (result bytes / spread bytes that differ):")
+    for kind, case in A.REDUCE_WRONG.items():
+        mode, mem, aff = rcases[case]
+        wr, wsp = A.reduce_affine_ref(mem, aff, mode, True)
+        gr, gsp = A.reduce_affine_ref(mem, aff, mode, True, wrong=kind)
+        say(f"  {kind:30s} {case:18s} {int((gr != wr).sum()):5d} / {int((gsp != wsp).sum()):5d} of {wr.size}")
+    say(f"grids: {len(cases)} solve cases, {len(rcases) + 2} reduce cases; the specification equals the numpy reference on all of "
+        "them (tests/test_ensemble_align_cpu.py)")
+
+
+def align_leg(T, H, W, reps):
+    dev = torch.device("cuda")
+    gen = torch.Generator(device="cuda").manual_seed(4)
+    shape = (1, T, H, W, 3)
+    n = T * H * W * 3
+    truth = torch.randint(40, 180, shape, generator=gen, device=dev, dtype=torch.uint8).float()
+    pool = []
+    for k in range(8):
+        g, o = 1.0 + 0.08 * ((k * 5) % 7 - 3) * (k > 0), 6.0 * ((k * 3) % 5 - 2) * (k > 0)
+        m = truth * g + o + 4.0 * torch.randn(shape, generator=gen, device=dev)
+        pool.append(m.round().clamp(0, 255).to(torch.uint8))
+        del m
+    del truth
+    say(f"align leg: members [1,{T},{H},{W},3] uint8 ({n / 2**20:.0f} MiB each) at gains and offsets of their own; device events "
+        f"around the calls, median of {reps} after a warm-up, arms alternating; peak = device memory above the members")
+
+    def timed(arms):
+        ms, peak = {k: [] for k in arms}, {}
+        for fn in arms.values():
+            fn()
+        for _ in range(reps):
+            for k, fn in arms.items():
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn()
+                e1.record()
+                e1.synchronize()
+                ms[k].append(e0.elapsed_time(e1))
+                peak[k] = max(peak.get(k, 0), torch.cuda.max_memory_allocated() - base)
+                del out
+        return {k: (statistics.median(v), min(v), peak[k]) for k, v in ms.items()}
+
+    res = {}
+    for N in (3, 5, 8):
+        members = pool[:N]
+        a_hip, a_torch = E.align_members(members, backend="hip"), E.align_members(members, backend="torch")
+        same = torch.equal(a_hip, a_torch)
+        t = timed({"hip": lambda: E.align_members(members, backend="hip"), "torch": lambda: E.align_members(members, backend="torch")})
+        need = n * N
+        (mh, lh, ph), (mt, lt, pt) = t["hip"], t["torch"]
+        res[(N, "solve")] = (mh, mt)
+        say(f"  N = {N}  solve (two launches)     kernels {mh:7.3f} ms (min {lh:7.3f})  peak {ph / 2**20:6.1f} MiB  "
+            f"{need / mh / 1e9:5.2f} TB/s of the {need / 2**20:.0f} MiB it reads | torch path {mt:9.3f} ms (min {lt:9.3f})  peak "
+            f"{pt / 2**20:6.0f} MiB | {mt / mh:6.1f}x | same bits: {same}; gains {[round(float(x), 3) for x in a_hip[:, 0, 0]]}")
+        for mode in ("median", "mean"):
+            for spread in (False, True):
+                outs = [E.reduce_members(members, mode, spread=spread, backend=b, affine=a_hip) for b in ("torch", "hip")]
+                same = torch.equal(outs[0][0], outs[1][0]) and (not spread or torch.equal(outs[0][1], outs[1][1]))
+                del outs
+                t = timed({"plain": lambda: E.reduce_members(members, mode, spread=spread, backend="hip"),
+                           "affine": lambda: E.reduce_members(members, mode, spread=spread, backend="hip", affine=a_hip),
+                           "torch": lambda: E.reduce_members(members, mode, spread=spread, backend="torch", affine=a_hip)})
+                need = n * (N + (2 if spread else 1))
+                (mp, lp, _), (ma, la, pa), (mt, lt, pt) = t["plain"], t["affine"], t["torch"]
+                res[(N, mode, spread)] = (mp, ma, mt)
+                say(f"  N = {N}  {mode:6s} {'+ spread' if spread else '        '}  today's reduce {mp:7.3f} ms (min {lp:7.3f}) | through "
+                    f"the affines {ma:7.3f} ms (min {la:7.3f})  peak {pa / 2**20:5.0f} MiB  {need / ma / 1e9:5.2f} TB/s of the "
+                    f"{need / 2**20:.0f} MiB it needs  {ma / mp:5.2f}x today's | torch path {mt:9.3f} ms  peak {pt / 2**20:6.0f} MiB  "
+                    f"{mt / ma:6.1f}x | same bytes: {same}")
+    say("  (an aligned pass costs the solve plus the reduce through the affines; today's reduce is what the same pass costs with "
+        "the switch off)")
+    for N in (3, 5, 8):
+        mp, ma, _ = res[(N, "median", False)]
+        say(f"  N = {N}: aligned median pass {res[(N, 'solve')][0] + ma:7.3f} ms against {mp:7.3f} ms unaligned")
+    return res
 
 
 def reduce_leg(T, H, W, reps):
@@ -176,6 +288,7 @@ def pipeline_leg(T, H, W, steps, rounds, N=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parity", action="store_true", help="the robustness figures and the stand-in counts on the CPU; no timing")
+    ap.add_argument("--align", action="store_true", help="ensembles that agree: the solve and the reduce through the affines")
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--frames", type=int, default=57)
     ap.add_argument("--height", type=int, default=576)
@@ -186,7 +299,14 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.parity:
-        parity()
+        align_parity() if a.align else parity()
+    elif a.align:
+        if not torch.cuda.is_available():
+            sys.exit("ensemblebench needs the GPU for its timings (--align --parity runs on the CPU)")
+        if a.reps < 3:
+            sys.exit("medians of at least three runs")
+        say(f"# tools/ensemblebench.py --align on {torch.cuda.get_device_name(0)}; nothing was set in advance")
+        align_leg(a.frames, a.height, a.width, a.reps)
     else:
         if not torch.cuda.is_available():
             sys.exit("ensemblebench needs the GPU for its timings (--parity runs on the CPU)")
