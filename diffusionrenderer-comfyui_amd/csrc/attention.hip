@@ -663,8 +663,10 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
     attention_fwd_kernel<<<dim3((unsigned)L.total, 1, 1), dim3(512), 0, st>>>(
         (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, heads, Sq, Sk, ldq, ldk, ldv, ldo, bsq, bsk,
         bsv, bso, L.scale_log2e, (int)L.nqb, (int)L.total, L.nsplit, L.kv_chunk, L.opart, L.mlpart);
-    if (L.nsplit > 1)
+    if (L.nsplit > 1) {
+        DRN_TRY(drn_launch_status());                    // a failed partials launch: its code, and no combine pass behind it
         drn_attention_combine_launch(L.opart, L.mlpart, o, L.nsplit, batch, heads, Sq, ldo, bso, L.scale_log2e, oq, os, L.mx_bs, st);
+    }
     return drn_launch_status();
 }
 

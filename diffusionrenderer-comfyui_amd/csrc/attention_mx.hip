@@ -366,8 +366,10 @@ int attention_mx_launch(const void* qq, const void* qs, const void* kq, const vo
             (const uint8_t*)qq, (const uint8_t*)qs, (const uint8_t*)kq, (const uint8_t*)ks, (const uint8_t*)vt, (const uint8_t*)vs,
             (bf16_t*)o, heads, Sq, Sk, q_bs, k_bs, Skp, ldo, bso, L.scale_log2e, (int)L.nqb, (int)L.total, L.nsplit, L.kv_chunk, L.opart,
             L.mlpart, nullptr, nullptr, 0);
-    if (L.nsplit > 1)
+    if (L.nsplit > 1) {
+        DRN_TRY(drn_launch_status());                    // a failed partials launch: its code, and no combine pass behind it
         drn_attention_combine_launch(L.opart, L.mlpart, o, L.nsplit, batch, heads, Sq, ldo, bso, L.scale_log2e, oq, os, L.mx_bs, st);
+    }
     return drn_launch_status();
 }
 

@@ -199,9 +199,10 @@ extern "C" int drn_conv3d_igemm(const void* x, const void* w, const void* bias, 
     DRN_CHECK_ARG(!(out_f32 && residual));
     DRN_CHECK_ARG(in_halo == 0 || in_halo == 1);
     // every tap of every output position must stay inside the stored (halo-padded) input image
-    const int hmax = (Ho - 1) * sH - pad + (kH - 1) + in_halo, wmax = (Wo - 1) * sW - pad + (kW - 1) + in_halo;
-    DRN_CHECK_ARG(hmax < H + 2 * in_halo && wmax < W + 2 * in_halo && in_halo - pad >= 0);
-    DRN_CHECK_ARG((To - 1) * sT + (kT - 1) - t_off < T);
+    // (64-bit: the products of two ints may pass 2^31 for sizes this check exists to refuse)
+    const int64_t hmax = (int64_t)(Ho - 1) * sH - pad + (kH - 1) + in_halo, wmax = (int64_t)(Wo - 1) * sW - pad + (kW - 1) + in_halo;
+    DRN_CHECK_ARG(hmax < (int64_t)H + 2 * in_halo && wmax < (int64_t)W + 2 * in_halo && in_halo - pad >= 0);
+    DRN_CHECK_ARG((int64_t)(To - 1) * sT + (kT - 1) - (int64_t)t_off < T);
     DRN_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & 7) == 0);
     ConvGeom g;
     g.To = To; g.Ho = Ho; g.Wo = Wo;

@@ -376,10 +376,17 @@ int validate(const drn_dit_forward_args* a, int64_t al[8]) {
     DRN_CHECK_ARG(a->P && a->w_patch && a->w_final && a->final_shift && a->final_scale && a->shift && a->scale && a->gate);
     const int64_t S = a->S, B = a->B, D = a->D;
     DRN_CHECK_ARG(a->precision == 0 || a->precision == 1);
+    // what a launcher further down would refuse only when its turn comes, after the launches in front of it: the shapes of the
+    // linears (K % 64, N % 128), the LayerNorm's width, the row count, and the 16-byte bases of every GEMM operand
+    DRN_CHECK_ARG(a->kpad > 0 && a->kpad % 64 == 0 && a->n_final > 0 && a->n_final % 128 == 0 && a->hidden % 128 == 0 && D <= 8192);
+    DRN_CHECK_ARG(B <= ((1ll << 31) - 1) / S);
+    DRN_CHECK_ARG((((uintptr_t)a->P | (uintptr_t)a->w_patch | (uintptr_t)a->w_final | (uintptr_t)a->X | (uintptr_t)a->H | (uintptr_t)a->QKV |
+                    (uintptr_t)a->O | (uintptr_t)a->U | (uintptr_t)a->Y | (uintptr_t)a->gemm_ws | (uintptr_t)a->attn_ws) & 15) == 0);
     // the split-K slices of every linear this forward runs (patch embed and final layer are bf16 in either precision)
     int64_t need = drn_dit_forward_gemm_workspace_bytes(B, S, D, a->hidden, a->n_final, a->kpad);
     if (a->precision == 1) {
         DRN_CHECK_ARG(D % 256 == 0 && a->hidden % 256 == 0 && a->AQ && a->AS);
+        DRN_CHECK_ARG(((uintptr_t)a->AQ & 15) == 0 && ((uintptr_t)a->AS & 3) == 0);
         DRN_CHECK_ARG(a->act_bytes >= drn_dit_forward_mx_act_bytes(B, S, D, a->hidden));
         const int64_t ends[3] = {bf16_splitk_bytes(B, S, D, a->kpad), bf16_splitk_bytes(B, S, a->n_final, D),
                                  drn_dit_forward_mx_gemm_workspace_bytes(B, S, D, a->hidden)};
@@ -388,7 +395,9 @@ int validate(const drn_dit_forward_args* a, int64_t al[8]) {
     }
     DRN_CHECK_ARG(need == 0 || (a->gemm_ws && a->gemm_ws_bytes >= need));
     DRN_CHECK_ARG(a->mx_fused == 0 || (a->mx_fused == 1 && a->precision == 1));
-    if (a->mx_fused) DRN_CHECK_ARG(a->UQ && a->US && a->u_act_bytes >= drn_dit_forward_mx_u_bytes(B, S, a->hidden));
+    if (a->mx_fused)
+        DRN_CHECK_ARG(a->UQ && a->US && a->u_act_bytes >= drn_dit_forward_mx_u_bytes(B, S, a->hidden) && ((uintptr_t)a->UQ & 15) == 0 &&
+                      ((uintptr_t)a->US & 3) == 0);
     DRN_CHECK_ARG(a->attn_precision == 0 || a->attn_precision == 1);
     if (a->attn_precision == 1) {
         DRN_TRY(drn_dit_forward_mx_attn_layout(B, S, D, al));
@@ -403,12 +412,14 @@ int validate(const drn_dit_forward_args* a, int64_t al[8]) {
             continue;
         }
         DRN_CHECK_ARG(sb->w_a && sb->w_b && (a->precision == 0 || (sb->s_a && sb->s_b)));
+        DRN_CHECK_ARG((((uintptr_t)sb->w_a | (uintptr_t)sb->w_b) & 15) == 0 && (((uintptr_t)sb->s_a | (uintptr_t)sb->s_b) & 3) == 0);
         if (sb->kind == DRN_SUB_FA) {
             DRN_CHECK_ARG(sb->qn && sb->kn && a->cos && a->sin);
             any_fa = true;
         }
     }
     if (any_fa) {                                        // the split-KV partials of the plan's split launch
+        DRN_CHECK_ARG(B <= 65535);                       // (the split launches and the V^T quantiser put the clip in a grid dimension)
         const int64_t att = drn_dit_forward_attn_workspace_bytes(B, a->heads, S);
         DRN_CHECK_ARG(att == 0 || (a->attn_ws && a->attn_ws_bytes >= att));
     }

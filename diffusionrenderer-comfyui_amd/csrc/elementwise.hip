@@ -389,6 +389,7 @@ template <bool MX>
 static int launch_ln_modulate(void* x, const void* add_vec, const void* shift, const void* scale, void* h, void* hq, void* hs,
                               int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream) {
     DRN_CHECK_ARG(x && shift && scale && rows >= 0 && D > 0 && D % 8 == 0 && D <= 8192 && rows_per_batch > 0);
+    DRN_CHECK_ARG((rows + 3) / 4 < (1ll << 31));                         // one workgroup index in 31 bits (four rows per workgroup)
     if (rows == 0) return DRN_OK;
     hipStream_t st = (hipStream_t)stream;
     const int nch = (int)((D + 511) / 512);
@@ -503,6 +504,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__
 
 extern "C" int drn_rmsnorm(const void* x, const void* w, void* y, int64_t rows, int64_t D, float eps, void* stream) {
     DRN_CHECK_ARG(x && w && y && rows >= 0 && D > 0 && D % 8 == 0);
+    DRN_CHECK_ARG(D < (1ll << 31) && (rows + 3) / 4 < (1ll << 31));     // the kernel's int D; one workgroup index in 31 bits
     if (rows == 0) return DRN_OK;
     rmsnorm_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
         (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rows, (int)D, eps);
@@ -681,6 +683,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const bf16_t* __restrict_
 extern "C" int drn_patchify_concat(const void* x, const void* cond, void* out, int B, int Cx, int Cc, int with_mask,
                                    int Tl, int Hl, int Wl, int pt, int ps, int64_t ldo, void* stream) {
     DRN_CHECK_ARG(x && out && B > 0 && Cx > 0 && Cc >= 0 && (Cc == 0 || cond) && pt > 0 && ps > 0);
+    DRN_CHECK_ARG(Tl > 0 && Hl > 0 && Wl > 0);                           // (an empty latent would be a launch of zero workgroups)
     DRN_CHECK_ARG(Tl % pt == 0 && Hl % ps == 0 && Wl % ps == 0);
     DRN_CHECK_ARG(ldo >= (int64_t)(Cx + Cc + (with_mask ? 1 : 0)) * pt * ps * ps);
     const int64_t total = (int64_t)B * (Tl / pt) * (Hl / ps) * (Wl / ps) * ldo;

@@ -323,6 +323,7 @@ extern "C" int drn_gemm_plan_describe(int64_t M, int64_t N, int64_t K, int64_t l
     GemmLaunch L{0, 0, M, rows_per_batch};
     if (splits > 1) {
         if (p.blocked() || M <= 0 || splits > 64 || (K / BK) % splits != 0 || lda < K || ldc < N) return -1;
+        if (((M + BM - 1) / BM) * (N / BN) >= 65536) return -1;       // splitk_slices' grid limit: the call is refused, so is its plan
         L.kernel = gemm_plan_splitk(s, p.clip_rows(), N, K, splits).kernel;
     }
     for (int64_t row = 0; row < M; row += L.rows, ++n) {

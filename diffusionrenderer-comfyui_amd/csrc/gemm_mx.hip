@@ -312,10 +312,11 @@ extern "C" int64_t drn_mx_quant_calls(int reset) {
 extern "C" int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q, void* scales, void* stream) {
     DRN_CHECK_ARG(X && Q && scales && M >= 1 && K >= 32 && K % 32 == 0 && ldx >= K && ldx % 8 == 0);
     DRN_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 7) == 0);
-    DRN_CHECK_ARG(M * (K / 8) < (1ll << 31));
+    // the kernel numbers its 8-element chunks in an int, the last workgroup's idle lanes included: total rounded up to 256 < 2^31
+    DRN_CHECK_ARG(M <= ((1ll << 31) - 256) / (K / 8));
     const int total = (int)(M * (K / 8));
     ++g_mx_quant_calls;
-    mx_quant_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+    mx_quant_kernel<<<dim3((unsigned)(((int64_t)total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
         (const bf16_t*)X, ldx, (int)(K / 8), total, (uint8_t*)Q, (uint8_t*)scales, K);
     return drn_launch_status();
 }

@@ -77,6 +77,9 @@ static inline int gemm_shape_set_blocks(GemmShape* p, int64_t a_block_cols, int6
 // the part of drn_gemm_bf16's argument checks that the shape decides (the pointers are the entry's own)
 static inline bool gemm_shape_ok(const GemmShape& p) {
     if (!(p.M >= 0 && p.N > 0 && p.K > 0 && p.K % 64 == 0 && p.N % 128 == 0)) return false;
+    // every launch of a plan stays inside its kernel's grid: rows in 31 bits, and so are the tiles of the smallest tile (a plan of
+    // several launches must not find this out at its second launch: DRN_EINVAL means that nothing was launched)
+    if (!(p.M < (1ll << 31) && ((p.M + 127) / 128) * (p.N / 128) < (1ll << 31))) return false;
     if (!(p.lda % 8 == 0 && p.ldw % 8 == 0 && p.ldc % 8 == 0 && p.ldw >= p.K)) return false;
     if (!((p.blk[0] != 62 || p.lda >= p.K) && (p.blk[2] != 62 || p.ldc >= p.N))) return false;
     return p.epilogue != DRN_EPI_GATE_RES || (p.ldr % 8 == 0 && p.ldr >= p.N && p.rows_per_batch > 0);

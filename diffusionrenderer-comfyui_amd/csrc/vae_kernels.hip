@@ -127,6 +127,7 @@ extern "C" int drn_groupnorm_silu(const void* x, const void* gamma, const void* 
     const int64_t frame_elems = (int64_t)(H + 2 * halo) * (W + 2 * halo) * C;
     hipStream_t st = (hipStream_t)stream;
     gn_stats_kernel<<<dim3(GN_NBLK, frames), dim3(256), 0, st>>>((const bf16_t*)x, (double*)workspace, frame_elems, GN_NBLK);
+    DRN_TRY(drn_launch_status());                        // (no normalisation behind statistics that were never enqueued)
     gn_apply_launch((const bf16_t*)x, (const double*)workspace, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, frames, H, W, C,
                     halo, GN_NBLK, eps, silu, (float)H * (float)W * (float)C, st);
     return drn_launch_status();
@@ -149,7 +150,9 @@ extern "C" int drn_groupnorm_apply(const void* x, const void* part, int nparts, 
                     nparts, eps, silu, count, (hipStream_t)stream);
     return drn_launch_status();
 }
-extern "C" int64_t drn_groupnorm_workspace_bytes(int frames) { return (int64_t)frames * GN_NBLK * 2 * sizeof(double); }
+extern "C" int64_t drn_groupnorm_workspace_bytes(int frames) {
+    return frames > 0 ? (int64_t)frames * GN_NBLK * 2 * (int64_t)sizeof(double) : 0;      // (signed throughout; 0 for a count the entry refuses)
+}
 
 // ------------------------------------------------------------------------------------------------ Haar
 #define HW_ 0.70703125f          // bf16(0.7071067811865476): the wavelet taps are cast to the activation dtype
@@ -493,7 +496,9 @@ __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict
 
 extern "C" int drn_transpose_bf16(const void* x, void* y, int rows, int cols, int64_t ldx, int64_t ldo, void* stream) {
     DRN_CHECK_ARG(x && y && rows > 0 && cols > 0 && ldx >= cols && ldo >= rows);
-    dim3 grid((cols + 31) / 32, (int)((ldo + 31) / 32));
+    // the output rows' tiles are grid.y (<= 65535); the kernel's column index of a tile's last lane stays an int
+    DRN_CHECK_ARG((ldo + 31) / 32 <= 65535 && cols <= 0x7fffffff - 31);
+    dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((ldo + 31) / 32));
     transpose_kernel<<<grid, dim3(256), 0, (hipStream_t)stream>>>((const bf16_t*)x, (bf16_t*)y, rows, cols, ldx, ldo);
     return drn_launch_status();
 }
@@ -569,6 +574,7 @@ __global__ __launch_bounds__(256) void temporal_attn_kernel(const bf16_t* __rest
 extern "C" int drn_temporal_attention(const void* q, const void* k, const void* v, void* o, int T, int64_t P, int C,
                                       float scale, void* stream) {
     DRN_CHECK_ARG(q && k && v && o && T > 0 && T <= 16 && P > 0 && C > 0 && C % 8 == 0);
+    DRN_CHECK_ARG((P + 3) / 4 < (1ll << 31));                            // one workgroup index in 31 bits (four pixels per workgroup)
     dim3 grid((unsigned)((P + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define TA(N) temporal_attn_kernel<N><<<grid, block, 0, st>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, T, P, C, scale)

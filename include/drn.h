@@ -59,7 +59,8 @@ const char* drn_error_string(int code);
  * Replaces every nn.Linear of the DiT blocks (CleanGeneralDIT.py:273-276 q/k/v, :254-257 to_out,
  * :445-447 MLP, :386/:417 patch embed, :555/:590 final linear) plus the GELU (:446) and the gated
  * residual (:517) that follow them.
- * Requirements: K % 64 == 0, N % 128 == 0, lda/ldw/ldc/ldr % 8 == 0, 16-byte aligned bases.
+ * Requirements: K % 64 == 0, N % 128 == 0, lda/ldw/ldc/ldr % 8 == 0, 16-byte aligned bases; M < 2^31 and fewer than 2^31 tiles of
+ * 128 x 128 (checked before the first launch of a plan, so that DRN_EINVAL keeps meaning that nothing was launched).
  * gate: [batches, N] bf16 (row r uses batch r / rows_per_batch); residual R: [M, ldr] bf16 (may alias C). */
 int drn_gemm_bf16(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K,
                   int64_t lda, int64_t ldw, int64_t ldc, int epilogue,
@@ -132,7 +133,7 @@ int drn_gemm_tall_force_shape(int shape);
  * Layouts: elements [rows, K] row-major, contiguous (ld = K), one byte each; scales [rows, K / 32] row-major, one byte each
  * (the scale of elements k .. k+31 of row r at r * (K / 32) + k / 32).  Weights [N, K] and activations [M, K] alike. */
 /* X [M, K] bf16 with row stride ldx -> Q [M, K] e4m3 + scales [M, K / 32].  K % 32 == 0, ldx % 8 == 0, X 16-byte and Q 8-byte
- * aligned, M * K / 8 < 2^31. */
+ * aligned, M * K / 8 <= 2^31 - 256 (the kernel numbers its 8-element chunks in an int, the last workgroup's idle lanes included). */
 int drn_mx_quant_bf16(const void* X, int64_t M, int64_t K, int64_t ldx, void* Q, void* scales, void* stream);
 /* host-side count of the launches drn_mx_quant_bf16 has enqueued in this process (reset != 0 zeroes it after reading): lets a
  * test state "this forward issued no quantise launch" without a profiler.  A plain counter on the launch path (one host thread
@@ -223,7 +224,8 @@ int drn_gemv_bf16(const void* x, const void* W, void* y, int64_t N, int64_t K,
  * with the reference's rounding points (CleanGeneralDIT.py:7-11, :481, :506; final layer :587).
  * If add_vec != NULL the row is first updated in place, x <- bf16(x + add_vec[batch]) (the broadcast
  * cross-attention residual, :517 with F8), and LN runs on the updated row.
- * x,h: [rows, D] bf16; shift/scale/add_vec: [batches, D] bf16; batch = row / rows_per_batch. D % 8 == 0, D <= 8192. */
+ * x,h: [rows, D] bf16; shift/scale/add_vec: [batches, D] bf16; batch = row / rows_per_batch. D % 8 == 0, D <= 8192; at most
+ * 2^33 - 4 rows (2^31 - 1 workgroups of four rows; DRN_EINVAL beyond, nothing launched). */
 int drn_ln_modulate(void* x, const void* add_vec, const void* shift, const void* scale, void* h,
                     int64_t rows, int64_t D, int64_t rows_per_batch, float eps, void* stream);
 /* the same with h written as MXFP8: hq [rows, D] e4m3 + hs [rows, D / 32] scales (h: bf16 as above, or NULL).  D % 32 == 0 on top
@@ -254,7 +256,8 @@ int drn_bcast_add(void* x, const void* vec, int64_t rows, int64_t D, int64_t row
  * New on this path: the reference has no multi-GPU code. */
 int drn_permute_021(const void* x, void* y, int64_t A, int64_t B, int64_t C, void* stream);
 
-/* ---- RMSNorm over the last dim, fp32 internal: y = bf16(x * rsqrt(mean(x^2)+eps) * w)   CleanGeneralDIT.py:14-33 */
+/* ---- RMSNorm over the last dim, fp32 internal: y = bf16(x * rsqrt(mean(x^2)+eps) * w)   CleanGeneralDIT.py:14-33
+ * D % 8 == 0, D < 2^31, at most 2^33 - 4 rows (2^31 - 1 workgroups of four rows); DRN_EINVAL otherwise, nothing launched. */
 int drn_rmsnorm(const void* x, const void* w, void* y, int64_t rows, int64_t D, float eps, void* stream);
 
 /* ---- per-head RMSNorm(q), RMSNorm(k) + 3-D RoPE, in place (CleanGeneralDIT.py:288-295, :45-84).
@@ -419,7 +422,11 @@ typedef struct drn_dit_forward_args {
     int32_t reserved2;
     void* mx_attn; int64_t mx_attn_bytes; /* attn_precision 1: scratch for QQ | QS | KQ | KS | VT | VS (drn_dit_forward_mx_attn_bytes) */
 } drn_dit_forward_args;
-/* Every argument and workspace check is made up front, against the sizers below, before anything is enqueued: gemm_ws must hold
+/* Every argument and workspace check is made up front, against the sizers below, before anything is enqueued - also those a
+ * launcher further down would make only when its turn comes: kpad % 64 == 0, n_final % 128 == 0, hidden % 128 == 0, D <= 8192,
+ * B S < 2^31 (B <= 65535 with a FA sub-block), 16-byte bases for P, w_patch, w_final, X, H, QKV, O, U, Y, both workspaces, AQ, UQ and
+ * every w_a / w_b (4-byte for AS, US, s_a, s_b).  A launch that fails ends the call with its code; nothing is enqueued behind it.
+ * gemm_ws must hold
  * drn_dit_forward_gemm_workspace_bytes (precision 1: the larger of its patch-embed / final-layer share and
  * drn_dit_forward_mx_gemm_workspace_bytes), attn_ws drn_dit_forward_attn_workspace_bytes when a FA sub-block is present - whatever
  * sub-blocks the forward holds.  DRN_EINVAL therefore always means that nothing was launched. */
@@ -483,7 +490,7 @@ int drn_timer_read(void* timer, int index, int* kind, float* ms, double* flops, 
 
 /* ---- patchify + channel concat: out[b*T*H*W + (t,h,w), (c r m n)] gathered from x | cond | ones-mask
  * (CleanGeneralDIT.py:669-675, :409-414).  x: [B,Cx,Tl,Hl,Wl], cond: [B,Cc,Tl,Hl,Wl] bf16; with_mask appends the
- * all-ones channel; columns [C*pt*ps*ps, ldo) are zero-filled (K padding for the GEMM).  Bit-exact index op. */
+ * all-ones channel; columns [C*pt*ps*ps, ldo) are zero-filled (K padding for the GEMM).  Bit-exact index op.  Tl, Hl, Wl >= 1. */
 int drn_patchify_concat(const void* x, const void* cond, void* out, int B, int Cx, int Cc, int with_mask,
                         int Tl, int Hl, int Wl, int pt, int ps, int64_t ldo, void* stream);
 
@@ -862,7 +869,7 @@ void drn_conv_force_tile(int tile);
 int drn_conv_last_tile(void);
 
 /* ---- CosmosCausalGroupNorm(1 group, per frame) [+ SiLU]: y = [silu](bf16((x-mean)*rstd*gamma + beta)).
- * workspace: drn_groupnorm_workspace_bytes(frames) bytes of device scratch. */
+ * workspace: drn_groupnorm_workspace_bytes(frames) bytes of device scratch (0 for frames < 1, which the entry refuses). */
 int drn_groupnorm_silu(const void* x, const void* gamma, const void* beta, void* y, void* workspace,
                        int frames, int H, int W, int C, int halo, float eps, int silu, void* stream);
 int64_t drn_groupnorm_workspace_bytes(int frames);
@@ -888,6 +895,8 @@ int drn_resample(const void* x, void* y, int mode, int T, int H, int W, int C, i
 int drn_softmax_rows(const void* scores, void* probs, int64_t rows, int n, int64_t ld, int64_t ldp, void* stream);
 /* the same with the scores multiplied by `scale` first (one fp32 product per element: what a GEMM epilogue with alpha = scale forms) */
 int drn_softmax_rows_scaled(const void* scores, void* probs, int64_t rows, int n, int64_t ld, int64_t ldp, float scale, void* stream);
+/* (transpose: ldo <= 65535 * 32 - the output rows' tiles are a grid dimension - and cols <= 2^31 - 32; temporal attention: at most
+ * 2^33 - 4 pixels P, four per workgroup; DRN_EINVAL beyond, nothing launched) */
 int drn_transpose_bf16(const void* x, void* y, int rows, int cols, int64_t ldx, int64_t ldo, void* stream);
 int drn_temporal_attention(const void* q, const void* k, const void* v, void* o, int T, int64_t P, int C, float scale,
                            void* stream);
