@@ -42,6 +42,13 @@ class DitForwardArgs(Structure):              # drn_dit_forward_args (include/dr
                 ("attn_precision", c_int32), ("reserved2", c_int32), ("mx_attn", c_void_p), ("mx_attn_bytes", c_int64)]
 
 
+class GbufferEditMap(Structure):              # drn_gbuffer_edit_map (include/drn.h), field for field
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("layer", c_void_p),
+                ("src_bs", c_int64), ("src_ts", c_int64), ("dst_bs", c_int64), ("dst_ts", c_int64),
+                ("layer_bs", c_int64), ("layer_ts", c_int64), ("gain", c_float * 3), ("offset", c_float * 3),
+                ("is_normal", c_int32), ("reserved", c_int32)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES); must match include/drn.h one-to-one
 SIGNATURES = {
     "drn_attention_plan": [_I, _L, _L, POINTER(c_int64)],
@@ -120,6 +127,8 @@ SIGNATURES = {
     "drn_ensemble_align_workspace_bytes": [_I, _I, _L],
     "drn_ensemble_align_affine": [POINTER(c_void_p), _I, _I, _L, _P, _P, _P, _L, _P],
     "drn_ensemble_reduce_affine_u8": [POINTER(c_void_p), _I, _P, _I, _L, _P, _P, _I, _P],
+    "drn_gbuffer_edit_map_bytes": [],
+    "drn_gbuffer_edit_u8": [POINTER(GbufferEditMap), _I, _P, _L, _L, _P, _L, _L, _I, _I, _L, _P],
     "drn_step_cache_workspace_bytes": [_I, _L],
     "drn_step_cache_probe": [_P, _P, _P, _P, _L, _I, _L, _P],
     "drn_step_cache_residual": [_P, _P, _P, _L, _P],
@@ -172,6 +181,8 @@ def load_library():
         raise RuntimeError("libdrn.so ABI version mismatch")
     if lib.drn_dit_forward_args_bytes() != ctypes.sizeof(DitForwardArgs) or lib.drn_dit_sub_bytes() != ctypes.sizeof(DitSub):
         raise RuntimeError("libdrn.so: drn_dit_forward_args / drn_dit_sub layout differs from the ctypes mirror in native.py")
+    if lib.drn_gbuffer_edit_map_bytes() != ctypes.sizeof(GbufferEditMap):
+        raise RuntimeError("libdrn.so: drn_gbuffer_edit_map layout differs from the ctypes mirror in native.py")
     _LIB = lib
     return lib
 
@@ -1176,6 +1187,49 @@ def ensemble_reduce_affine_u8(members, affine, mode: str, spread: bool = False):
     _check(load_library().drn_ensemble_reduce_affine_u8(table, N, _ptr(affine), B, clip_bytes, _ptr(out), _ptr(sp),
                                                         ENSEMBLE_MODES[mode], _stream()), "drn_ensemble_reduce_affine_u8")
     return out, sp
+
+
+def _frame_strides(name, t, B, T, frame_shape):
+    """A uint8 tensor [1 or B, 1 or T, *frame_shape] whose frames are contiguous -> (batch stride, frame stride) in bytes, 0 where
+    the axis is broadcast."""
+    assert t.dtype == torch.uint8 and t.ndim == 2 + len(frame_shape) and tuple(t.shape[2:]) == tuple(frame_shape), \
+        f"{name}: uint8 [B, T, {', '.join(str(n) for n in frame_shape)}] required, got {t.dtype} {tuple(t.shape)}"
+    assert t.shape[0] in (1, B) and t.shape[1] in (1, T), f"{name}: {tuple(t.shape[:2])} clips and frames for {(B, T)}"
+    assert t[0, 0].is_contiguous() and t.stride(0) >= 0 and t.stride(1) >= 0, f"{name}: contiguous frames required"
+    return (t.stride(0) if t.shape[0] > 1 else 0), (t.stride(1) if t.shape[1] > 1 else 0)
+
+
+def gbuffer_edit_u8(maps, edit_mask=None, insert_mask=None):
+    """Material edits and layer insertion on 1..5 G-buffers in one launch (drn_gbuffer_edit_u8; the rule and the specification:
+    gbuffer_edit.edit_gbuffers).  maps: a list of (src, dst, layer or None, gain[3], offset[3], is_normal); src and dst uint8
+    [B, T, H, W, 3] on one device with contiguous frames - a batch-strided [:, :keep] view is fine -, dst the same tensor as src
+    (in place) or one that overlaps nothing; layer uint8 [1 or B, 1 or T, H, W, 3].  edit_mask, insert_mask: uint8
+    [1 or B, 1 or T, H, W] or None.  Returns the dsts."""
+    first = maps[0][0]
+    B, T, H, W, _ = first.shape
+    table = (GbufferEditMap * len(maps))()
+    for k, (src, dst, layer, gain, offset, is_normal) in enumerate(maps):
+        e = table[k]
+        assert src.device == first.device and dst.device == first.device and tuple(src.shape) == tuple(dst.shape) == (B, T, H, W, 3), \
+            "the maps of a call are uint8 [B, T, H, W, 3] tensors of one shape on one device"
+        e.src, e.dst = _ptr(src), _ptr(dst)
+        e.src_bs, e.src_ts = _frame_strides("src", src, B, T, (H, W, 3))
+        e.dst_bs, e.dst_ts = _frame_strides("dst", dst, B, T, (H, W, 3))
+        if layer is not None:
+            assert layer.device == first.device, "a layer lives on the maps' device"
+            e.layer = _ptr(layer)
+            e.layer_bs, e.layer_ts = _frame_strides("layer", layer, B, T, (H, W, 3))
+        for c in range(3):
+            e.gain[c], e.offset[c] = float(gain[c]), float(offset[c])
+        e.is_normal = int(bool(is_normal))
+    ms = []
+    for name, m in (("edit_mask", edit_mask), ("insert_mask", insert_mask)):
+        if m is not None:
+            assert m.device == first.device, f"{name} lives on the maps' device"
+        ms.append((0, 0) if m is None else _frame_strides(name, m, B, T, (H, W)))
+    _check(load_library().drn_gbuffer_edit_u8(table, len(maps), _ptr(edit_mask), ms[0][0], ms[0][1], _ptr(insert_mask), ms[1][0],
+                                              ms[1][1], B, T, H * W, _stream()), "drn_gbuffer_edit_u8")
+    return [m[1] for m in maps]
 
 
 def _latent_canvas(name, t):

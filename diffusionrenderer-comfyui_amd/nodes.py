@@ -119,6 +119,31 @@ def _ensemble_inputs():
                                                       "reduced as they are.  Ignored at ensemble = 1"})}
 
 
+def _edit_inputs():
+    """Optional inputs of the relight node for edits between its two stages (gbuffer_edit.py)."""
+    gain = {"default": 1.0, "min": 0.0, "max": 8.0, "step": 0.01}
+    offset = {"default": 0.0, "min": -1.0, "max": 1.0, "step": 0.01}
+    layer = "the inserted object's {} as an IMAGE at the source's or the model's size (one frame for all, or one per frame); needs insert_mask"
+    return {"edit_mask": ("MASK", {"tooltip": "where the material edit applies (1 = fully, 0 = not at all), at the source's or the "
+                                              "model's size, one frame for all or one per frame; none = everywhere"}),
+            "edit_base_color_tint": ("INT", {"default": 0xFFFFFF, "min": 0, "max": 0xFFFFFF, "step": 1, "display": "color",
+                                             "tooltip": "the base colour is multiplied by this colour (0xRRGGBB) / 255, per channel"}),
+            "edit_base_color_gain": ("FLOAT", dict(gain, tooltip="base colour gain (times the tint); 0 plus an offset = a constant")),
+            "edit_roughness_gain": ("FLOAT", dict(gain, tooltip="roughness gain; 0 plus an offset = a constant roughness")),
+            "edit_metallic_gain": ("FLOAT", dict(gain, tooltip="metallic gain; 0 plus an offset of 1 = fully metallic")),
+            "edit_base_color_offset": ("FLOAT", dict(offset, tooltip="added to the base colour, in units of the full range")),
+            "edit_roughness_offset": ("FLOAT", dict(offset, tooltip="added to the roughness, in units of the full range")),
+            "edit_metallic_offset": ("FLOAT", dict(offset, tooltip="added to the metallic map, in units of the full range")),
+            "insert_mask": ("MASK", {"tooltip": "the inserted object's matte (1 = the object, 0 = the scene); required with any "
+                                                "insert_* layer.  The object's G-buffers are composited into the scene's under it "
+                                                "and both are lit together; inserted normals are renormalised"}),
+            "insert_base_color": ("IMAGE", {"tooltip": layer.format("base colour")}),
+            "insert_metallic": ("IMAGE", {"tooltip": layer.format("metallic map")}),
+            "insert_roughness": ("IMAGE", {"tooltip": layer.format("roughness")}),
+            "insert_normal": ("IMAGE", {"tooltip": layer.format("normal map")}),
+            "insert_depth": ("IMAGE", {"tooltip": layer.format("depth")})}
+
+
 def _fit_inputs():
     """Optional inputs of both renderers for clips off the model's grid (fit.py)."""
     return {"fit": (["off", "crop", "stretch"],
@@ -498,7 +523,7 @@ class Cosmos1Relight:
                          "env_spin": ("FLOAT", {"default": 0.0, "min": -720.0, "max": 720.0, "step": 1.0}),
                          "env_sequence": ("BOOLEAN", {"default": False, "tooltip": _ENV_SEQUENCE_TOOLTIP}),
                          **_window_inputs(), **_fit_inputs(), **_tile_inputs(), **_guide_inputs(), **_sampler_inputs(),
-                         **_ensemble_inputs()},
+                         **_ensemble_inputs(), **_edit_inputs()},
         }
 
     RETURN_TYPES = ("IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE", "IMAGE")
@@ -511,12 +536,30 @@ class Cosmos1Relight:
                     window_frames=0, window_overlap=8, fit="off", fit_height=0, fit_width=0, fit_restore=False,
                     tile_height=0, tile_width=0, tile_overlap=64, tile_join="pixel", restore_guide="off", restore_sigma=12.0,
                     env_sequence=False, window_align=False, sampler="euler", steps=0, ensemble=1, ensemble_reduce="median",
-                    step_cache=0.0, ensemble_align=False):
+                    step_cache=0.0, ensemble_align=False, edit_mask=None, edit_base_color_tint=0xFFFFFF, edit_base_color_gain=1.0,
+                    edit_roughness_gain=1.0, edit_metallic_gain=1.0, edit_base_color_offset=0.0, edit_roughness_offset=0.0,
+                    edit_metallic_offset=0.0, insert_mask=None, insert_base_color=None, insert_metallic=None,
+                    insert_roughness=None, insert_normal=None, insert_depth=None):
         """Tiles, and the way they are joined, window_align, the sampler, its steps and step_cache apply to both stages; ensemble,
         ensemble_reduce and ensemble_align to the inverse stage only (the forward stage always renders one sample: averaged renders blur).  The two pipelines may be one object that holds both checkpoints (model_instance = {"inverse": ..., "forward": ...}).
-        restore_guide = 'source': the input picture guides the way back of all six outputs."""
+        restore_guide = 'source': the input picture guides the way back of all six outputs.
+        edit_* / insert_*: the G-buffers are edited on the device between the two stages (gbuffer_edit.py: a gain and offset per
+        material map under edit_mask, the inserted object's layers under insert_mask), on the joined full clip and picture, so
+        windows, tiles, ensembles, samplers and the step cache compose untouched.  The G-buffers returned are the EDITED ones:
+        what the image was rendered from.  With every edit input at its default nothing is built and the call is the one it was."""
         from .fit import plan_fit, plan_restore, restore_frames, restore_frames_guided
+        from .gbuffer_edit import build_edit, check_edit, edit_gbuffers, fit_edit
         tiles = (tile_height, tile_width, tile_overlap)
+        edit = build_edit(standardize_to_5d, edit_mask, edit_base_color_tint, edit_base_color_gain, edit_roughness_gain,
+                          edit_metallic_gain, edit_base_color_offset, edit_roughness_offset, edit_metallic_offset, insert_mask,
+                          insert_base_color, insert_metallic, insert_roughness, insert_normal, insert_depth,
+                          clips=standardize_to_5d(image).shape[0])
+        eplan = None
+        if edit is not None:                    # refused from the settings and shapes alone, before any pipeline or GPU call
+            B, T, H, W = standardize_to_5d(image).shape[:4]
+            if fit != "off":
+                eplan = plan_fit(T, H, W, fit, fit_height, fit_width, windowed=window_frames > 0 and T > window_frames)
+            check_edit(edit, (B, T) + ((H, W) if eplan is None else (eplan.H_out, eplan.W_out)), source_hw=(H, W))
         rplan = None
         if fit != "off" and fit_restore:        # a crop that cut is refused before any GPU work, as the two nodes refuse it
             T, H, W = standardize_to_5d(image).shape[1:4]
@@ -529,6 +572,8 @@ class Cosmos1Relight:
                                         window_align=window_align, sampler=sampler, steps=steps, ensemble=ensemble,
                                         ensemble_reduce=ensemble_reduce, step_cache=step_cache, ensemble_align=ensemble_align)
         gbuffers = [torch.as_tensor(o)[:, :keep] for o in outs]                # in INVERSE_PASSES order
+        if edit is not None:                    # one pass over bytes that are already on the device
+            gbuffers = edit_gbuffers(gbuffers, fit_edit(edit, eplan, gbuffers[0].device))
         # 2. + 3. the forward node on those bytes: fit 'crop' with no target is the identity in space (they are on the grid) and
         # pads time as the forward node would; the way back is the inverse fit's
         names = {"basecolor": "base_color"}

@@ -811,6 +811,43 @@ int drn_ensemble_align_affine(const void* const* members, int N, int B, int64_t 
 int drn_ensemble_reduce_affine_u8(const void* const* members, int N, const void* affine, int B, int64_t clip_bytes, void* dst,
                                   void* spread, int mode, void* stream);
 
+/* ---- relight edits: material edits and layer insertion on the device G-buffers, between the inverse and the forward stage of
+ * Cosmos1Relight (no reference line: the reference has no such seam; the rule and the torch specification: gbuffer_edit.py,
+ * edit_gbuffers).  ONE launch for all maps of a call.  maps: a HOST array of n_maps blocks (they travel to the
+ * kernel by value: no device table); per map src, dst: uint8 [B][T][pixels][3]; layer: the inserted object's map, uint8 of the
+ * same frame shape, or NULL; gain, offset: per channel, offsets on the byte scale; is_normal: the map holds encoded normals.
+ * edit_mask: uint8 [B][T][pixels] or NULL (255 everywhere); insert_mask: the object's matte, likewise, needed with any layer
+ * (without one it is not read).  Every tensor has a batch and a frame stride in BYTES, 0 = that axis is broadcast; a frame itself
+ * is contiguous.  Per map, pixel and channel, with x = src's byte, m_e / m_i the pixel's mask bytes, L the layer's byte,
+ * unit(i) = fp32(i) / 255.0f correctly rounded (fit.u8_unit), every fp32 operation rounded on its own, rint half to even:
+ *   e = u8(rint(clamp(fp32(g * fp32(x)) + o, 0, 255)))        drn_ensemble_reduce_affine_u8's affine: two operations, never an FMA
+ *   y = u8(rint(x + unit(m_e) * (e - x)))                     drn_tile_blend_u8's blend; m_e = 255 gives e, 0 gives x
+ *   z = layer ? u8(rint(y + unit(m_i) * (L - y))) : y
+ *   is_normal, a layer and m_i != 0:  z <- drn_ensemble_reduce_u8's mode 2 on the one pixel z (decode, renormalise, encode)
+ * dst <- z.  A pixel with m_e == 0 and m_i == 0 keeps its bytes in every map; a normal is never renormalised where nothing was
+ * inserted.  dst may be src (with src's strides: in place; a lane whose pixels all have both masks 0 then stores nothing);
+ * otherwise it may overlap nothing.  Nothing outside dst is written.  16 whole pixels per lane (48 bytes of every map and layer,
+ * 16 of every mask, in 16-byte words) where every base and every non-zero stride is on the 16-byte grid, with what pixels % 16
+ * leaves of a frame one pixel per lane; one pixel per lane otherwise - the same bits.  64-bit offsets; the grid is capped at
+ * 2048 blocks that stride over the flat (frame, piece) index.
+ * DRN_EINVAL (nothing launched): a null maps, src or dst; n_maps outside 1..5; B < 1, T < 1, pixels < 0; a layer without
+ * insert_mask; a non-finite gain or offset; a negative stride, a dst stride that lets two of its frames overlap, B T pixels
+ * beyond 2^58; dst overlapping a mask, a layer, another map's src or dst, or its own src other than in place.  pixels == 0:
+ * DRN_OK, nothing launched.  drn_gbuffer_edit_map_bytes: sizeof(drn_gbuffer_edit_map) as compiled (host only). */
+typedef struct drn_gbuffer_edit_map {
+    const void* src;
+    void* dst;
+    const void* layer;
+    int64_t src_bs, src_ts, dst_bs, dst_ts, layer_bs, layer_ts;
+    float gain[3], offset[3];
+    int32_t is_normal;
+    int32_t reserved;
+} drn_gbuffer_edit_map;
+int drn_gbuffer_edit_map_bytes(void);
+int drn_gbuffer_edit_u8(const drn_gbuffer_edit_map* maps, int n_maps, const void* edit_mask, int64_t edit_mask_bs,
+                        int64_t edit_mask_ts, const void* insert_mask, int64_t insert_mask_bs, int64_t insert_mask_ts, int B, int T,
+                        int64_t pixels, void* stream);
+
 /* ---- step cache (step_cache.py: the rule, the controller and the torch / numpy specification; no reference
  * counterpart).  A cached denoising loop runs block 0 on every step, asks how far the residual stream behind it moved since the
  * last computed step, and where it hardly moved adds that step's contribution of blocks 1 .. L-1 instead of running them.
