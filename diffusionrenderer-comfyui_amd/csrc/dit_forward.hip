@@ -8,6 +8,7 @@
 // (cfg 1: a 6.8 ms GPU step) made the host the bound of the denoising loop.  From C the same launches cost the host ~2 ms.
 // Host code only (no kernel lives in this file).
 #include "drn_common.h"
+#include "drn_launchers.h"
 
 // ---- how to cover the (q-block, head) grid with whole rounds of the 256 CUs (was native.attention_plan; measured cost model)
 static const int kCUs = 256;
@@ -286,6 +287,11 @@ struct Forward {
         }
         if (splits > 1)
             return drn_gemm_bf16_splitk(l.a, l.w, l.c, M, N, K, K, K, N, l.epi, l.gate, l.residual, ldr, rpb, splits, a->gemm_ws, stream);
+        // QKV and MLP-up of a clip of 18 432 tokens at D = 4096: 13.5 and 18 rounds of 256 x 256 tiles are 9 and 12 whole rounds of
+        // 384 x 256 ones, measured in this sequence 1.318 -> 1.280 and 1.753 -> 1.736 ms, the step 269.32 -> 265.24 ms
+        // (profiles/harvest_18k.txt 1, 2); same bits.  Out-proj ties and keeps its plan.
+        if (Mb == 18432 && K == 4096 && ((N == 12288 && l.epi == DRN_EPI_NONE) || (N == 16384 && l.epi == DRN_EPI_GELU)))
+            return drn_gemm_bf16_measured384(l.a, l.w, l.c, M, N, K, K, K, N, l.epi, l.gate, l.residual, ldr, rpb, stream);
         return drn_gemm_bf16(l.a, l.w, l.c, M, N, K, K, K, N, l.epi, l.gate, l.residual, ldr, rpb, stream);
     }
 

@@ -19,6 +19,10 @@ void drn_attention16_launch(const void* q, const void* k, const void* v, void* o
 
 // ---- gemm.hip: the process's GEMM settings (gemm_plan.h: the A/B switches, read once; .group = DRN_GEMM_GROUP for the tile launchers)
 const GemmSettings& drn_gemm_settings();
+// ---- gemm.hip: drn_gemm_bf16 with GemmShape::measured384 set (the caller's own A/B stands in for kGemm384Measured)
+int drn_gemm_bf16_measured384(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                              int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
+                              void* stream);
 // ---- gemm256s.hip: 256x256x64 tile, streamed schedule (tile kernel 1), and its fp32 K slices
 int drn_gemm256s_dispatch(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                           int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rpb,

@@ -13,9 +13,11 @@
 // summation tree for the mean and the variance, so they return the same bits and the launcher may pick either by row count:
 //     per lane and chunk: the 8 elements in order;  per lane and GROUP of NCH / 4 chunks: the chunks in order;
 //     per group: the 64-lane butterfly;  total = (G0 + G1) + (G2 + G3).
-//   * ln_modulate_kernel<NCH>:   one wave per row (a row stays in one wave's registers) - many rows;
+//   * ln_modulate_kernel<NCH>:   one wave per row (a row stays in one wave's registers) - D <= 1024, the MXFP8 form with the
+//     pre-add at many rows, and drn_ln_force_kernel(0);
 //   * ln_modulate_kernel4<NCH>:  four waves per row, wave w owns group w, partial sums meet in LDS - few rows (cfg 1: 256 rows
-//     on 64 workgroups of the one-wave kernel took 11.7 us per call, a chain of three memory round trips on a quarter of the CUs).
+//     on 64 workgroups of the one-wave kernel took 11.7 us per call, a chain of three memory round trips on a quarter of the CUs)
+//     and many (18 432 rows: 7 waves per SIMD against 4, see launch_ln_modulate).
 // NCH < 4 (D <= 1024: the tiny test networks) keeps a single butterfly and has no four-wave form.
 // Where the modulated row goes.  MX = false: h [rows, D] bf16 (the kernels as they always were; hq / hs are unused trailing
 // arguments).  MX = true: the same bf16 values quantised as MXFP8 (drn.h: elements hq [rows, D] + one E8M0 byte per 32 columns in
@@ -393,10 +395,11 @@ static int launch_ln_modulate(void* x, const void* add_vec, const void* shift, c
     if (rows == 0) return DRN_OK;
     hipStream_t st = (hipStream_t)stream;
     const int nch = (int)((D + 511) / 512);
-    // few rows: four waves per row (same bits as one wave per row: shared summation tree) - 4 x the waves in flight
-    // (many rows, measured at 18432 x 4096 with tools/lnbench.py: without the pre-add 77-81 us one wave per row, 64-67 us four
-    //  waves per row; with it 82-95 vs 85-95 us: a draw, left on the one-wave kernel)
-    const bool four = nch > 2 && rows < (1ll << 31) && (g_ln_force == 1 || (g_ln_force < 0 && (rows <= 4096 || !add_vec)));
+    // four waves per row (same bits as one wave per row: shared summation tree) - 4 x the waves in flight: few rows, and many rows
+    // too (18432 x 4096, tools/lnbench.py over rotating buffers, profiles/harvest_18k.txt 3: without the pre-add 79.6 us one wave
+    // per row, 58.4 four; with it 105.7 vs 95.6 us - on one buffer pair, which the Infinity Cache then holds, that pair was a
+    // draw).  The MXFP8 form with the pre-add at many rows keeps the one-wave kernel: nobody measured it.  D <= 1024 has one form.
+    const bool four = nch > 2 && rows < (1ll << 31) && (g_ln_force == 1 || (g_ln_force < 0 && (rows <= 4096 || !add_vec || !MX)));
     dim3 grid(four ? (unsigned)rows : (unsigned)((rows + 3) / 4)), block(256);
 #define LAUNCH(K, N)                                                                                                  \
     K<N, MX><<<grid, block, 0, st>>>((bf16_t*)x, (const bf16_t*)add_vec, (const bf16_t*)shift, (const bf16_t*)scale,  \

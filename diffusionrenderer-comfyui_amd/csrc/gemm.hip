@@ -275,6 +275,17 @@ extern "C" int drn_gemm_bf16(const void* A, const void* W, void* C, int64_t M, i
     return gemm_impl(A, W, C, GemmShape{M, N, K, lda, ldw, ldc, ldr, epilogue, rows_per_batch, {62, 0, 62, 0}}, gate, residual, stream);
 }
 
+// drn_gemm_bf16 for a caller that measured the 384 x 256 tile faster than the plan without it on this product, in its own launch
+// sequence and under the gate of profiles/gemm_plan.txt 3: the planner takes that tile if its other rules allow it (preconditions,
+// whole rounds or fewer round-equivalents, DRN_GEMM384 / a forced tile), and plans as ever otherwise.  Not part of the C ABI.
+int drn_gemm_bf16_measured384(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                              int64_t ldc, int epilogue, const void* gate, const void* residual, int64_t ldr, int64_t rows_per_batch,
+                              void* stream) {
+    GemmShape p{M, N, K, lda, ldw, ldc, ldr, epilogue, rows_per_batch, {62, 0, 62, 0}};
+    p.measured384 = true;
+    return gemm_impl(A, W, C, p, gate, residual, stream);
+}
+
 // Same product with operands stored in column blocks ("planes"): logical A[m][k] lives at
 // A + (k / a_block_cols) * a_block_stride + m * lda + k % a_block_cols, logical C[m][n] at
 // C + (n / c_block_cols) * c_block_stride + m * ldc + n % c_block_cols (block_cols = 0: plain).  Block widths are powers of

@@ -42,6 +42,9 @@ struct GemmShape {
     int64_t M, N, K, lda, ldw, ldc, ldr;
     int epilogue;
     int64_t rows_per_batch, blk[4];
+    // the caller measured the 384 x 256 tile faster on THIS product in its own launch sequence (drn_gemm_bf16_measured384: the
+    // DiT forward's block linears, dit_forward.hip) - stands in for an entry on kGemm384Measured, every other rule holds
+    bool measured384 = false;
     bool blocked() const { return blk[0] != 62 || blk[2] != 62; }
     // B clips stacked along the rows: tile kernel and tail split decide the accumulation order of an output element, so both are
     // chosen from ONE clip's rows - a clip then gets the same bits whatever it is batched with (the reference steps its G-buffer
@@ -121,8 +124,9 @@ static inline int gemm_tile_echo(const GemmSettings& s, int kernel) { return (s.
 // workgroup does 1.5 units of work.  Chosen for ONE clip's rows, and only where all of these hold:
 //   * its preconditions (drn_gemm384_ok);
 //   * the 384-row tiling fills whole rounds of the 256 CUs, or costs fewer round-equivalents than the plan without it;
-//   * the shape is on the list of shapes where an interleaved A/B measured it faster than that plan (profiles/gemm384.txt) -
-//     a shape that ties or loses, or that nobody measured, keeps that plan.  (DRN_GEMM384=2 skips this rule: A/B runs.)
+//   * the shape is on the list of shapes where an interleaved A/B measured it faster than that plan (profiles/gemm384.txt), or
+//     the caller says that it measured this product so (GemmShape::measured384) - a shape that ties or loses, or that nobody
+//     measured, keeps that plan.  (DRN_GEMM384=2 skips this rule: A/B runs.)
 struct Gemm384Shape { int64_t M, N, K; };
 static const Gemm384Shape kGemm384Measured[] = {
     {18432, 4096, 16384},                                  // MLP-down at 18 432 tokens: 1.737 -> 1.665 ms
@@ -133,7 +137,7 @@ static inline bool gemm384_choice(const GemmSettings& s, const GemmShape& p, int
     const int64_t t384 = (M / 384) * (p.N / 256);
     const double cost384 = 1.5 * (double)((t384 + 255) / 256);
     if (t384 % 256 != 0 && !(cost384 < cost_without)) return false;
-    if (s.mode384 == 2) return true;
+    if (s.mode384 == 2 || p.measured384) return true;
     for (const Gemm384Shape& m : kGemm384Measured)
         if (m.M == M && m.N == p.N && m.K == p.K) return true;
     return false;

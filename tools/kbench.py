@@ -12,6 +12,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from __graft_entry__ import load_package  # noqa: E402
+from tools.abgate import gate as ab_gate  # noqa: E402
 
 
 def main():
@@ -27,6 +28,7 @@ def main():
                     "they come from HBM, not from the 256 MB Infinity Cache, as inside the model (4-6 copies)")
     ap.add_argument("--splitk", type=int, default=0, help="gemm: 1 = take the split-K path where drn_gemm_splitk_choice says so (few tokens)")
     ap.add_argument("--shapes", default="", help="attention: comma list of kernel bodies to time in one process (0 = 32x32x16, 1 = 16x16x32)")
+    ap.add_argument("--qkv-split", action="store_true", help="gemm: also time QKV as two calls, [q|k] on tile 1 and [v] on tile 5")
     ap.add_argument("--diag", default="", help="attention: library built with -DATT_DIAG=1; prints the per-segment cycle shares")
     args = ap.parse_args()
     pkg = load_package()
@@ -113,6 +115,19 @@ def main():
                 lib.drn_gemm_force_tile(-1)
                 assert rc == 0, rc
               cases.append((f"gemm {nm} [{S}x{K}]x[{Nn}x{K}] tile {tile}", run_gemm, 2.0 * S * Nn * K))
+            if nm == "qkv" and args.qkv_split:
+              # the other whole-round form of QKV: [q|k] (N = 2D) on the 256^2 kernel, [v] (N = D) on the 384-row kernel, two
+              # calls on column slices of one C (ldc stays 3D) - what a two-launch plan would run, timed before anyone builds it
+              def run_split(lib, As=As, Ws=Ws, C=C, Nn=Nn, K=K, turn=turn):
+                turn[0] = (turn[0] + 1) % len(As)
+                A, Wt = As[turn[0]], Ws[turn[0]]
+                for tile, col0, cols in ((1, 0, 2 * D), (5, 2 * D, D)):
+                    lib.drn_gemm_force_tile(tile)
+                    rc = lib.drn_gemm_bf16(A.data_ptr(), Wt.data_ptr() + 2 * col0 * K, C.data_ptr() + 2 * col0, S, cols, K, K, K, Nn, 0,
+                                           None, None, Nn, S, st)
+                    lib.drn_gemm_force_tile(-1)
+                    assert rc == 0, rc
+              cases.append((f"gemm {nm} [{S}x{K}]x[{Nn}x{K}] tile 1[q|k]+5[v]", run_split, 2.0 * S * Nn * K))
     if args.diag and "attn" in args.what:
         lib = ctypes.CDLL(os.path.abspath(args.diag))
         for name, at in N.SIGNATURES.items():
@@ -177,6 +192,12 @@ def main():
                 med, mn = t[len(t) // 2], t[0]
                 print(f"{name:46s} {os.path.basename(path):28s} median {med:8.3f} ms  {fl/med/1e9:8.1f} TF/s   min {mn:8.3f} ms {fl/mn/1e9:8.1f} TF/s"
                       f"   max {t[-1]:8.3f} ms", flush=True)
+        # the gate (abgate.py): every other member of the group against its first (the first tile on the first library)
+        for c, (name, fn, fl) in enumerate(members):
+            for i, path in enumerate(libs):
+                if (c, i) != (0, 0):
+                    print(f"    {name.split(' tile ')[-1] if ' tile ' in name else name} {os.path.basename(path)} vs "
+                          f"{members[0][0].split(' tile ')[-1] if ' tile ' in name else 'first'}: {ab_gate(times[(0, 0)], times[(c, i)])[1]}", flush=True)
 
 
 if __name__ == "__main__":
